@@ -8,7 +8,7 @@ intervals into 16 k-mer spectra (minimizers -> jump hash -> spectrum), the spect
 count-min update, and ONE pass over the CWS table applies all 16 histosketch updates in interval order —
 bit-identical to flushing after every 100k reads (tests/test_gpu_parity.py).  The flush of step n
 runs on a second stream under the minimizer kernels of step n+1.  Default K=20 steps = 32 M reads
-(C2's 10 M reads = 6.25 steps; `value_cold` is C2 exactly as stated: 10 M reads, fresh context, no warm-up).
+(C2's 10 M reads = 6.25 steps; `value_cold`, a --full leg, is C2 exactly as stated: 10 M reads, fresh context, no warm-up).
 
 N>1: one process per GPU; the exchange between the ranks is INSIDE libhulkhip.so (hulk_comm_init: RCCL over xGMI;
 hulk_step_sharded / hulk_step_sliced, include/hulk_hip.h) — torch.distributed only carries the rendezvous (the 128-byte
@@ -24,7 +24,7 @@ rule, pipeline/sketch.go:211-215), so every mode but `sliced-weak` computes the 
   sliced-strong (SURVEY.md 8e to the letter): a step = 16 intervals, rank g bins reads [g*I/N, (g+1)*I/N) of every interval,
       ONE all-reduce (uint32 sum) of the 16 spectra per step; total work fixed as N grows.
   sliced-weak: every rank bins 100k reads per interval, i.e. the global interval is N x 100k — another sketch than C2's.
-  At N > 1 the modes not used for the headline are timed too (`other_scaling`), and `value_c4` is BASELINE configs[3]:
+  With --full at N > 1 the modes not used for the headline are timed too (`other_scaling`), and `value_c4` is BASELINE configs[3]:
   50 M reads per rank (400 M at N = 8) through the sharded steps on fresh contexts, ragged last step, the clock stopped
   after the EOF gather of the sketch.
 HULK_BENCH_TRANSPORT=gloo (test aid): the ranks share GPU 0 and the library's HOST transport carries the exchange over gloo
@@ -35,9 +35,11 @@ tests/cpp/libfakerccl.so (HULK_RCCL_LIB); torch.distributed (control plane: barr
 
 Passes, in order: discarded ones (the first pass of a process measures low, and a GPU fresh from idle for seconds: one
 pass + HULK_BENCH_PREWARM_S = 2 s of them), then the HEADLINE (W warm-up + K timed steps between barriers, no event
-brackets in it), then the secondary legs, each of them fault-isolated: `kernels` (the same steps with every kernel alone on
-one stream and bracketed by HIP events: the durations the roofline objects are computed from), `value_unpruned`,
-`ms_per_step_long` (>= 200 steps), at N = 1 `value_cold`, `c3`, `c5`, the end-to-end file figures and the CPU baseline, at
+brackets in it).  A plain run ends there: with --dump-outputs DIR it writes what the timed pass computed (the sketch after
+its last step and the count-min counters, float64 .npy files; the input is the same synthetic stream on every run with the
+same arguments), then it prints the line.  Only with --full come the secondary legs, each of them fault-isolated:
+`kernels` (the same steps with every kernel alone on one stream and bracketed by HIP events: the durations the roofline
+objects are computed from), `value_unpruned`, `ms_per_step_long` (>= 200 steps), at N = 1 `value_cold`, `c3`, `c5`, the end-to-end file figures and the CPU baseline, at
 N > 1 the other modes and `value_c4`.  A leg that raises leaves `"<leg>_error": "<text>"` in the line and the run goes on;
 a leg that hangs (a rank stuck in a collective) is ended by a watchdog on every rank after HULK_BENCH_LEG_TIMEOUT_S
 (default 300) seconds: rank 0 prints the line with what it has and every rank exits 0.  HULK_BENCH_FAIL=<leg>[,<leg>] makes
@@ -157,6 +159,14 @@ def cpu_baseline(sample_intervals=4):
             "nproc": nproc, "cpu_model": cpu_model(),
             "single_thread": {"value": n / dt1, "unit": "reads/s", "cores": 1, "seconds": dt1},
             "reference_binary": "unavailable: no Go toolchain on this box, the reference's modules are not vendored"}
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (exact here: slot minima are bin indices < k^4, the count-min
+    counters integers far below 2^53)"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def self_spawn(args):
@@ -333,6 +343,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the secondary legs too (kernel durations and rooflines, value_unpruned, the long "
+                         "pass, value_cold, C3, C5, long reads, end-to-end file figures, the CPU baseline; at N > 1 the other modes "
+                         "and value_c4; the --no-* switches below pick among them).  Without it only the headline is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed pass computed to DIR/<name>.npy (float64): sketch_mins, sketch_weights (the sketch "
+                         "after its last step) and countmin (the count-min counters, 7 x 2000)")
     ap.add_argument("--mode", choices=("sharded", "sliced-strong", "sliced-weak"), default="sharded",
                     help="N > 1: how the global stream is shared (see the module docstring); at N = 1 all three are the same "
                          "work and the plain single-GPU calls are used unless --force-collective")
@@ -574,11 +591,11 @@ def main():
         sk.comm_init_host(rank, world, gloo_exchange(dist, host_group[0]))
         return sk
 
-    def run_pass(prune, inp=None, brackets=0, serial=False, n_steps=None):
+    def run_pass(prune, inp=None, brackets=0, serial=False, n_steps=None, want_cms=False):
         """warm-up + the timed K steps on a fresh context; prune=False disables the exact bounds of the CWS stage
         (HULK_FLAG_NO_PRUNE), so that every interval streams the whole table like the reference does; serial=True puts the
         flush on the work stream and bins a batch in one piece (HULK_FLAG_NO_OVERLAP: every kernel alone); brackets: the
-        hulk_set_profiling mask of the timed steps (0 = none)."""
+        hulk_set_profiling mask of the timed steps (0 = none); want_cms: the count-min counters are read back too."""
         bufs, offs, per, n_step, in_mode = inp if inp is not None else main_input
         k_steps = n_steps or steps
         comm = use_dist or loop_world
@@ -654,9 +671,10 @@ def main():
         counters = sk.counters()
         mins, weights = sk.gather_sketch() if (comm and not loop_world) else sk.sketch()
         cstats = sk.comm_stats() if comm else None
+        cms = sk.cms() if want_cms else None
         sk.close()
         return dict(elapsed=elapsed, steps=k_steps, prof=prof, counters=counters, mins=mins, weights=weights, tiles0=tiles0,
-                    tiles1=tiles1, comm=cstats, table=table)
+                    tiles1=tiles1, comm=cstats, table=table, cms=cms)
 
     def run_cold():
         """C2 exactly as BASELINE.json states it: 10 M reads, interval 100k, through the interval rule of
@@ -932,7 +950,7 @@ def main():
             sys.stderr.write(f"repeat {i}: {r['elapsed'] / steps * 1e3:.4f} ms/step\n")
     # ---- the HEADLINE: W warm-up + K timed steps, no event brackets (every bracket costs the stream two event records:
     # k_minimizer_fast's alone was 2 % of a step)
-    main_pass = run_pass(not args.no_prune, brackets=0)
+    main_pass = run_pass(not args.no_prune, brackets=0, want_cms=bool(args.dump_outputs))
     elapsed, counters = main_pass["elapsed"], main_pass["counters"]
     mins, weights = main_pass["mins"], main_pass["weights"]
     total_reads = steps * reads_per_step
@@ -987,6 +1005,23 @@ def main():
     out["survey_model"] = {"bytes_per_read": model_bytes, "reads_per_s_at_hbm_peak": HBM_PEAK_GBS * 1e9 * world / model_bytes,
                            "value_over_model": value * model_bytes / 1e9 / (HBM_PEAK_GBS * world)}
     state["headline_done"] = True
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sketch_mins": mins, "sketch_weights": weights, "countmin": main_pass["cms"]})
+
+    def finish():
+        for name, err in leg_errors.items():
+            out[f"{name}_error"] = err
+        state["leg"], state["kick"] = "exit", time.monotonic()
+        print_line()
+        if use_dist:
+            try:
+                dist.destroy_process_group()
+            except Exception:             # noqa: BLE001 — the line is out; a rank that left a collective early must not turn that into rc != 0
+                pass
+
+    if not args.full:                  # a plain run: the headline is all it measures
+        finish()
+        return
 
     # ---- leg `kernels`: the same steps, every kernel alone (one stream, one piece per batch) and bracketed by HIP events on
     # the stream it runs on: the launch durations the roofline objects are computed from
@@ -1223,15 +1258,7 @@ def main():
             out["speedup_vs_cpu"] = value / cb["value"]
             if out.get("value_cold"):
                 out["speedup_vs_cpu_cold"] = out["value_cold"] / cb["value"]
-    for name, err in leg_errors.items():
-        out[f"{name}_error"] = err
-    state["leg"], state["kick"] = "exit", time.monotonic()
-    print_line()
-    if use_dist:
-        try:
-            dist.destroy_process_group()
-        except Exception:             # noqa: BLE001 — the line is out; a rank that left a collective early must not turn that into rc != 0
-            pass
+    finish()
 
 
 if __name__ == "__main__":

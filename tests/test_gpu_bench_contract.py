@@ -2,6 +2,7 @@
 sharded-step path through RCCL at world size 1; and `bench.py --gpus 2` / `--gpus 8` END TO END — self-spawn, the pre-warm
 agreement, the other modes, value_c4 with ranks that hold none of the ragged last step, and the JSON relay — with all ranks
 on this box's one GPU over the library's host transport (HULK_BENCH_TRANSPORT=gloo)."""
+import hashlib
 import json
 import os
 import subprocess
@@ -27,7 +28,8 @@ def _keep(name, p):
         pass
 
 
-def _run(extra, env_extra=None, timeout=900):
+def _run(extra, env_extra=None, timeout=900, full=True):
+    """one bench.py run at N = 1; full: with --full (the secondary legs), else the plain run the driver times"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HULK_BENCH_PREWARM_S="0",   # (no need to warm the GPU for a contract test)
                HULK_BENCH_LONG_STEPS="6")
     env.update(env_extra or {})
@@ -35,6 +37,8 @@ def _run(extra, env_extra=None, timeout=900):
         extra = [x for x in extra if x != "--c3"]
     else:
         extra = extra + ["--no-c3", "--no-c5", "--no-long-reads"]
+    if full:
+        extra = ["--full"] + extra
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2"] + extra,   # (2: both work lanes have run once before the clock starts)
                        capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -157,6 +161,33 @@ def test_bench_line_survives_any_secondary_leg():
     assert c["sketch_md5"] == ok["sketch_md5"] and "timeout" in c["kernels_error"] and c["roofline"] is None
 
 
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full a run is setup, the discarded passes and the headline: none of the secondary legs' keys in the line.
+    --dump-outputs writes the sketch the timed pass ended with and the count-min counters as float64 .npy files — the
+    sketch the line's sketch_md5 names — and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    a = _run(["--dump-outputs", str(tmp_path / "a")], full=False)
+    for k in REQUIRED:
+        assert k in a, k
+    assert a["steps"] == 3 and a["warmup"] == 2 and a["roofline"] is None
+    assert abs(a["ms_per_step"] * a["value"] / 1e3 - a["config"]["reads_per_step"]) < 1.0
+    assert not [k for k in a if k.endswith("_error")], [k for k in a if k.endswith("_error")]
+    for gone in ("ms_per_step_kernels_alone", "value_unpruned", "ms_per_step_long", "value_cold", "c3", "long_reads", "c5", "e2e",
+                 "cpu_baseline", "other_scaling", "value_c4"):
+        assert gone not in a, gone
+    b = _run(["--dump-outputs", str(tmp_path / "b")], full=False)
+    assert b["sketch_md5"] == a["sketch_md5"]
+    shapes = {"sketch_mins": (512,), "sketch_weights": (512,), "countmin": (7, 2000)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in shapes)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    for name, shape in shapes.items():
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype == np.float64 and x.shape == shape and np.array_equal(x, y), name
+    mins = np.load(tmp_path / "a" / "sketch_mins.npy")
+    assert hashlib.md5(mins.astype("<u8").tobytes()).hexdigest() == a["sketch_md5"]
+    assert np.load(tmp_path / "a" / "countmin.npy").sum() > 0
+
+
 def test_bench_says_so_when_rccl_cannot_be_bound():
     """hulk_comm_init failing (here: HULK_RCCL_LIB names a file that is not there) must not leave a scaling run without a
     line: every rank learns of it, the run goes over the library's host transport on a gloo group and the line says so."""
@@ -189,7 +220,7 @@ def test_bench_world_two_end_to_end_on_one_gpu(transport):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(HULK_BENCH_TRANSPORT=transport, HULK_BENCH_PREWARM_S="0.3", HULK_BENCH_C4_READS_PER_RANK="4100000")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     _keep("world_two_" + transport, p)                        # (what the two ranks printed: gpurun_out/contract_world_two_<transport>.txt)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -227,7 +258,7 @@ def test_bench_world_eight_end_to_end_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(HULK_BENCH_TRANSPORT="gloo", HULK_BENCH_PREWARM_S="0", HULK_BENCH_C4_READS_PER_RANK="1850000", HULK_BENCH_LONG_STEPS="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=1800, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1800, env=env, cwd=ROOT)
     _keep("world_eight", p)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

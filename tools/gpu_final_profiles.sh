@@ -11,11 +11,11 @@ run() { # name, bench args, env...
   cp gpurun_out/prof_bench/bench.json $O/$name.bench.json
   rm -rf gpurun_out/prof_bench
 }
-TITLE="Round ${R#r0}: default configuration (two streams, CWS-scan bounds on)" CMD="python bench.py --no-cpu-baseline --no-cold --no-e2e --no-c3 --no-c5 --no-long-reads --single-pass" run ${R}_kernel_stats "" A=1
-TITLE="Round ${R#r0}: each kernel alone (HULK_NO_OVERLAP=1), CWS-scan bounds on" CMD="HULK_NO_OVERLAP=1 python bench.py --no-cpu-baseline --no-cold --no-e2e --no-c3 --no-c5 --no-long-reads --single-pass" run ${R}_kernel_stats_serial "" HULK_NO_OVERLAP=1
-TITLE="Round ${R#r0}: each kernel alone (HULK_NO_OVERLAP=1), CWS-scan bounds OFF (bench.py --no-prune = HULK_FLAG_NO_PRUNE on the timed context)" CMD="HULK_NO_OVERLAP=1 python bench.py --no-cpu-baseline --no-cold --no-e2e --no-c3 --no-c5 --no-long-reads --no-prune" run ${R}_kernel_stats_serial_noprune "--no-prune" HULK_NO_OVERLAP=1
+TITLE="Round ${R#r0}: default configuration (two streams, CWS-scan bounds on)" CMD="python bench.py --full --no-cpu-baseline --no-cold --no-e2e --no-c3 --no-c5 --no-long-reads --single-pass" run ${R}_kernel_stats "" A=1
+TITLE="Round ${R#r0}: each kernel alone (HULK_NO_OVERLAP=1), CWS-scan bounds on" CMD="HULK_NO_OVERLAP=1 python bench.py --full --no-cpu-baseline --no-cold --no-e2e --no-c3 --no-c5 --no-long-reads --single-pass" run ${R}_kernel_stats_serial "" HULK_NO_OVERLAP=1
+TITLE="Round ${R#r0}: each kernel alone (HULK_NO_OVERLAP=1), CWS-scan bounds OFF (bench.py --no-prune = HULK_FLAG_NO_PRUNE on the timed context)" CMD="HULK_NO_OVERLAP=1 python bench.py --full --no-cpu-baseline --no-cold --no-e2e --no-c3 --no-c5 --no-long-reads --no-prune" run ${R}_kernel_stats_serial_noprune "--no-prune" HULK_NO_OVERLAP=1
 HULK_NO_OVERLAP=1 bash tools/gpu_pmc.sh > $O/pmc_print.txt 2>&1
 python tools/pmc_to_json.py gpurun_out/pmc $O/${R}_pmc.json
 rm -rf gpurun_out/pmc
-python bench.py > $O/bench_$R.json 2> $O/bench_$R.err
+python bench.py --full > $O/bench_$R.json 2> $O/bench_$R.err
 ls -la $O

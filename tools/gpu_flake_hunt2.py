@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Hunt for the intermittent failure of the multi-rank bench run (commit 51a2aa5: "one unexplained failure in ~60 runs" of
 tests/test_gpu_bench_contract.py::test_bench_world_two_end_to_end_on_one_gpu, its text lost): the SAME invocation the test makes
-— `python bench.py --gpus W --steps 3 --warmup 1 --no-cpu-baseline` with all ranks on GPU 0 — N times, JOBS at a time (several
+— `python bench.py --gpus W --steps 3 --warmup 1 --full --no-cpu-baseline` with all ranks on GPU 0 — N times, JOBS at a time (several
 runs side by side load the box the way a busy node would), every run checked the way the test checks it: exit status 0, ONE
 JSON line, no `<leg>_error` key, the sharded sketch's MD5 equal in every run, hulk_get_comm_health all zero.  The complete
 stdout + stderr of every failing run is kept under gpurun_out/flake/ and the tally is printed (-> profiles/r06_flake.txt).
@@ -39,7 +39,7 @@ def one(i):
     t0 = time.time()
     try:
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(a.world), "--steps", "3" if a.world == 2 else "2",
-                            "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                            "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
         rc, so, se = p.returncode, p.stdout, p.stderr
     except subprocess.TimeoutExpired as e:
         rc, so, se = -999, (e.stdout or b"").decode("utf-8", "replace") if isinstance(e.stdout, bytes) else (e.stdout or ""), \

@@ -3,7 +3,7 @@
 O=gpurun_out; mkdir -p $O
 timeout 2400 python -m pytest tests -q -m gpu -x > $O/r6z_full.txt 2>&1; echo "full suite rc=$?"; tail -4 $O/r6z_full.txt | head -2
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py > $O/r6z_bench.json 2> $O/r6z_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/r6z_bench.json 2> $O/r6z_bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r6z_bench.json").read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ for k in ('reads_5kb', 'contigs_500kb'):
     if x: print('%-34s %-14s %.3g bases/s  kernels alone (us per Gbase): %s  sketch %s' % (tag, k, x['bases_per_s'], x['kernels_alone']['us'], x['sketch_md5'][:8]))
 if d.get('long_reads_error'): print(tag, 'ERROR', d['long_reads_error'])
 PY
-B="python bench.py --no-c3 --no-c5 --no-e2e --no-cpu-baseline --no-cold --single-pass"
+B="python bench.py --full --no-c3 --no-c5 --no-e2e --no-cpu-baseline --no-cold --single-pass"
 echo "# (1) where k_long_emit's time goes (two-pass form; sketches of the ablated runs are wrong by design)"
 for D in 0 4 2; do HULK_LIB=exp HULK_LONG_TWO_PASS=1 HULK_K1_DEBUG=$D $B 2>/dev/null | python /tmp/lr_print.py "two-pass, HULK_K1_DEBUG=$D"; done
 echo "# (2) the tile kernel (shipping library) against the two-pass form (profiling build)"

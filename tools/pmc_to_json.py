@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """gpurun_out/pmc/**/counter_collection.csv (tools/gpu_pmc.sh) -> profiles/rNN_pmc.json
 Per-launch averages per kernel over the launches of the timed region and the warm-up of
-`bench.py --no-cpu-baseline --no-cold --single-pass --steps 5 --warmup 1` (16 intervals = 1.6e6 reads per launch).
+`bench.py --full --no-cpu-baseline --no-cold --single-pass --steps 5 --warmup 1` (16 intervals = 1.6e6 reads per launch).
 
 HBM bytes follow MI355X_MICROARCH.md's rocprofv3 section: FETCH_SIZE / WRITE_SIZE come from separate --pmc passes and are
 reported in KiB; on gfx950 FETCH_SIZE reads HALF of the fetched bytes (calibrated here on k_build_k32: 2.39 GB read ->
@@ -44,7 +44,7 @@ for f in sorted(glob.glob(src + "/sq/**/*kernel_trace.csv", recursive=True)):
             dur[m.group(1)].append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
 doc = {
     "source": "rocprofv3 --kernel-trace --pmc <set> (separate passes: FETCH_SIZE | WRITE_SIZE | SQ_* | VALU | LDS | TCC_* | GRBM) -- "
-              "python bench.py --no-cpu-baseline --no-cold --single-pass --steps 5 --warmup 1  (tools/gpu_pmc.sh, "
+              "python bench.py --full --no-cpu-baseline --no-cold --single-pass --steps 5 --warmup 1  (tools/gpu_pmc.sh, "
               "tools/pmc_to_json.py); per-launch averages",
     "reads_per_launch": reads_per_launch,
     "units": "FETCH_SIZE/WRITE_SIZE as reported (KiB); hbm_bytes_per_launch = (2*FETCH_SIZE + WRITE_SIZE)*1024 - gfx950 "
