@@ -41,7 +41,7 @@ ABI_SYMBOLS = (
     "hulk_comm_unique_id", "hulk_comm_init", "hulk_comm_init_host", "hulk_comm_init_loopback", "hulk_step_sharded", "hulk_step_sharded_host",
     "hulk_step_sliced", "hulk_gather_sketch", "hulk_get_comm_stats", "hulk_get_comm_health", "hulk_release_caches", "hulk_get_device_checks", "hulk_get_profile_table",
     "hulk_load_sketches", "hulk_sketch_set_free", "hulk_sketch_set_info", "hulk_sketch_set_mins", "hulk_sketch_set_weights", "hulk_sketch_set_path",
-    "hulk_sketch_set_banner", "hulk_smash_files",
+    "hulk_sketch_set_banner", "hulk_smash_files", "hulk_bgzf_inflate",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -63,7 +63,7 @@ class IngestStats(ctypes.Structure):
                 ("bytes_in", ctypes.c_uint64), ("seconds", ctypes.c_double)]
 
 
-HULK_INGEST_GZ_ONE_THREAD, HULK_INGEST_GZ_ZLIB, HULK_INGEST_TRACE, HULK_INGEST_HOST_PARSER = 1, 2, 4, 8
+HULK_INGEST_GZ_ONE_THREAD, HULK_INGEST_GZ_ZLIB, HULK_INGEST_TRACE, HULK_INGEST_HOST_PARSER, HULK_INGEST_DEVICE_INFLATE = 1, 2, 4, 8, 16
 
 
 class IngestOpts(ctypes.Structure):
@@ -231,6 +231,9 @@ def load():
     L.hulk_sketch_files_opts.restype = ctypes.c_int
     L.hulk_sketch_files_opts.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), u32, ctypes.c_int, ctypes.POINTER(IngestOpts),
                                          ctypes.POINTER(IngestStats)]
+    L.hulk_bgzf_inflate.restype = ctypes.c_int
+    L.hulk_bgzf_inflate.argtypes = [ctypes.c_char_p, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                    ctypes.c_char_p, u64]
     L.hulk_comm_unique_id.restype = ctypes.c_int; L.hulk_comm_unique_id.argtypes = [vp]
     L.hulk_comm_init.restype = ctypes.c_int; L.hulk_comm_init.argtypes = [vp, vp, u32, u32]
     L.hulk_comm_init_host.restype = ctypes.c_int; L.hulk_comm_init_host.argtypes = [vp, u32, u32, EXCHANGE_FN, vp]

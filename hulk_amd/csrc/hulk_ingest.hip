@@ -41,6 +41,7 @@
 #include "par_inflate.h"
 #include "crc32_clmul.h"
 #include "hulk_fastq.h"
+#include "hulk_bgzf.h"
 
 namespace {
 
@@ -58,6 +59,7 @@ struct IngestCfg {
     bool zlib = false;                        // zlib's inflate instead of fast_inflate.h
     bool trace = false;                       // per-phase seconds on stderr
     bool host_parser = false;                 // FASTQ lines -> reads on the host's parser threads instead of the device
+    bool dev_inflate = false;                 // the device parsers: bgzip'd files inflated on the GPU (hulk_bgzf.hip)
     bool block_set = false, readers_set = false;   // the caller (or the environment) chose; else the device path takes its own defaults
 };
 static IngestCfg resolve_cfg(const hulk_ingest_opts *o, uint32_t threads) {
@@ -73,6 +75,7 @@ static IngestCfg resolve_cfg(const hulk_ingest_opts *o, uint32_t threads) {
         if (o->flags & HULK_INGEST_GZ_ZLIB) c.zlib = true;
         if (o->flags & HULK_INGEST_TRACE) c.trace = true;
         if (o->flags & HULK_INGEST_HOST_PARSER) c.host_parser = true;
+        if (o->flags & HULK_INGEST_DEVICE_INFLATE) c.dev_inflate = true;
     }
     if (!o || !o->gz_threads) {                   // the default of 16 inflate threads is for hosts that have them
         const long hw = (long)std::thread::hardware_concurrency();
@@ -82,6 +85,7 @@ static IngestCfg resolve_cfg(const hulk_ingest_opts *o, uint32_t threads) {
     if (const char *e = getenv("HULK_GZ_THREADS")) c.gz_threads = (unsigned)std::max(1L, strtol(e, nullptr, 10));
     if (const char *e = getenv("HULK_GZ_PAR")) c.gz_par = !(e[0] == '0');
     if (const char *e = getenv("HULK_GZ_PAR_CHUNK")) c.gz_chunk = (size_t)strtoull(e, nullptr, 10);
+    if (const char *e = getenv("HULK_GZ_DEVICE")) c.dev_inflate = !(e[0] == '0');
     if (const char *e = getenv("HULK_INGEST_READERS")) { c.readers = (unsigned)std::max(1L, strtol(e, nullptr, 10)); c.readers_set = true; }
     if (getenv("HULK_GZ_ZLIB")) c.zlib = true;
     if (getenv("HULK_INGEST_TRACE")) c.trace = true;
@@ -97,7 +101,7 @@ static IngestCfg resolve_cfg(const hulk_ingest_opts *o, uint32_t threads) {
 // the header states are refused, not clamped (an empty string: the options are fine)
 static std::string check_opts(const hulk_ingest_opts *o) {
     if (!o) return std::string();
-    if (o->flags & ~(HULK_INGEST_GZ_ONE_THREAD | HULK_INGEST_GZ_ZLIB | HULK_INGEST_TRACE | HULK_INGEST_HOST_PARSER)) return "hulk_ingest_opts: unknown flags";
+    if (o->flags & ~(HULK_INGEST_GZ_ONE_THREAD | HULK_INGEST_GZ_ZLIB | HULK_INGEST_TRACE | HULK_INGEST_HOST_PARSER | HULK_INGEST_DEVICE_INFLATE)) return "hulk_ingest_opts: unknown flags";
     if (o->reserved[0] || o->reserved[1]) return "hulk_ingest_opts: reserved must be 0";
     if (o->parser_threads > 256) return "hulk_ingest_opts: parser_threads must be 0 (default) or 1..256";
     if (o->gz_threads > 64) return "hulk_ingest_opts: gz_threads must be 0 (default) or 1..64";
@@ -484,23 +488,7 @@ class GzBgzf : public GzStream {
  public:
     unsigned threads() const { return cfg_.gz_threads; }
     // total size of the member whose header starts at p (n bytes available), 0 = not a BGZF member / header incomplete
-    static size_t member_size(const uint8_t *p, size_t n, size_t *header_len) {
-        if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return 0;       // FEXTRA and nothing else
-        const size_t xlen = (size_t)p[10] | ((size_t)p[11] << 8);
-        if (n < 12 + xlen) return 0;
-        size_t bsize = 0; bool found = false;
-        for (size_t o = 12; o + 4 <= 12 + xlen;) {
-            const size_t sl = (size_t)p[o + 2] | ((size_t)p[o + 3] << 8);
-            if (o + 4 + sl > 12 + xlen) return 0;
-            if (p[o] == 'B' && p[o + 1] == 'C' && sl == 2 && !found) { bsize = (size_t)p[o + 4] | ((size_t)p[o + 5] << 8); found = true; }
-            o += 4 + sl;
-        }
-        if (!found) return 0;
-        const size_t total = bsize + 1;
-        if (total < 12 + xlen + 2 + 8) return 0;                   // header + the shortest deflate stream + trailer
-        *header_len = 12 + xlen;
-        return total;
-    }
+    static size_t member_size(const uint8_t *p, size_t n, size_t *header_len) { return hulk::bgzf::member_size(p, n, header_len); }
     static bool looks_like(int fd) {
         uint8_t h[64];
         const ssize_t m = ::pread(fd, h, sizeof h, 0);
@@ -548,8 +536,8 @@ class GzBgzf : public GzStream {
 
  private:
     IngestCfg cfg_;                                          // this run's knobs (resolve_cfg)
-    static constexpr size_t IN_BATCH = 8u << 20, MAX_ISIZE = 1u << 16;
-    struct Member { size_t hdr_off, in_off, in_len, out_off; uint32_t crc, isize; };
+    static constexpr size_t IN_BATCH = 8u << 20;
+    using Member = hulk::bgzf::Member;
     struct Batch {
         PageBuf in, out; std::vector<Member> mem;      // (huge-page mappings, not zero-filled by one thread: 16 inflate threads touch them first)
         size_t out_len = 0, off = 0; off_t hand_over = -1; bool eof = false, any_member = false; std::string err;
@@ -593,20 +581,8 @@ class GzBgzf : public GzStream {
             }
             if (got == 0) { b->eof = true; publish(b); return; }
             // the members that lie in this piece of the file, whole
-            size_t o = 0, out_total = 0;
-            while (o < got) {
-                size_t hl = 0;
-                const size_t total = member_size(b->in.data() + o, got - o, &hl);
-                if (total == 0 || o + total > got) break;
-                Member m;
-                m.hdr_off = o; m.in_off = o + hl; m.in_len = total - hl - 8; m.out_off = out_total;
-                const uint8_t *t = b->in.data() + o + total - 8;
-                m.crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-                m.isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-                if (m.isize > MAX_ISIZE) break;
-                b->mem.push_back(m);
-                out_total += m.isize; o += total;
-            }
+            size_t out_total = 0;
+            const size_t o = hulk::bgzf::frame(b->in.data(), got, b->mem, SIZE_MAX, SIZE_MAX, &out_total);
             // (a member cut by the end of the piece starts the next piece; one cut by the end of the FILE, or not a BGZF member, is
             // then the first thing of a piece: the sequential reader's from there on)
             if (b->mem.empty()) { b->hand_over = pos; publish(b); return; }
@@ -1051,9 +1027,14 @@ class ByteSource {
         stdin_mode_ = paths_.empty();
     }
     ~ByteSource() { close_current(); }
+    // HULK_INGEST_DEVICE_INFLATE: a regular file whose first member is BGZF is inflated on the device (hulk_bgzf.hip); its
+    // text is then delivered to device memory (read's `ddst`) instead of `dst`
+    void set_device_inflate(hulk::bgzf::DevBufs *b) { dev_bufs_ = b; }
 
-    // up to cap bytes into dst; 0 = all inputs exhausted; -1 = error
-    long read(uint8_t *dst, size_t cap, IngestError &err) {
+    // up to cap bytes into dst; 0 = all inputs exhausted; -1 = error.  With `ddst` (device memory for up to cap bytes), bytes that
+    // are device text go there and *on_dev says so.
+    long read(uint8_t *dst, size_t cap, IngestError &err, uint8_t *ddst = nullptr, bool *on_dev = nullptr) {
+        if (on_dev) *on_dev = false;
         for (;;) {
             if (!open_) {
                 if (stdin_mode_) { if (stdin_done_) return 0; fd_ = 0; open_ = true; is_gz_ = false; }
@@ -1068,6 +1049,17 @@ class ByteSource {
                 std::string msg;
                 n = gzf_->read(dst, cap, msg);
                 if (n < 0) { err.set(HULK_ERR_IO, msg); return -1; }
+            } else if (dgz_) {
+                std::string msg;
+                uint8_t last = last_;
+                n = dgz_->read(ddst, cap, &last, msg);
+                if (n < 0) { err.set(HULK_ERR_HIP, msg); return -1; }
+                if (n > 0) { last_ = last; got_any_ = true; *on_dev = true; return n; }
+                if (dgz_->hand_over() >= 0) {                  // the rest of the file is the sequential reader's (GzBgzf's rule)
+                    if (::lseek(fd_, dgz_->hand_over(), SEEK_SET) < 0) { err.set(HULK_ERR_IO, std::string("lseek: ") + strerror(errno)); return -1; }
+                    gzf_.reset(new GzFast(fd_, !dgz_->any_member()));
+                    continue;
+                }
             } else if (is_gz_) {
                 n = gzread(gz_, dst, (unsigned)std::min<size_t>(cap, 1u << 30));
                 if (n < 0) { int e = 0; const char *m = gzerror(gz_, &e); err.set(HULK_ERR_IO, std::string("gzip: ") + (m ? m : "read error")); return -1; }
@@ -1143,6 +1135,7 @@ class ByteSource {
             if (m < 2 || magic[0] != 0x1f || magic[1] != 0x8b) { close_current(); return err.set(HULK_ERR_IO, "gzip: invalid header"); }
             const bool use_zlib = cfg_.zlib;
             if (!use_zlib) {
+                if (regular_ && dev_bufs_ && hulk::bgzf::DevReader::looks_like(fd_)) { dgz_.reset(new hulk::bgzf::DevReader(fd_, dev_bufs_, cfg_.trace)); return true; }
                 if (regular_ && cfg_.gz_threads > 1 && GzBgzf::looks_like(fd_)) gzf_.reset(new GzBgzf(fd_, cfg_));
                 else if (regular_ && GzPar::wanted(fd_, cfg_)) gzf_.reset(new GzPar(fd_, cfg_));
                 else gzf_.reset(new GzFast(fd_));
@@ -1155,6 +1148,7 @@ class ByteSource {
         return true;
     }
     void close_current() {
+        dgz_.reset();                                             // (the device reader does not own the descriptor)
         if (gzf_) { gzf_.reset(); fd_ = -1; }                     // (the gzip readers close the descriptor)
         else if (gz_) { gzclose(gz_); gz_ = nullptr; fd_ = -1; }  // gzclose closes the descriptor
         else if (fd_ > 0) ::close(fd_);
@@ -1168,6 +1162,8 @@ class ByteSource {
     off_t pos_ = 0;
     gzFile gz_ = nullptr;
     std::unique_ptr<GzStream> gzf_;
+    hulk::bgzf::DevBufs *dev_bufs_ = nullptr;
+    std::unique_ptr<hulk::bgzf::DevReader> dgz_;
     uint8_t last_ = '\n';
     std::unique_ptr<Team> team_;                                  // read_pieces' readers
 };
@@ -1706,10 +1702,14 @@ struct FqDev {
         hipEvent_t ev_busy[2][2] = {};
         bool busy0[2] = {}, busy1[2] = {};
     } fa;
+    // HULK_INGEST_DEVICE_INFLATE (allocated by the first such run of the set): two batches of members and a device twin of each
+    // pinned block — about 2 x 144 MB + 6 x 16 MiB of HBM and 2 x 16 MiB pinned at the default block size
+    hulk::bgzf::DevBufs *gz = nullptr;
     size_t raw_bytes() const { return (size_t)porch + block + 64; }
     void release() {
         if (cs) hipStreamSynchronize(cs);
         if (ps) hipStreamSynchronize(ps);
+        hulk::bgzf::dev_bufs_free(gz); gz = nullptr;
         for (auto &b : fa.B) { hipFree(b.wgcnt); hipFree(b.line_end); hipFree(b.linfo); hipFree(b.ldst); hipFree(b.wghdr); hipFree(b.hrel); hipFree(b.wgbytes); }
         for (auto &e : fa.ev_placed) if (e) hipEventDestroy(e);
         hipFree(fa.d_state); if (fa.h_state) hipHostFree(fa.h_state);
@@ -1825,9 +1825,11 @@ static FqDev *fq_dev_for(hulk_ctx *ctx, size_t block, IngestError &err) {
 // reader thread of the device path: raw blocks of exactly `block` bytes (the last one shorter) into the pinned buffers
 class RawReader {
  public:
-    struct Item { int idx = -1; size_t len = 0; bool eof = false; };
+    // dev: [offset, length) pieces of the block that are device text, in the twin of pinned buffer idx (the rest is in the buffer)
+    struct Item { int idx = -1; size_t len = 0; bool eof = false; std::vector<std::pair<size_t, size_t>> dev; };
     RawReader(const char *const *paths, uint32_t n, const IngestCfg &cfg, FqDev *dev) : dev_(dev), src_(paths, n, cfg) {
         for (int i = 0; i < FqDev::NHOST; i++) free_.push_back(i);
+        if (cfg.dev_inflate) src_.set_device_inflate(dev->gz);
         th_ = std::thread([this] { run(); });
     }
     ~RawReader() {
@@ -1856,13 +1858,23 @@ class RawReader {
                 idx = free_.front(); free_.pop_front();
             }
             size_t have = 0; bool eof = false; IngestError e;
+            Item it;
+            uint8_t *twin = dev_->gz ? hulk::bgzf::dev_bufs_block(dev_->gz, idx) : nullptr;
             while (have < dev_->block) {
-                const long n = src_.read(dev_->h_buf[idx] + have, dev_->block - have, e);
+                bool on_dev = false;
+                const long n = src_.read(dev_->h_buf[idx] + have, dev_->block - have, e, twin ? twin + have : nullptr, &on_dev);
                 if (n < 0) { std::lock_guard<std::mutex> g(m_); err_ = e; done_ = true; cv_.notify_all(); return; }
                 if (n == 0) { eof = true; break; }
+                if (on_dev) {
+                    if (!it.dev.empty() && it.dev.back().first + it.dev.back().second == have) it.dev.back().second += (size_t)n;
+                    else it.dev.emplace_back(have, (size_t)n);
+                }
                 have += (size_t)n; bytes_in_ += (uint64_t)n;
             }
-            { std::lock_guard<std::mutex> g(m_); Item it; it.idx = idx; it.len = have; it.eof = eof; q_.push_back(it); }
+            if (!it.dev.empty() && hulk::bgzf::dev_bufs_mark_block(dev_->gz, idx) != hipSuccess) {
+                std::lock_guard<std::mutex> g(m_); err_.set(HULK_ERR_HIP, "hipEventRecord (device BGZF text)"); done_ = true; cv_.notify_all(); return;
+            }
+            { std::lock_guard<std::mutex> g(m_); it.idx = idx; it.len = have; it.eof = eof; q_.push_back(std::move(it)); }
             cv_.notify_all();
             if (eof) break;
         }
@@ -1880,6 +1892,39 @@ class RawReader {
     IngestError err_;
     std::atomic<uint64_t> bytes_in_{0};
 };
+
+// HULK_INGEST_DEVICE_INFLATE: the set's device BGZF reader buffers (hulk_bgzf.hip), allocated by the first such run
+static bool gz_ensure(FqDev *D, IngestError &err) {
+    if (D->gz) return true;
+    std::string msg;
+    D->gz = hulk::bgzf::dev_bufs_new(D->device, FqDev::NHOST, D->block, msg);
+    return D->gz ? true : err.set(HULK_ERR_HIP, msg);
+}
+// a block's bytes -> its raw slot on the copy stream: pinned bytes host-to-device, device text device-to-device from the
+// block's twin (behind the reader thread's copies into it)
+static hipError_t copy_block(FqDev *D, const RawReader::Item &it, uint8_t *dst) {
+    if (it.dev.empty()) return hipMemcpyAsync(dst, D->h_buf[it.idx], it.len, hipMemcpyHostToDevice, D->cs);
+    const uint8_t *twin = hulk::bgzf::dev_bufs_block(D->gz, it.idx);
+    hipError_t e = hipStreamWaitEvent(D->cs, hulk::bgzf::dev_bufs_block_event(D->gz, it.idx), 0);
+    size_t at = 0;
+    for (const auto &pc : it.dev) {
+        if (e == hipSuccess && pc.first > at) e = hipMemcpyAsync(dst + at, D->h_buf[it.idx] + at, pc.first - at, hipMemcpyHostToDevice, D->cs);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst + pc.first, twin + pc.first, pc.second, hipMemcpyDeviceToDevice, D->cs);
+        at = pc.first + pc.second;
+    }
+    if (e == hipSuccess && it.len > at) e = hipMemcpyAsync(dst + at, D->h_buf[it.idx] + at, it.len - at, hipMemcpyHostToDevice, D->cs);
+    return e;
+}
+// the host parser takes over: a block's device text back into its pinned buffer
+static bool host_bytes(FqDev *D, const RawReader::Item &it, IngestError &err) {
+    if (it.dev.empty()) return true;
+    const uint8_t *twin = hulk::bgzf::dev_bufs_block(D->gz, it.idx);
+    if (hipEventSynchronize(hulk::bgzf::dev_bufs_block_event(D->gz, it.idx)) != hipSuccess) return err.set(HULK_ERR_HIP, "hipEventSynchronize (device BGZF text)");
+    for (const auto &pc : it.dev)
+        if (hipMemcpy(D->h_buf[it.idx] + pc.first, twin + pc.first, pc.second, hipMemcpyDeviceToHost) != hipSuccess)
+            return err.set(HULK_ERR_HIP, "hipMemcpy (device BGZF text to the host parser)");
+    return true;
+}
 
 // hulk_sketch_files over the device parser.  `host_took_over` tells the statistics that the host parser finished the stream.
 int run_ingest_device(hulk_ctx *ctx, const char *const *paths, uint32_t n_paths, const IngestCfg &cfg_in, PhaseTrace &g_trace,
@@ -1900,6 +1945,7 @@ int run_ingest_device(hulk_ctx *ctx, const char *const *paths, uint32_t n_paths,
     (void)lease;                                                 // (declared before the reader: released after its thread has ended)
 #define DEV_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err.set(HULK_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); return err.code; } } while (0)
     DEV_HIP(hipSetDevice(D->device));
+    if (cfg.dev_inflate && !gz_ensure(D, err)) return err.code;
     // (busy0 / busy1 of the output sets survive between runs: the binning kernels of the run before — this context's or
     //  another's — may still be reading a set when this run's first parse is queued; its events say when they are done)
     GpuSink sink(ctx, g_trace);                                  // the host parser's way into the context, should it take over
@@ -1971,7 +2017,7 @@ int run_ingest_device(hulk_ctx *ctx, const char *const *paths, uint32_t n_paths,
             const double tb1 = PhaseTrace::now(); g_trace.wait_block += tb1 - tb0;
             if (!got) { ok = err.code == HULK_OK; break; }
             if (on_host) {
-                ok = host_feed(D->h_buf[it.idx], it.len, it.eof);
+                ok = host_bytes(D, it, err) && host_feed(D->h_buf[it.idx], it.len, it.eof);
                 g_trace.parse += PhaseTrace::now() - tb1;
                 reader.recycle(it.idx);
                 if (!ok || it.eof) break;
@@ -1981,7 +2027,7 @@ int run_ingest_device(hulk_ctx *ctx, const char *const *paths, uint32_t n_paths,
             const int r = (int)(b % FqDev::NRAW), o = (int)(b % FqDev::NOUT), st = (int)(b % FqDev::NST);
             // raw slot r held block b - NRAW and served block b - NRAW + 1 as the source of its tail
             if (b >= (uint64_t)FqDev::NRAW) DEV_HIP(hipStreamWaitEvent(D->cs, D->ev_parsed[(b - FqDev::NRAW + 1) % FqDev::NST], 0));
-            DEV_HIP(hipMemcpyAsync(D->d_raw[r] + D->porch, D->h_buf[it.idx], it.len, hipMemcpyHostToDevice, D->cs));
+            DEV_HIP(copy_block(D, it, D->d_raw[r] + D->porch));
             DEV_HIP(hipEventRecord(D->ev_copied[it.idx], D->cs));
             DEV_HIP(hipStreamWaitEvent(D->ps, D->ev_copied[it.idx], 0));
             if (D->busy0[o]) { DEV_HIP(hipStreamWaitEvent(D->ps, D->ev_busy[o][0], 0)); D->busy0[o] = false; }
@@ -2010,13 +2056,13 @@ int run_ingest_device(hulk_ctx *ctx, const char *const *paths, uint32_t n_paths,
             bool eof = false;
             while (ok && !held.empty()) {
                 const RawReader::Item it = held.front(); held.pop_front();
-                ok = host_feed(D->h_buf[it.idx], it.len, it.eof); eof = it.eof;
+                ok = host_bytes(D, it, err) && host_feed(D->h_buf[it.idx], it.len, it.eof); eof = it.eof;
                 reader.recycle(it.idx);
             }
             while (ok && !eof) {
                 RawReader::Item it;
                 if (!reader.next(it, err)) { ok = err.code == HULK_OK; break; }
-                ok = host_feed(D->h_buf[it.idx], it.len, it.eof); eof = it.eof;
+                ok = host_bytes(D, it, err) && host_feed(D->h_buf[it.idx], it.len, it.eof); eof = it.eof;
                 reader.recycle(it.idx);
             }
         }
@@ -2098,6 +2144,7 @@ int run_ingest_fasta_device(hulk_ctx *ctx, const char *const *paths, uint32_t n_
 #define DEV_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err.set(HULK_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); return err.code; } } while (0)
     DEV_HIP(hipSetDevice(D->device));
     if (!fa_ensure(D, err)) return err.code;
+    if (cfg.dev_inflate && !gz_ensure(D, err)) return err.code;
     FqDev::Fasta &F = D->fa;
     const uint64_t min_len = hulk::ctx_min_read_len(ctx);
     int cur = 0;
@@ -2227,7 +2274,7 @@ int run_ingest_fasta_device(hulk_ctx *ctx, const char *const *paths, uint32_t n_
             const int r = (int)(b % FqDev::NRAW), st = (int)(b % FqDev::NST);
             // the copy, and the block's index: neither needs to know where the blocks before left the accumulation buffer
             if (b >= (uint64_t)FqDev::NRAW) DEV_HIP(hipStreamWaitEvent(D->cs, F.ev_placed[r], 0));     // (the block that used this raw slot)
-            DEV_HIP(hipMemcpyAsync(D->d_raw[r] + D->porch, D->h_buf[it.idx], it.len, hipMemcpyHostToDevice, D->cs));
+            DEV_HIP(copy_block(D, it, D->d_raw[r] + D->porch));
             DEV_HIP(hipEventRecord(D->ev_copied[it.idx], D->cs));
             DEV_HIP(hipStreamWaitEvent(D->ps, D->ev_copied[it.idx], 0));
             DEV_HIP(hulk::launch_fa_index(D->ps, F.B[b & 1], b ? D->d_raw[(b - 1) % FqDev::NRAW] : nullptr, b ? F.d_state + (b - 1) % FqDev::NST : nullptr,

@@ -55,6 +55,26 @@ def parse_files(paths, fasta=False, threads=0, collect=True, opts=None):
     return bases, offsets, stats_dict(st)
 
 
+def bgzf_inflate(data):
+    """Whole BGZF members (bytes) -> their text, inflated on the current GPU by the device reader's kernel (hulk_bgzf_inflate).
+    A member that is not whole or fails to inflate raises HulkError(HULK_ERR_IO, "bgzf: member <i> (byte <offset>): <reason>")
+    with `.member` = <i>."""
+    L = _lib.load()
+    data = bytes(data)
+    u64 = ctypes.c_uint64
+    out_len, n, bad = u64(0), u64(0), u64(0)
+    err = ctypes.create_string_buffer(512)
+    rc = L.hulk_bgzf_inflate(data, len(data), None, 0, ctypes.byref(out_len), ctypes.byref(n), ctypes.byref(bad), err, 512)
+    if rc == 0:
+        out = ctypes.create_string_buffer(max(out_len.value, 1))
+        rc = L.hulk_bgzf_inflate(data, len(data), out, out_len.value, ctypes.byref(out_len), ctypes.byref(n), ctypes.byref(bad), err, 512)
+    if rc != 0:
+        e = HulkError(rc, err.value.decode("latin-1") or L.hulk_strerror(rc).decode())
+        e.member = None if bad.value == 2 ** 64 - 1 else int(bad.value)
+        raise e
+    return out.raw[:out_len.value]
+
+
 def stats_dict(st):
     return {"n_seqs": int(st.n_seqs), "total_len": int(st.total_len), "n_lines": int(st.n_lines),
             "bytes_in": int(st.bytes_in), "seconds": float(st.seconds)}

@@ -219,6 +219,14 @@ int hulk_parse_files(const char *const *paths, uint32_t n_paths, int fasta, uint
                                        * empty lines — hands the stream to the host parser, whose reads and messages are the same.
                                        * --fasta: the device decides everything (the empty line that ends the parsing, the line of 64 KiB
                                        * that is bufio.Scanner's error); sequences of any length accumulate in device memory across blocks */
+#define HULK_INGEST_DEVICE_INFLATE 16u /* hulk_sketch_files* on the device parsers: a regular file whose first member is BGZF (bgzip,
+                                       * htslib) has its members inflated on the GPU and the text goes device-to-device to the parser;
+                                       * the host only read()s the compressed bytes.  At the first member that is not a clean, verified
+                                       * BGZF member the text in front of it is delivered and the file is handed to the one-thread
+                                       * host reader at that member, so reads, counters and messages are those of the host path.  STDIN,
+                                       * pipes, one-member .gz and plain files are read as without the flag; HULK_INGEST_GZ_ZLIB takes
+                                       * precedence.  Accepted and ignored with HULK_INGEST_HOST_PARSER and by hulk_parse_files*.  The
+                                       * environment variable HULK_GZ_DEVICE=1 (0) switches it on (off) for any run. */
 typedef struct hulk_ingest_opts {
     uint32_t parser_threads;  /* 0 = one per hardware thread, at most 16 (the measured optimum); any other figure is taken as it is (<= 256) */
     uint32_t gz_threads;      /* threads inflating the members of a bgzip'd input, or the chunks of ONE gzip member, side by side: 1..64, 0 = 16 */
@@ -237,6 +245,15 @@ int hulk_sketch_files(hulk_ctx *ctx, const char *const *paths, uint32_t n_paths,
                       hulk_ingest_stats *stats);
 int hulk_sketch_files_opts(hulk_ctx *ctx, const char *const *paths, uint32_t n_paths, int fasta, const hulk_ingest_opts *opts,
                            hulk_ingest_stats *stats);
+/* The device BGZF inflater on its own: `in` holds whole BGZF members (in_len bytes, nothing else), inflated on the current
+ * device into `out`.  *out_len = the text's size (the ISIZE fields summed), *n_members = members framed, *bad_member = index of
+ * the first member that failed (UINT64_MAX if none).  out == NULL: a size query (framing only).  Errors: HULK_ERR_IO with
+ * "bgzf: member <i> (byte <offset>): <reason>" in errbuf — a piece that is not a whole BGZF member, or a member that fails to
+ * inflate (invalid block type, invalid or over-subscribed Huffman code, invalid symbol, distance before the member's start,
+ * output longer or shorter than ISIZE, payload exhausted, deflate end not at the payload end, CRC-32 mismatch); HULK_ERR_ARG
+ * (out_cap below *out_len), HULK_ERR_HIP.  `out` then holds the text of the members in front of the bad one. */
+int hulk_bgzf_inflate(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *n_members,
+                      uint64_t *bad_member, char *errbuf, uint64_t errbuf_len);
 
 /* Intervals are flushed in batches: up to hulk_batch_size() consecutive sketching intervals are
  * binned into separate k-mer spectra by one kernel launch and then pushed through count-min + CWS
