@@ -1041,6 +1041,7 @@ __global__ __launch_bounds__(256) void k_long_emit(const LongSeqDesc *__restrict
 // and the window minima, run starts, the per-sequence set (HBM, 64-bit CAS: unchanged) and the queue of new values follow from
 // LDS.  Same values, same set, same counts as the two-pass form (HULK_LONG_TWO_PASS in the profiling build keeps it as comparator).
 constexpr int LONG_TILE = 2048;                 // tile indices per workgroup = 256 threads x 8 positions
+constexpr uint32_t LONG_TILE_LAG = 1u << 8;     // P.debug bit (profiling build, launch_long_group's copy of P only): see HULK_LONG_TILE_LAG
 __global__ __launch_bounds__(256) void k_long_tile(const uint8_t *__restrict__ bases, const LongSeqDesc *__restrict__ desc,
                                                    MinimizerParams P, uint64_t *__restrict__ table_all,
                                                    uint32_t *__restrict__ hists, unsigned long long *__restrict__ min_slots) {
@@ -1068,8 +1069,8 @@ __global__ __launch_bounds__(256) void k_long_tile(const uint8_t *__restrict__ b
     unsigned fresh = 0;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t o = tile * TP - H;                         // sequence position of tile index 0 (negative in the first tile)
-        if (tid == 0) qn = 0;
-        __syncthreads();                                         // (also: the previous tile's readers of code / Xs / q are done, lut is built)
+        __syncthreads();                                         // (A: the previous tile's readers of code / Xs / qn / q are done, lut is built)
+        if (tid == 0) qn = 0;                                    // (behind A: every wave has read the last tile's qn; the emitters add after C)
         for (int b = tid; b < LONG_TILE + (int)k; b += 256) {
             const int64_t pos = o - 1 + b;
             code[b] = (pos >= 0 && pos < L) ? lut[seq[pos]] : (uint8_t)0;
@@ -1137,6 +1138,12 @@ __global__ __launch_bounds__(256) void k_long_tile(const uint8_t *__restrict__ b
         }
         __syncthreads();
         {
+#ifdef HULK_EXPERIMENTS
+            if ((P.debug & LONG_TILE_LAG) && tid >= 64) {            // (profiling build, HULK_LONG_TILE_LAG: waves 1-3 read qn ~40 us late)
+                for (int i = 0; i < 10; i++) __builtin_amdgcn_s_sleep(127);
+                __atomic_signal_fence(__ATOMIC_SEQ_CST);             // (the read of qn stays behind the wait)
+            }
+#endif
             const unsigned nq = qn < QCAP ? qn : QCAP;
             for (unsigned i = tid; i < nq; i += 256) atomicAdd(&hist[jump_hash(q[i], P.num_bins)], 1u);
         }
@@ -1278,6 +1285,10 @@ hipError_t launch_long_group(hipStream_t s, const uint8_t *d_bases, const LongSe
     const uint64_t cap = std::max<uint64_t>(1, 262144 / n_seqs);
     if (bx > cap) bx = cap;
     if (bx > 65535) bx = 65535;
+    // (profiling build) HULK_LONG_TILE_GRID=n: at most n workgroups per sequence, so that short inputs stride over many tiles too;
+    // HULK_LONG_TILE_LAG: waves 1-3 wait before they read the queue length of a tile's flush (the order of qn's reset behind them)
+    if (const char *e = HULK_EXP_ENV("HULK_LONG_TILE_GRID")) { const long n = atol(e); if (n > 0 && bx > (uint64_t)n) bx = (uint64_t)n; }
+    if (HULK_EXP_ENV("HULK_LONG_TILE_LAG")) P.debug |= LONG_TILE_LAG;
     prof_mark(s, "k_long_tile");
     hipLaunchKernelGGL(k_long_tile, dim3((unsigned)bx, n_seqs), dim3(256), 0, s, d_bases, d_desc, P, d_table, d_hists, d_min_slots);
     return hipGetLastError();
