@@ -26,6 +26,9 @@ HULK_XCHG_ALLGATHER, HULK_XCHG_ALLREDUCE_U32 = 0, 1
 HULK_CWS_GO_COMPAT = 0
 HULK_CWS_EXTERNAL = 1
 HULK_FLAG_GAMMA_CPYTHON, HULK_FLAG_NO_PRUNE, HULK_FLAG_NO_SKIP, HULK_FLAG_SHARD_FULL, HULK_FLAG_NO_OVERLAP, HULK_FLAG_NO_PRERESERVE, HULK_FLAG_CMS_CHAIN = 1, 2, 4, 8, 16, 32, 64
+HULK_FLAG_KMV, HULK_FLAG_KHF = 128, 256     # feed the bottom-k / k-hash-functions MinHash sketches (hulk_get_minhash)
+HULK_MINHASH_KMV, HULK_MINHASH_KHF = 0, 1
+HULK_MINHASH_MAX_SKETCH = 4096
 HULK_MAX_BINS = 1 << 20
 HULK_INJECT_NONE, HULK_INJECT_STALE_SEAL, HULK_INJECT_STALE_STAGE = 0, 1, 2
 HULK_DEBUG_TILEMIN, HULK_DEBUG_SCANMAP = 1, 2
@@ -41,7 +44,7 @@ ABI_SYMBOLS = (
     "hulk_comm_unique_id", "hulk_comm_init", "hulk_comm_init_host", "hulk_comm_init_loopback", "hulk_step_sharded", "hulk_step_sharded_host",
     "hulk_step_sliced", "hulk_gather_sketch", "hulk_get_comm_stats", "hulk_get_comm_health", "hulk_release_caches", "hulk_get_device_checks", "hulk_get_profile_table",
     "hulk_load_sketches", "hulk_sketch_set_free", "hulk_sketch_set_info", "hulk_sketch_set_mins", "hulk_sketch_set_weights", "hulk_sketch_set_path",
-    "hulk_sketch_set_banner", "hulk_smash_files", "hulk_bgzf_inflate",
+    "hulk_sketch_set_banner", "hulk_smash_files", "hulk_bgzf_inflate", "hulk_get_minhash", "hulk_minhash_merge",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -262,6 +265,8 @@ def load():
     L.hulk_get_device_checks.restype = ctypes.c_int; L.hulk_get_device_checks.argtypes = [vp, vp, vp]
     L.hulk_get_profile_table.restype = ctypes.c_int; L.hulk_get_profile_table.argtypes = [vp, ctypes.c_char_p, u64]
     L.hulk_release_caches.restype = ctypes.c_int; L.hulk_release_caches.argtypes = []
+    L.hulk_get_minhash.restype = ctypes.c_int; L.hulk_get_minhash.argtypes = [vp, ctypes.c_int, vp, vp, vp]
+    L.hulk_minhash_merge.restype = ctypes.c_int; L.hulk_minhash_merge.argtypes = [vp, ctypes.c_int, vp, u32]
     _lib = L
     return L
 

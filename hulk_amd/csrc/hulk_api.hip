@@ -96,8 +96,11 @@ int hulk_create(const hulk_params *params, hulk_ctx **out) {
     // the binning kernels pack (spectrum slot << 20 | bin) into a dword (hulk_spectrum.hip); k^4 <= 31^4 < 2^20
     if (bins > (int64_t)HULK_MAX_BINS)
         return fail(nullptr, HULK_ERR_ARG, "num_bins " + std::to_string(bins) + " exceeds HULK_MAX_BINS (2^20; k^4 at k = 31 is 923521)");
-    if (p.flags & ~(HULK_FLAG_GAMMA_CPYTHON | HULK_FLAG_NO_PRUNE | HULK_FLAG_NO_SKIP | HULK_FLAG_SHARD_FULL | HULK_FLAG_NO_OVERLAP | HULK_FLAG_NO_PRERESERVE | HULK_FLAG_CMS_CHAIN))
+    if (p.flags & ~(HULK_FLAG_GAMMA_CPYTHON | HULK_FLAG_NO_PRUNE | HULK_FLAG_NO_SKIP | HULK_FLAG_SHARD_FULL | HULK_FLAG_NO_OVERLAP | HULK_FLAG_NO_PRERESERVE | HULK_FLAG_CMS_CHAIN | HULK_FLAG_KMV | HULK_FLAG_KHF))
         return fail(nullptr, HULK_ERR_ARG, "unknown flags");
+    if ((p.flags & (HULK_FLAG_KMV | HULK_FLAG_KHF)) && (p.sketch_size < 1 || p.sketch_size > HULK_MINHASH_MAX_SKETCH))
+        return fail(nullptr, HULK_ERR_ARG, "HULK_FLAG_KMV / HULK_FLAG_KHF need 1 <= sketch_size <= " + std::to_string(HULK_MINHASH_MAX_SKETCH) +
+                                               " (got " + std::to_string(p.sketch_size) + ")");
     if (p.batch > (uint32_t)SCAN_BATCH_MAX) return fail(nullptr, HULK_ERR_ARG, "batch must be 0 (default) or 1..16");
     if (p.work_lanes > 2) return fail(nullptr, HULK_ERR_ARG, "work_lanes must be 0 (default), 1 or 2");
     if (p.reserved != 0) return fail(nullptr, HULK_ERR_ARG, "reserved must be 0");
@@ -208,6 +211,23 @@ int hulk_create(const hulk_params *params, hulk_ctx **out) {
         CHK_CREATE(dalloc(&c->d_sege0, T * 64));
         CHK_CREATE(hipMemsetAsync(c->d_ctrd, 0, NC * 8, c->stream));
     }
+    if (p.flags & (HULK_FLAG_KMV | HULK_FLAG_KHF)) {
+        MinHashState &M = c->mh;
+        M.S = p.sketch_size;
+        CHK_CREATE(dalloc(&M.kmv, S)); CHK_CREATE(dalloc(&M.khf, S)); CHK_CREATE(dalloc(&M.xmin, 1));
+        CHK_CREATE(dalloc(&M.fed, (size_t)MH_FED_SLOTS)); CHK_CREATE(dalloc(&c->d_mh_in, S));
+        CHK_CREATE(hipMemsetAsync(M.kmv, 0xff, S * 8, c->stream));
+        CHK_CREATE(hipMemsetAsync(M.khf, 0xff, S * 8, c->stream));
+        CHK_CREATE(hipMemsetAsync(M.xmin, 0xff, 8, c->stream));
+        CHK_CREATE(hipMemsetAsync(M.fed, 0, (size_t)MH_FED_SLOTS * 8, c->stream));
+        if (p.flags & HULK_FLAG_KMV) M.mode |= MH_KMV;
+        if (p.flags & HULK_FLAG_KHF) {
+            // a fed value is below 2^(2k+8) and the largest multiplier is S: when the product cannot reach 2^64 the signature is
+            // (i+1) * min(x) and the feed is one min-reduction; otherwise every value updates every slot
+            uint32_t lg = 0; while ((1ull << lg) < (uint64_t)S) lg++;
+            M.mode |= (2 * p.k + 8 + lg <= 64) ? MH_KHF_MIN : MH_KHF_BRUTE;
+        }
+    }
     CHK_CREATE(dalloc(&c->d_candA, T * SL));
     CHK_CREATE(dalloc(&c->d_candB, T * SL));
     CHK_CREATE(hipMemsetAsync(c->d_state, 0, sizeof(DevState), c->stream));
@@ -253,6 +273,7 @@ void hulk_destroy(hulk_ctx *c) {
         hipFree(hs.d_bases); hipFree(hs.d_off);
     }
     hipFree(c->d_min_slots);
+    hipFree(c->mh.kmv); hipFree(c->mh.khf); hipFree(c->mh.xmin); hipFree(c->mh.fed); hipFree(c->d_mh_in);
     for (auto &ln : c->lane) {
         if (ln.stream) { hipStreamSynchronize(ln.stream); hipStreamDestroy(ln.stream); }
         hipFree(ln.d_slow_list); hipFree(ln.d_slow_count);
@@ -474,6 +495,61 @@ int hulk_get_counters(hulk_ctx *c, uint64_t *n_reads, uint64_t *n_minimizers, ui
     if (n_reads) *n_reads = c->seq_count;
     if (n_minimizers) *n_minimizers = nm;
     if (total_len) *total_len = st.total_len;
+    return HULK_OK;
+}
+
+static int minhash_ready(hulk_ctx *c, int algo) {
+    if (c->sticky != HULK_OK) return fail(c, c->sticky);
+    if (algo != HULK_MINHASH_KMV && algo != HULK_MINHASH_KHF) return fail(c, HULK_ERR_ARG, "algo must be HULK_MINHASH_KMV or HULK_MINHASH_KHF");
+    const uint32_t need = algo == HULK_MINHASH_KMV ? MH_KMV : (MH_KHF_MIN | MH_KHF_BRUTE);
+    if (!(c->mh.mode & need))
+        return fail(c, HULK_ERR_STATE, algo == HULK_MINHASH_KMV ? "the context was created without HULK_FLAG_KMV" : "the context was created without HULK_FLAG_KHF");
+    return sync_all(c);
+}
+
+int hulk_get_minhash(hulk_ctx *c, int algo, uint64_t *mins, uint32_t *n, uint64_t *n_fed) {
+    if (!c || !mins || !n) return fail(c, HULK_ERR_ARG, "NULL");
+    { const int rc = minhash_ready(c, algo); if (rc != HULK_OK) return rc; }
+    const MinHashState &M = c->mh;
+    std::vector<unsigned long long> v(M.S), fed(MH_FED_SLOTS);
+    unsigned long long xmin = ~0ull;
+    HIPCHK(c, hipMemcpyAsync(v.data(), algo == HULK_MINHASH_KMV ? M.kmv : M.khf, (size_t)M.S * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(fed.data(), M.fed, (size_t)MH_FED_SLOTS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&xmin, M.xmin, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    unsigned long long nf = 0;
+    for (auto x : fed) nf += x;
+    if (n_fed) *n_fed = nf;
+    if (algo == HULK_MINHASH_KMV) {
+        // the entries are the S smallest fed values; the order the reference's GetSketch gives them (kmv.go:161-169) is ascending
+        std::sort(v.begin(), v.end());
+        const unsigned long long held = std::min<unsigned long long>(M.S, nf + c->mh_merged);
+        for (uint32_t i = 0; i < (uint32_t)held; i++) mins[i] = v[i];
+        *n = (uint32_t)held;
+    } else {
+        // MH_KHF_MIN: slot i of the fed stream is (i+1) * min(x), no wrap (hulk_create); khf[] holds what was merged in
+        for (uint32_t i = 0; i < M.S; i++) {
+            unsigned long long r = v[i];
+            if ((M.mode & MH_KHF_MIN) && xmin != ~0ull) r = std::min(r, xmin * (unsigned long long)(i + 1));
+            mins[i] = r;
+        }
+        *n = M.S;
+    }
+    return HULK_OK;
+}
+
+int hulk_minhash_merge(hulk_ctx *c, int algo, const uint64_t *mins, uint32_t n) {
+    if (!c || (n && !mins)) return fail(c, HULK_ERR_ARG, "NULL");
+    { const int rc = minhash_ready(c, algo); if (rc != HULK_OK) return rc; }
+    if (algo == HULK_MINHASH_KHF && n != c->mh.S)
+        return fail(c, HULK_ERR_ARG, "KHF merge needs a signature of sketch_size entries (" + std::to_string(c->mh.S) + "), got " + std::to_string(n));
+    for (uint32_t at = 0; at < n; at += c->mh.S) {                 // (a KMV signature may be longer than this context's)
+        const uint32_t m = std::min<uint32_t>(c->mh.S, n - at);
+        HIPCHK(c, hipMemcpyAsync(c->d_mh_in, mins + at, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_minhash_merge(c->stream, c->d_mh_in, m, algo == HULK_MINHASH_KHF, c->mh));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (algo == HULK_MINHASH_KMV) c->mh_merged += n;
     return HULK_OK;
 }
 

@@ -98,6 +98,9 @@ struct hulk_ctx {
     float *d_kmin32 = nullptr, *d_rext = nullptr, *d_kminslot = nullptr;          // bound test of k_cws_scan (no concept drift only)
     unsigned long long *d_visited = nullptr; uint64_t scan_tiles_total = 0; bool prune = false, no_skip = false;
     double *d_candA = nullptr; int32_t *d_candB = nullptr;
+    // HULK_FLAG_KMV / HULK_FLAG_KHF: the MinHash sketches (hulk_minhash.h); mode == 0 and no allocation without the flags.
+    // Both work lanes feed the one state with atomics; mh_merged counts the values hulk_minhash_merge folded into the KMV
+    hulk::MinHashState mh{}; uint64_t mh_merged = 0; uint64_t *d_mh_in = nullptr;
     // staging for host reads
     // hulk_add_reads (host buffers): two sets of pinned + device staging; the copy of chunk i+1 into pinned memory
     // and over PCIe runs while the kernels of chunk i do

@@ -160,6 +160,9 @@ int bin_long_reads(hulk_ctx *c, hipStream_t s, const uint8_t *d_bases, const uin
         HIPCHK(c, launch_long_group(s, d_bases, (const hulk::LongSeqDesc *)c->d_long_desc, (uint32_t)descs.size(),
                                     max_npos, P, c->d_long_xs, c->d_long_valid, c->d_long_table, tab_total, hist,
                                     c->d_min_slots));
+        // a sequence's distinct minimizers are the occupied entries of its set table: the MinHash sketches read them there,
+        // before ev_long hands the tables to the other lane's next group
+        if (c->mh.mode) HIPCHK(c, launch_minhash_table(s, c->d_long_table, tab_total, c->mh));
         if (!c->ev_long) HIPCHK(c, hipEventCreateWithFlags(&c->ev_long, hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ev_long, s));
         c->long_last_stream = s; c->long_pending = true;
@@ -291,7 +294,10 @@ static int bin_fast(hulk_ctx *c, hulk_ctx::BinLane &ln, hipStream_t s, const uin
     static const uint32_t slow_blocks = [] { const char *e = HULK_EXP_ENV("HULK_SLOW_BLOCKS"); const long v = e ? atol(e) : 2048; return (uint32_t)(v < 1 ? 1 : v > 8192 ? 8192 : v); }();
     const uint32_t list_blocks = (uint32_t)std::min<uint64_t>(slow_blocks, (n + 3) / 4);
     HIPCHK(c, launch_minimizer_bin(s, d_bases, d_offsets, n, P, threads, hist, c->d_state, c->d_min_slots, ln.d_slow_list,
-                                   ln.d_slow_count, list_blocks));
+                                   ln.d_slow_count, list_blocks, &c->mh));
+    // the MinHash sketches read the lane's minimizer list at the end of its chain: the spectrum kernels do not wait for them,
+    // and the list stays as it is until the lane's next k_minimizer_fast, which this stream orders behind
+    if (c->mh.mode) HIPCHK(c, launch_minhash_list(s, ln.ml, n, c->mh));
     prof_mark(s, "-");
     return HULK_OK;
 }
@@ -390,7 +396,7 @@ int bin_reads(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, ui
             const bool fits = pick_config(c->p.k, max_len, P, threads);
             P.skip_long = fits ? 0u : 1u;
             HIPCHK(c, launch_minimizer_bin(s, d_bases, d_offsets, n, P, threads, hist, c->d_state,
-                                           c->d_min_slots, nullptr, nullptr, 0));
+                                           c->d_min_slots, nullptr, nullptr, 0, &c->mh));
             if (!fits) rc = bin_long_reads(c, s, d_bases, d_offsets, n, P, hist, c->h_off_chunk);
         }
     }

@@ -90,6 +90,23 @@ struct MinimizerParams {
     uint32_t ring_base, ring_n;   // spectra live in a ring of ring_n histograms
 };
 
+// The MinHash sketches of a context created with HULK_FLAG_KMV / HULK_FLAG_KHF (hulk_minhash.h has the semantics): device
+// pointers, handed to the kernels by value.  mode == 0: the context keeps none.
+constexpr uint32_t MH_KMV = 1, MH_KHF_MIN = 2, MH_KHF_BRUTE = 4;
+constexpr uint32_t MH_FED_SLOTS = 256;
+constexpr uint32_t MH_MAX_SKETCH = 4096;     // largest sketch_size of a context with either flag (64 slots per lane in registers)
+struct MinHashState {
+    unsigned long long *kmv;     // [S] MaxUint64 = empty; the S smallest fed values at rest (not necessarily in order)
+    unsigned long long *khf;     // [S] MaxUint64 = nothing fed
+    unsigned long long *xmin;    // MH_KHF_MIN: the smallest fed value
+    unsigned long long *fed;     // [MH_FED_SLOTS] AddHash calls, spread over slots like min_slots
+    uint32_t S, mode;
+};
+hipError_t launch_minhash_list(hipStream_t s, const MinimizerList &ml, uint64_t n_reads, const MinHashState &M);
+hipError_t launch_minhash_table(hipStream_t s, const uint64_t *d_table, uint64_t table_total, const MinHashState &M);
+// MinHash.Merge of n host-order values already copied to d_vals
+hipError_t launch_minhash_merge(hipStream_t s, const uint64_t *d_vals, uint32_t n, int khf, const MinHashState &M);
+
 // bytes of dynamic LDS per wave / per workgroup for k_minimizer_bin
 size_t minimizer_lds_per_wave(uint32_t xcap, uint32_t tab_size);
 size_t minimizer_lds_per_block(uint32_t xcap, uint32_t tab_size, int waves);
@@ -98,7 +115,7 @@ hipError_t launch_minimizer_bin(hipStream_t s, const uint8_t *d_bases, const uin
                                 uint64_t n_reads, MinimizerParams P, int block_threads,
                                 uint32_t *d_hist, DevState *d_state, unsigned long long *d_min_slots,
                                 const uint32_t *d_read_list, const uint32_t *d_read_list_count,
-                                uint32_t list_blocks);
+                                uint32_t list_blocks, const MinHashState *mh = nullptr);
 hipError_t launch_minimizer_fast(hipStream_t s, const uint8_t *d_bases, const uint64_t *d_offsets,
                                  uint64_t n_reads, MinimizerParams P, const MinimizerList &ml,
                                  DevState *d_state, unsigned long long *d_min_slots);

@@ -3,7 +3,7 @@
 //       k_minimizer_bin    reads of up to 1024 k-mer positions, any bytes (fused jump hash + atomics)
 //       k_long_hash/k_long_emit   long reads and contigs, grouped launches
 // All kernels are wave64 code for CDNA4; none of them has a CPU or library fallback.
-#include "hulk_device.h"
+#include "hulk_minhash.h"
 
 #include <type_traits>
 
@@ -35,13 +35,16 @@ __device__ __forceinline__ uint8_t nt4_of(unsigned c) {
     return 4;
 }
 
+// MH: the context keeps MinHash sketches (hulk_minhash.h) — every value that leaves the queue for the jump hash is fed to them
+// too.  The instance without them is the kernel as it was.
+template <bool MH>
 __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict__ bases,
                                                        const uint64_t *__restrict__ offsets,
                                                        uint64_t n_reads, MinimizerParams P,
                                                        uint32_t *__restrict__ hist, DevState *st,
                                                        unsigned long long *__restrict__ min_slots,
                                                        const uint32_t *__restrict__ read_list,
-                                                       const uint32_t *__restrict__ read_list_count) {
+                                                       const uint32_t *__restrict__ read_list_count, MinHashState M) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint8_t *lut = smem;
     if (read_list) {                                // second pass over the reads the fast kernel deferred
@@ -78,6 +81,7 @@ __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict
     unsigned long long nmin = 0;     // wave-uniform
     const uint32_t dbg = P.debug;    // ablation switches for tools/archive/k1_ablate.py (0 in production)
     uint32_t sink = 0;
+    uint64_t mh_min = ~0ull;         // MH: the lane's smallest fed value (MH_KHF_MIN)
 
     if (!read_list && blockIdx.x == 0 && threadIdx.x == 0 && n_reads)
         atomicAdd(&st->total_len, (unsigned long long)(offsets[n_reads] - offsets[0]));
@@ -216,6 +220,7 @@ __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict
                 const uint32_t xs = qs[lane];
                 const uint64_t keep = (lane + 64u < qn) ? q[lane + 64] : 0;
                 const uint32_t keeps = (lane + 64u < qn) ? qs[lane + 64] : 0;
+                if (MH) mh_feed_wave(M, x, true, mh_min);
                 const int32_t bin = (dbg & 2u) ? (int32_t)((uint32_t)(x >> 20) & 0xffffu) : jump_hash(x, P.num_bins);
                 if (dbg & 1u) sink += (uint32_t)bin; else
                 atomicAdd(&hist[(size_t)xs * (size_t)P.num_bins + bin], 1u);
@@ -230,10 +235,12 @@ __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict
         wave_sync();
     }
     if (qn) {
+        if (MH) mh_feed_wave(M, (uint32_t)lane < qn ? q[lane] : ~0ull, (uint32_t)lane < qn, mh_min);
         if ((uint32_t)lane < qn)
             atomicAdd(&hist[(size_t)qs[lane] * (size_t)P.num_bins + jump_hash(q[lane], P.num_bins)], 1u);
         nmin += qn;
     }
+    if (MH) mh_finish_wave(M, mh_min);
     // same-address atomics serialise at ~12 ns each on this chip: every block adds to its own slot of
     // min_slots[] instead (an atomic all the same: launches of the two work lanes run side by side)
     __shared__ unsigned long long blk_nmin[4];
@@ -243,6 +250,7 @@ __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict
         unsigned long long t = 0;
         for (int x = 0; x < nw; x++) t += blk_nmin[x];
         if (t) atomicAdd(&min_slots[blockIdx.x], t);
+        if (MH && t) atomicAdd(&M.fed[blockIdx.x & (MH_FED_SLOTS - 1)], t);
     }
     if (dbg && sink == 0xdeadbeefu) hist[0] = sink;     // keep ablated work alive
 }
@@ -1179,7 +1187,7 @@ hipError_t launch_minimizer_bin(hipStream_t s, const uint8_t *d_bases, const uin
                                 uint64_t n_reads, MinimizerParams P, int block_threads,
                                 uint32_t *d_hist, DevState *d_state, unsigned long long *d_min_slots,
                                 const uint32_t *d_read_list, const uint32_t *d_read_list_count,
-                                uint32_t list_blocks) {
+                                uint32_t list_blocks, const MinHashState *mh) {
     if (n_reads == 0) return hipSuccess;
     const int waves = block_threads / 64;
     P.lds_per_wave = (uint32_t)minimizer_lds_per_wave(P.xcap, P.tab_size);
@@ -1188,14 +1196,19 @@ hipError_t launch_minimizer_bin(hipStream_t s, const uint8_t *d_bases, const uin
     if (blocks > MIN_SLOTS) blocks = MIN_SLOTS;
     if (blocks < 1) blocks = 1;
     if (d_read_list) blocks = list_blocks;            // size unknown on the host: small fixed grid
+    const bool feed = mh && mh->mode;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_minimizer_bin,
+        hipError_t e = hipFuncSetAttribute(feed ? (const void *)k_minimizer_bin<true> : (const void *)k_minimizer_bin<false>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     prof_mark(s, "k_minimizer_bin");
-    hipLaunchKernelGGL(k_minimizer_bin, dim3((unsigned)blocks), dim3(block_threads), lds, s, d_bases,
-                       d_offsets, n_reads, P, d_hist, d_state, d_min_slots, d_read_list, d_read_list_count);
+    if (feed)
+        hipLaunchKernelGGL(k_minimizer_bin<true>, dim3((unsigned)blocks), dim3(block_threads), lds, s, d_bases,
+                           d_offsets, n_reads, P, d_hist, d_state, d_min_slots, d_read_list, d_read_list_count, *mh);
+    else
+        hipLaunchKernelGGL(k_minimizer_bin<false>, dim3((unsigned)blocks), dim3(block_threads), lds, s, d_bases,
+                           d_offsets, n_reads, P, d_hist, d_state, d_min_slots, d_read_list, d_read_list_count, MinHashState{});
     return hipGetLastError();
 }
 

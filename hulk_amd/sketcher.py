@@ -292,6 +292,32 @@ class GpuSketcher:
         mins, weights = self.sketch()
         return HistoSketch(self.k, mins, weights, self.num_bins, self.decay_ratio != 1.0)
 
+    # ---- the MinHash sketches of a context created with HULK_FLAG_KMV / HULK_FLAG_KHF (boss.CollectKMVsketch / CollectKHFsketch)
+    def minhash(self, algo):
+        """(signature as np.uint64, AddHash calls so far) — hulk_get_minhash.  algo: HULK_MINHASH_KMV (the sketch_size
+        smallest fed values, ascending; fewer while fewer were fed) or HULK_MINHASH_KHF (sketch_size slots)."""
+        mins = np.zeros(self.sketch_size, dtype=np.uint64)
+        n, fed = ctypes.c_uint32(), ctypes.c_uint64()
+        self._chk(self._L.hulk_get_minhash(self._ctx, algo, mins.ctypes.data, ctypes.byref(n), ctypes.byref(fed)))
+        return mins[:n.value].copy(), int(fed.value)
+
+    def minhash_merge(self, algo, mins):
+        """MinHash.Merge: fold a signature of the same kind into the context's (hulk_minhash_merge)."""
+        mins = np.ascontiguousarray(mins, dtype=np.uint64)
+        self._chk(self._L.hulk_minhash_merge(self._ctx, algo, mins.ctypes.data, len(mins)))
+
+    def kmv_sketch(self):
+        """The fed KMV sketch as sketchio.KMVSketch (`num` = entries held: SetSketch overwrites SketchSize)."""
+        from .sketchio import KMVSketch
+        mins, _ = self.minhash(_lib.HULK_MINHASH_KMV)
+        return KMVSketch(self.k, len(mins), mins)
+
+    def khf_sketch(self):
+        """The fed KHF sketch as sketchio.KHFSketch."""
+        from .sketchio import KHFSketch
+        mins, _ = self.minhash(_lib.HULK_MINHASH_KHF)
+        return KHFSketch(self.k, self.sketch_size, mins)
+
     def histogram(self):
         h = np.zeros(self.num_bins, dtype=np.uint32)
         self._chk(self._L.hulk_get_histogram(self._ctx, h.ctypes.data))

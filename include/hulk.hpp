@@ -45,6 +45,8 @@ struct SketchInfo {
     double DecayRatio = 1.0;       // -x
     int32_t SpectrumSize = 0;      // 0 = Pow(KmerSize, 4)  (cmd/sketch.go:118)
     int Device = 0;
+    bool KMV = false, KHF = false; // feed the MinHash sketches (HULK_FLAG_KMV / HULK_FLAG_KHF): the reference's boss constructs
+                                   // both and never feeds them (boss.go:18-19); Boss::CollectKMVsketch / CollectKHFsketch need these
     unsigned Rank = 0, World = 1;  // multi-GPU: this process is rank Rank of World (one GPU each); it owns the sketch
                                    // slots [S*Rank/World, S*(Rank+1)/World) and Boss::Shard connects it to the others
 };
@@ -143,6 +145,15 @@ class Boss {
         return hs;
     }
 
+    // theBoss.CollectKMVsketch / CollectKHFsketch (boss.go:44-51) of a Boss created with SketchInfo.KMV / .KHF: the signature
+    // over every read added so far — KMV: the SketchSize smallest values of the multiset, ascending (fewer while fewer were
+    // fed); KHF: SketchSize slots.  Without the flag: hulk::Error(HULK_ERR_STATE).
+    std::vector<uint64_t> CollectKMVsketch() { return collect(HULK_MINHASH_KMV); }
+    std::vector<uint64_t> CollectKHFsketch() { return collect(HULK_MINHASH_KHF); }
+    // MinHash.Merge (khf.go:49-55): fold another Boss's signature (another rank's share of the stream) into this one's
+    void MergeKMVsketch(const std::vector<uint64_t> &mins) { push(); check(hulk_minhash_merge(ctx_, HULK_MINHASH_KMV, mins.data(), (uint32_t)mins.size())); }
+    void MergeKHFsketch(const std::vector<uint64_t> &mins) { push(); check(hulk_minhash_merge(ctx_, HULK_MINHASH_KHF, mins.data(), (uint32_t)mins.size())); }
+
     hulk_ctx *handle() { return ctx_; }
 
  private:
@@ -151,6 +162,7 @@ class Boss {
         hulk_params p{};
         p.k = info.KmerSize; p.w = info.WindowSize; p.sketch_size = info.SketchSize; p.num_bins = info.SpectrumSize;
         p.decay_ratio = info.DecayRatio; p.interval = info.Interval; p.device = info.Device;
+        p.flags = (info.KMV ? HULK_FLAG_KMV : 0u) | (info.KHF ? HULK_FLAG_KHF : 0u);
         if (info.World > 1) {
             p.slot_begin = (uint32_t)((uint64_t)info.SketchSize * info.Rank / info.World);
             p.slot_count = (uint32_t)((uint64_t)info.SketchSize * (info.Rank + 1) / info.World) - p.slot_begin;
@@ -175,6 +187,14 @@ class Boss {
         check(rc);
     }
     void check(int rc) { if (rc != HULK_OK) throw Error(rc, hulk_last_error(ctx_)); }
+    std::vector<uint64_t> collect(int algo) {
+        push();
+        std::vector<uint64_t> mins(info_.SketchSize ? info_.SketchSize : 1);
+        uint32_t n = 0;
+        check(hulk_get_minhash(ctx_, algo, mins.data(), &n, nullptr));
+        mins.resize(n);
+        return mins;
+    }
 
     hulk_ctx *ctx_ = nullptr;
     SketchInfo info_;

@@ -31,6 +31,12 @@
  *   SeqMinimizer.Run's AddSeq / Flush loop when the read stream   hulk_comm_init + hulk_step_sharded
  *       is sharded over several GPUs                                (+ hulk_gather_sketch for
  *       src/pipeline/sketch.go:182-250, boss.go:24-41               Sketcher.Run's result, sketch.go:271-301)
+ *   minhash.KMVsketch.AddHash         src/minhash/kmv.go:39-71     HULK_FLAG_KMV (fed by hulk_add_reads* and every
+ *   minhash.KHFsketch.AddHash         src/minhash/khf.go:34-45     HULK_FLAG_KHF  other entry point that bins reads)
+ *   MinHash.Merge                     src/minhash/khf.go:49-55     hulk_minhash_merge
+ *   theBoss.CollectKMVsketch /        src/pipeline/boss.go:44-51   hulk_get_minhash
+ *       CollectKHFsketch                (the reference constructs both sketches, boss.go:70-71, and never feeds them:
+ *                                        "not used yet", boss.go:18-19 — feeding them is this library's addition, opt-in)
  *
  * Conventions: every call returns HULK_OK (0) or a negative HULK_ERR_*; the message the
  * reference would have passed to log.Fatalf("ERROR---> %v") is available from
@@ -109,6 +115,13 @@ extern "C" {
                                      * 3 GB per lane at the defaults): they grow with the first batches instead, at the price of an
                                      * allocation in the middle of the stream.  For contexts that see few or long reads, or many
                                      * contexts (ranks) on one GPU. */
+
+#define HULK_FLAG_KMV 128u         /* feed a bottom-k MinHash with every read's distinct minimizers */
+#define HULK_FLAG_KHF 256u         /* feed a k-hash-functions MinHash likewise */
+/* With either flag sketch_size must be 1 .. HULK_MINHASH_MAX_SKETCH (HULK_ERR_ARG otherwise; unrestricted without them), and
+ * the context holds 3 x sketch_size x 8 bytes + 2 KiB of device memory more (both signatures, a merge staging buffer, counters);
+ * a context without the flags allocates none of it and launches the kernels it launched before. */
+#define HULK_MINHASH_MAX_SKETCH 4096u
 
 /* Largest k-mer spectrum this build bins: the binning kernels pack (spectrum slot << 20 | bin) into one dword
  * (k^4 = 923,521 < 2^20 at the reference's maximum k = 31; cmd/sketch.go:118). */
@@ -391,6 +404,27 @@ int hulk_synchronize(hulk_ctx *ctx);
 int hulk_get_sketch(hulk_ctx *ctx, uint64_t *mins, double *weights);
 int hulk_get_counters(hulk_ctx *ctx, uint64_t *n_reads, uint64_t *n_minimizers, uint64_t *total_len);
 int hulk_get_histogram(hulk_ctx *ctx, uint32_t *bins);
+/* ---- the MinHash sketches of `hulk sketch --kmv / --khf` (HULK_FLAG_KMV / HULK_FLAG_KHF) -------------------------------------
+ * Both are fed what the boss's collector feeds the k-mer spectrum (boss.go:90-95): for every read, each of its DISTINCT minimizer
+ * values hash64(kmer) << 8 | span once — the values hulk_get_counters' n_minimizers counts; a value that occurs in R reads is fed R
+ * times.  Interval, decay and slot sharding do not apply; a rank of a sharded run accumulates the MinHash of ITS reads (the host
+ * gathers the signatures and merges them).
+ *   KMV (kmv.go:39-71): AddHash keeps the sketch_size smallest values of the fed MULTISET (no de-duplication); mins[0 .. *n) ascending,
+ *       *n = min(sketch_size, values fed + values merged in).
+ *   KHF (khf.go:34-45): mins[i] = min over fed x of (x + i * x) mod 2^64, MaxUint64 while nothing was fed; *n = sketch_size.
+ * Order-independent, so bit-exact whatever the batching.  The KHF feed is one min-reduction while 2k + 8 + ceil(log2 sketch_size)
+ * <= 64 (no product can wrap: the signature is (i+1) * min(x)); beyond that every value updates every slot (profiles/minhash.txt
+ * has the price). */
+#define HULK_MINHASH_KMV 0
+#define HULK_MINHASH_KHF 1
+/* synchronises; mins[sketch_size]; *n = entries held (KMV: min(sketch_size, fed), ascending; KHF: sketch_size);
+ * *n_fed = AddHash calls so far (may be NULL).  HULK_ERR_STATE if the context was created without the flag.  Valid on a finished
+ * context; on a context with a sticky error it returns that error. */
+int hulk_get_minhash(hulk_ctx *ctx, int algo, uint64_t *mins, uint32_t *n, uint64_t *n_fed);
+/* MinHash.Merge: fold a signature of the same kind (host array, n entries; KHF needs n == sketch_size, else HULK_ERR_ARG) into the
+ * context's: KHF slot-wise minimum (khf.go:49-55), KMV the sketch_size smallest of the two multisets together. */
+int hulk_minhash_merge(hulk_ctx *ctx, int algo, const uint64_t *mins, uint32_t n);
+
 /* Count-min counters as fp64 [7][2000] (test hook). */
 int hulk_get_cms(hulk_ctx *ctx, double *counters);
 /* Copy rows of the CWS tables owned by this context to host: each [slot_count][num_bins] (test hook). */
