@@ -149,7 +149,7 @@ int hulk_create(const hulk_params *params, hulk_ctx **out) {
     };
     c->T = knob("HULK_BATCH", p.batch, SCAN_BATCH_MAX, 1, SCAN_BATCH_MAX);
     // Two work lanes by default — unless count-min decay is on: the replay kernels of that flush hold a CU's whole LDS (112 KB
-    // of counters), a second binning lane keeps k_minimizer_fast workgroups (4 x 39.7 KB) resident on every CU twice as much
+    // of counters), a second binning lane keeps k_minimizer_fast workgroups (5 x 31.5 KB) resident on every CU twice as much
     // of the time, and the flush, which the next batch on the same ring waits for, no longer finds CUs: C3-shaped
     // 9.3e8 -> 3.0-5.2e8 reads/s with two lanes, C2 +2-4 % (profiles/r04_lanes.txt)
     const bool decay_on = p.decay_ratio > 0.0 && p.decay_ratio < 1.0;

@@ -264,12 +264,14 @@ __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict
 // register slots) so the w independent hash chains interleave.  With blocks of exactly w
 // positions the windowed minimum is the van Herk/Gil-Werman form: min(suffix-min of the previous
 // block — fetched from the neighbouring lane with DPP row_shr:1 —, prefix-min of the own block).
-// Per-read set semantics: a 128-entry open-addressing set per group; all run-start values of a
-// lane are inserted with back-to-back LDS compare-and-swaps (one round trip), collisions probe on.
+// Per-read set semantics: a 128-entry open-addressing set per group, holding the INDEX of a candidate (run-start value) in
+// the group's candidate list; all candidates of a lane are inserted with back-to-back 32-bit LDS compare-and-swaps (one
+// round trip); a slot found occupied names the candidate to compare with: equal = duplicate, different = probe on.
 // Eligible reads: no code-4 base, 1 <= w <= WM <= 16, k-mer positions <= 16*w, length <= 256,
 // <= 64 run starts.  Anything else is marked in the region's deferred mask and handled by k_minimizer_bin.
 //
-// LDS per group: tab[128] u64 | pk[20] u32 | pkn[20] u32 (code-4 flags)      per wave: raw ASCII of its 16 reads      per group: cs[64] u64
+// LDS: 16 x tab[128] u32 (8,192 B) | 16 x pk[20] u32 | 16 x pkn[20] u32 (code-4 flags; 2,560 B) | per wave: raw ASCII of its 16
+// reads (4 x 3,136 B; PAIR 4 x 5,184) | 16 x cs[64] u64 (8,192 B) = 31,488 B (PAIR 39,680): 5 (4) workgroups per CU
 // ------------------------------------------------------------------------------------------
 #ifndef HULK_FAST_TAB
 #define HULK_FAST_TAB 128
@@ -282,6 +284,15 @@ constexpr int FAST_PAD = HULK_FAST_PAD;
 constexpr int FAST_CAND = 64;          // max run starts per read on the fast path
 constexpr int FAST_RAW = 3072 + 64;    // raw ASCII of the wave's 16 reads, staged once (bytes per wave)
 constexpr int FAST_RAW_PAIR = 5120 + 64;   // ... when two groups share a read (reads of up to ~300 bases)
+// The per-read set holds 32-bit INDICES into the candidate list(s) of the read, not the 64-bit values: a candidate is
+// new iff its compare-and-swap (empty -> own index) finds the slot empty; an occupied slot names the candidate to compare with.
+constexpr uint32_t TAB_EMPTY32 = 0xFFFFFFFFu;
+constexpr int FAST_TAB_BYTES = 16 * FAST_TAB * 4;   // the 16 groups' tables
+// The probe loops end because a slot is only ever filled by a candidate's own compare-and-swap: at most FAST_CAND (a pair:
+// 2 * FAST_CAND) of the FAST_TAB (2 * FAST_TAB) slots are taken, so a probe sequence always meets an empty slot or its value.
+static_assert(FAST_TAB > FAST_CAND, "the set must keep more slots than a read can have candidates (finite probe loops)");
+static_assert((FAST_TAB & (FAST_TAB - 1)) == 0 && FAST_TAB % 16 == 0, "slot masks and the per-lane clear");
+static_assert(2 * FAST_CAND <= 0x7fffffff, "candidate indices must not reach TAB_EMPTY32");
 
 __device__ __forceinline__ uint32_t dpp_row_shr1(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
@@ -303,6 +314,19 @@ __device__ __forceinline__ uint64_t mul_u32_u64(uint32_t a, uint32_t b) {
 __device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t d;
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b), "v"(c));
+    return d;
+}
+// ... with a multiplier that is an inline constant (<= 64): an "s" operand would hold a scalar register for it
+template <uint32_t B> __device__ __forceinline__ uint64_t mul_u32_u64_inl(uint32_t a) {
+    static_assert(B <= 64, "inline constants are 0..64");
+    uint64_t d, carry;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(d), "=s"(carry) : "v"(a), "n"(B));
+    return d;
+}
+template <uint32_t B> __device__ __forceinline__ uint32_t mad_u24_inl(uint32_t a, uint32_t c) {
+    static_assert(B <= 64, "inline constants are 0..64");
+    uint32_t d;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "n"(B), "v"(c));
     return d;
 }
 template <bool FM> __device__ __forceinline__ uint64_t hash64_fm(uint64_t key, uint64_t mask) {
@@ -348,8 +372,8 @@ template <int KC> __device__ __forceinline__ uint64_t hash64_pack_kc(uint64_t ke
     hi = mad_u24(hi, 265u, (uint32_t)(p >> 32)) & HM; lo = (uint32_t)p;
     lo ^= __builtin_amdgcn_alignbit(hi, lo, 14);                   // key ^= key >> 14
     if (2 * KC - 32 > 14) hi ^= hi >> 14;
-    p = mul_u32_u64(lo, 21u);                                      // key + (key << 2) + (key << 4)
-    hi = mad_u24(hi, 21u, (uint32_t)(p >> 32)) & HM; lo = (uint32_t)p;
+    p = mul_u32_u64_inl<21u>(lo);                                  // key + (key << 2) + (key << 4)
+    hi = mad_u24_inl<21u>(hi, (uint32_t)(p >> 32)) & HM; lo = (uint32_t)p;
     lo ^= __builtin_amdgcn_alignbit(hi, lo, 28);                   // key ^= key >> 28
     p = mul_u32_u64(lo, 0x80000001u);                              // key + (key << 31)
     hi = ((uint32_t)(p >> 32) + hi) & HM; lo = (uint32_t)p;
@@ -374,8 +398,15 @@ template <bool FM> __device__ __forceinline__ uint64_t umin64(uint64_t a, uint64
 // PAIR: two neighbouring 16-lane groups share a read (2 x 16w - (w-1) k-mer positions: 300 bp at k = 21, w = 9).
 // The second group starts w-1 positions before the first one ends, so that every window it reports is complete,
 // and reports nothing for those w-1 positions; both groups feed the same per-read set.
+// Workgroups per CU each instance's REGISTERS are budgeted for (a 256-thread workgroup is one wave per SIMD).  The w = 9
+// instances with k fixed at compile time (hulk's default k = 21, and k = 31), single and PAIR, fit 5 (<= 96 VGPRs) with
+// nothing spilled; every other instance keeps 4 (<= 128; the WM = 16 ones are at 128 already).  What the LDS admits is
+// tied to this by the static_asserts at minimizer_fast_lds.
+template <int WM, bool DBG, bool WEQ, int KC> constexpr int fast_blocks_per_cu() {
+    return (WM == 9 && !DBG && WEQ && (KC == 21 || KC == 31)) ? 5 : 4;
+}
 template <int WM, bool FM, bool DBG, bool WEQ, int KC, bool PAIR>
-__global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__restrict__ bases,
+__global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void k_minimizer_fast(const uint8_t *__restrict__ bases,
                                                         const uint64_t *__restrict__ offsets,
                                                         uint64_t n_reads, MinimizerParams P,
                                                         MinimizerList ml, DevState *st,
@@ -422,15 +453,17 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
     const int half = PAIR ? (grp & 1) : 0;                         // which half of the read this group takes
     const int sub = PAIR ? ((grp & 3) >> 1) : (grp & 3);           // read of the iteration
     const int32_t posoff = half ? 16 * w - (w - 1) : 0;            // first k-mer position of this group
-    uint64_t *tab = (uint64_t *)(smem + FAST_PAD) + (size_t)(PAIR ? (grp & ~1) : grp) * FAST_TAB;   // the per-read set
-    uint32_t *pk32 = (uint32_t *)(smem + FAST_PAD + 16 * FAST_TAB * 8) + grp * 20;
-    uint32_t *pkn32 = (uint32_t *)(smem + FAST_PAD + 16 * FAST_TAB * 8 + 16 * 20 * 4) + grp * 20;   // "code 4" flags, pk's layout
-    uint32_t *raw32 = (uint32_t *)(smem + FAST_PAD + 16 * FAST_TAB * 8 + 2 * 16 * 20 * 4) + (size_t)wid * (RAWB / 4);
-    uint64_t *cs = (uint64_t *)(smem + FAST_PAD + 16 * FAST_TAB * 8 + 2 * 16 * 20 * 4 + 4 * RAWB) + (size_t)grp * FAST_CAND;
+    uint32_t *tab = (uint32_t *)(smem + FAST_PAD) + (size_t)(PAIR ? (grp & ~1) : grp) * FAST_TAB;   // the per-read set (candidate indices)
+    uint32_t *pk32 = (uint32_t *)(smem + FAST_PAD + FAST_TAB_BYTES) + grp * 20;
+    uint32_t *pkn32 = (uint32_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 16 * 20 * 4) + grp * 20;   // "code 4" flags, pk's layout
+    uint32_t *raw32 = (uint32_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 2 * 16 * 20 * 4) + (size_t)wid * (RAWB / 4);
+    uint64_t *cs = (uint64_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 2 * 16 * 20 * 4 + 4 * RAWB) + (size_t)grp * FAST_CAND;
+    // what a set index addresses: the group's own candidates, or (PAIR) the pair's two neighbouring lists as one
+    const uint64_t *csp = PAIR ? cs - (size_t)half * FAST_CAND : cs;
     {   // every group empties its OWN table (a pair's set spans both of its groups' tables)
-        uint64_t *own = (uint64_t *)(smem + FAST_PAD) + (size_t)grp * FAST_TAB;
+        uint32_t *own = (uint32_t *)(smem + FAST_PAD) + (size_t)grp * FAST_TAB;
 #pragma unroll
-        for (int x = 0; x < FAST_TAB / 16; x++) own[gl + 16 * x] = TAB_EMPTY;
+        for (int x = 0; x < FAST_TAB / 16; x++) own[gl + 16 * x] = TAB_EMPTY32;
     }
     __syncthreads();
 
@@ -454,7 +487,10 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
     const uint32_t nrd = wave_first < n_reads ? (uint32_t)((n_reads - wave_first < FAST_READS_PER_WAVE) ? n_reads - wave_first : FAST_READS_PER_WAVE) : 0u;
     uint64_t myoff = 0;
     if ((uint32_t)lane <= nrd && nrd) myoff = offsets[wave_first + (uint32_t)lane];
-    const uint64_t span_lo = __shfl(myoff, 0), span_hi = __shfl(myoff, (int)nrd);
+    // (wave-uniform, read into SGPRs: as VGPRs they stayed live across the main loop)
+    const uint32_t nrd_s = __builtin_amdgcn_readfirstlane(nrd);
+    const uint64_t span_lo = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)myoff) | (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(myoff >> 32)) << 32;
+    const uint64_t span_hi = (uint64_t)__builtin_amdgcn_readlane((uint32_t)myoff, nrd_s) | (uint64_t)__builtin_amdgcn_readlane((uint32_t)(myoff >> 32), nrd_s) << 32;
     const uintptr_t raw_a0 = ((uintptr_t)bases + span_lo) & ~(uintptr_t)15;
     const uintptr_t raw_end = (uintptr_t)bases + span_hi;
     const bool bulk = nrd && (raw_end - raw_a0) <= (uintptr_t)(RAWB - 64);
@@ -508,6 +544,11 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
     for (int it = 0; it < FAST_READS_PER_WAVE / RPI; it++) {
         if ((uint32_t)(RPI * it) >= nrd) break;
         const uint32_t idx = (uint32_t)(RPI * it + sub);       // read of the wave
+        // gl and half once more, opaque to the optimiser, for the loop's per-lane PREDICATES (gl == 0, half, ...): computed
+        // from gl and half themselves each of them is loop-invariant, is hoisted, and then holds a 64-bit lane mask — two
+        // scalar registers — across the whole loop; one v_cmp where it is used is cheaper than the registers.
+        int glq = gl, halfq = half;
+        if (KC != 0 && WEQ) { asm volatile("" : "+v"(glq)); if (PAIR) asm volatile("" : "+v"(halfq)); }
         bool act = idx < nrd;                                  // group-uniform
         uint32_t hslot = slot0;
         if (crosses) {                                          // wave-uniform: an interval ends inside the wave's reads
@@ -522,8 +563,7 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
         bool defer = false;
         if (act) {
             if (wide) defer = true;
-            else if (L < 1) { if (gl == 0) set_error(st, -3); act = false; }
-            else if (L < w + k - 1) { if (gl == 0) set_error(st, -4); act = false; }
+            else if (L < 1 || L < w + k - 1) { if (gl == 0) set_error(st, L < 1 ? -3 : -4); act = false; }   // (one atomic's operands to keep around, not two)
             else {
                 npos = L - k + 1;
                 if (npos > (PAIR ? 2 * 16 * w - (w - 1) : 16 * w) || L > (PAIR ? 512 : 256)) defer = true;
@@ -604,8 +644,8 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
                 }
             }
             pk32[gl] = pack;
-            if (gl < 4) pk32[16 + gl] = 0;                     // slack for 3-dword window reads
-            if (NV) { pkn32[gl] = npack; if (gl < 4) pkn32[16 + gl] = 0; }
+            if (glq < 4) pk32[16 + gl] = 0;                    // slack for 3-dword window reads
+            if (NV) { pkn32[gl] = npack; if (glq < 4) pkn32[16 + gl] = 0; }
         }
         {
             // a byte the kernel cannot take anywhere in the read defers it as a whole (both groups of a pair must agree)
@@ -699,6 +739,13 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
                 const uint64_t rv = __brevll(Fn) >> (64 - 2 * NBW);
                 Hb = ((rv >> 1) & 0x5555555555555555ull) | ((rv & 0x5555555555555555ull) << 1);
             }
+            // span = min(span0 + t, k) is k everywhere but in the read's first block (ap0 == 0: k - (w-1-t)), since every
+            // other block starts at ap0 >= w.  With k and w fixed, one select between two constants per position — computed
+            // here, behind an opaque copy of ap0: left visible, the nine loop-invariant spans are hoisted out of the main
+            // loop and occupy nine VGPRs across all of it.
+            uint32_t ap0_now = (uint32_t)ap0;
+            if (KC != 0 && WEQ) asm volatile("" : "+v"(ap0_now));
+            const bool first_block = ap0_now == 0u;
             auto phaseA = [&](auto nvx_tag) {
             constexpr bool NVX = decltype(nvx_tag)::value;
 #pragma unroll
@@ -735,8 +782,9 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
                     // (k = 31 with an N as the last base: r carries bit 62, and with A or N in the four bases before it its
                     //  bit pattern is a signalling NaN, which v_min_f64 does not pass through — integer minimum there)
                     const uint64_t canon = (NVX && k >= 31) ? (f < r ? f : r) : umin64<true>(f, r);
-                    int32_t span = span0 + t;
-                    if (span >= k) span = k;
+                    int32_t span;
+                    if (KC != 0 && WEQ) span = first_block ? k - (w - 1 - t) : k;
+                    else { span = span0 + t; if (span >= k) span = k; }
                     uint64_t x;
                     if (HP && !(dbg & 16u)) x = hash64_pack_kc<HP ? KC : 21>(canon, (uint32_t)span);
                     else if (KEY5) x = (hash64(canon, mask) & 0x00FFFFFFFFFFFFFFull) << 5 | (uint64_t)(uint32_t)span;
@@ -773,7 +821,7 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
             const uint64_t whole = dpp_row_shr1_u64(hp[0]);    // min of the whole previous block
             // lane 0 of a row has no previous block: DPP hands it zeros, which "no value" (+inf, FM) differs from in
             // the upper dword only — one v_or per value instead of a 64-bit select
-            const uint64_t xnfix = gl == 0 ? XN : 0ull;
+            const uint64_t xnfix = glq == 0 ? XN : 0ull;
 #pragma unroll
             for (int t = 0; t < WM - 1; t++) {
                 const uint64_t v = dpp_row_shr1_u64(hp[t + 1]);
@@ -798,9 +846,9 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
             {
                 const int32_t t1 = (w - 1) - (k - 1) - ap0;
                 if (t1 > 0) emitbits &= ~((1u << t1) - 1u);
-                if (PAIR && half) { const int32_t t2 = (w - 1) - p0; if (t2 > 0) emitbits &= ~((1u << t2) - 1u); }
+                if (PAIR && halfq) { const int32_t t2 = (w - 1) - p0; if (t2 > 0) emitbits &= ~((1u << t2) - 1u); }
             }
-            const uint32_t pe0 = (gl > 0 && ((pv >> (w - 1)) & 1u) && (ap0 - 1 + k - 1 >= w - 1) && !(half && p0 - 1 < w - 1)) ? 1u : 0u;
+            const uint32_t pe0 = (glq > 0 && ((pv >> (w - 1)) & 1u) && (ap0 - 1 + k - 1 >= w - 1) && !(halfq && p0 - 1 < w - 1)) ? 1u : 0u;
             // a run starts where a reporting position does not repeat the value of a reporting predecessor
             startbits = emitbits & ~(((emitbits << 1) | pe0) & eqbits);
         }
@@ -828,7 +876,7 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
             // deferred reads are marked in the region's mask (one store per wave at the end): a compact list is built by
             // k_region_offsets.  (An atomicAdd on ONE list counter per deferred read serialised at ~12 ns each: 5 % of
             // reads with an N doubled this kernel's time.)
-            const uint64_t dbal = __ballot(act && defer && gl == 0 && half == 0);
+            const uint64_t dbal = __ballot(act && defer && glq == 0 && halfq == 0);
             if (PAIR) dmask |= ((uint32_t)(dbal & 1u) | ((uint32_t)(dbal >> 32) & 1u) << 1) << (RPI * it);
             else dmask |= ((uint32_t)(dbal & 1u) | ((uint32_t)(dbal >> 16) & 1u) << 1 | ((uint32_t)(dbal >> 32) & 1u) << 2 |
                            ((uint32_t)(dbal >> 48) & 1u) << 3) << (RPI * it);
@@ -855,22 +903,26 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
             uint64_t x0 = 0, x1 = 0;
             if (a0) x0 = cs[c0];
             if (a1) x1 = cs[c1];
+            const uint64_t r0 = x0, r1 = x1;                       // as the candidate lists hold them (KEY5: keys)
             if (KEY5) { x0 = (x0 & ~31ull) << 3 | (x0 & 31ull); x1 = (x1 & ~31ull) << 3 | (x1 & 31ull); }   // key -> X = hash << 8 | span
             uint32_t sl0 = ((uint32_t)(x0 >> 8) ^ (uint32_t)(x0 >> 37)) & TABM, sl1 = ((uint32_t)(x1 >> 8) ^ (uint32_t)(x1 >> 37)) & TABM;
-            unsigned long long o0 = (unsigned long long)TAB_EMPTY, o1 = (unsigned long long)TAB_EMPTY;
+            const uint32_t i0 = (PAIR ? (uint32_t)half * FAST_CAND : 0u) + c0, i1 = i0 + 16u;   // own indices in csp[]
+            uint32_t o0 = TAB_EMPTY32, o1 = TAB_EMPTY32;
             if (!(dbg & 4u)) {
-                if (a0) o0 = atomicCAS((unsigned long long *)&tab[sl0], (unsigned long long)TAB_EMPTY, (unsigned long long)x0);
-                if (a1) o1 = atomicCAS((unsigned long long *)&tab[sl1], (unsigned long long)TAB_EMPTY, (unsigned long long)x1);
-                while (a0 && o0 != TAB_EMPTY && o0 != x0) {        // occupied by another value: probe on
+                if (a0) o0 = atomicCAS(&tab[sl0], TAB_EMPTY32, i0);
+                if (a1) o1 = atomicCAS(&tab[sl1], TAB_EMPTY32, i1);
+                // occupied: by an equal value (a duplicate: done) or by another one (probe on).  The candidate lists are not
+                // written between the wave_sync() before this phase and the one behind it.
+                while (a0 && o0 != TAB_EMPTY32 && csp[o0] != r0) {
                     sl0 = (sl0 + 1) & TABM;
-                    o0 = atomicCAS((unsigned long long *)&tab[sl0], (unsigned long long)TAB_EMPTY, (unsigned long long)x0);
+                    o0 = atomicCAS(&tab[sl0], TAB_EMPTY32, i0);
                 }
-                while (a1 && o1 != TAB_EMPTY && o1 != x1) {
+                while (a1 && o1 != TAB_EMPTY32 && csp[o1] != r1) {
                     sl1 = (sl1 + 1) & TABM;
-                    o1 = atomicCAS((unsigned long long *)&tab[sl1], (unsigned long long)TAB_EMPTY, (unsigned long long)x1);
+                    o1 = atomicCAS(&tab[sl1], TAB_EMPTY32, i1);
                 }
             }
-            const bool new0 = a0 && o0 == TAB_EMPTY, new1 = a1 && o1 == TAB_EMPTY;
+            const bool new0 = a0 && o0 == TAB_EMPTY32, new1 = a1 && o1 == TAB_EMPTY32;
             myslot[2 * pr] = sl0; myslot[2 * pr + 1] = sl1;
             const uint64_t nb0 = __ballot(new0), nb1 = __ballot(new1);
             if (nb0 | nb1) {
@@ -892,7 +944,7 @@ __global__ __launch_bounds__(256, 4) void k_minimizer_fast(const uint8_t *__rest
         // empty the set again: only the slots this lane filled
 #pragma unroll
         for (int rnd = 0; rnd < FAST_CAND / 16; rnd++)
-            if ((newmask >> rnd) & 1u) tab[myslot[rnd]] = TAB_EMPTY;
+            if ((newmask >> rnd) & 1u) tab[myslot[rnd]] = TAB_EMPTY32;
         wave_sync();
     }
     if (lane == 0 && wave_first < n_reads) { ml.cnt[region] = wcount; ml.dmask[region] = dmask; }
@@ -1212,9 +1264,21 @@ hipError_t launch_minimizer_bin(hipStream_t s, const uint8_t *d_bases, const uin
     return hipGetLastError();
 }
 
-size_t minimizer_fast_lds(uint32_t, bool pair) {
-    return FAST_PAD + 16 * (size_t)FAST_TAB * 8 + 2 * 16 * 20 * 4 + 4 * (size_t)(pair ? FAST_RAW_PAIR : FAST_RAW) + 16 * (size_t)FAST_CAND * 8;
+constexpr size_t fast_lds_bytes(bool pair) {
+    return FAST_PAD + (size_t)FAST_TAB_BYTES + 2 * 16 * 20 * 4 + 4 * (size_t)(pair ? FAST_RAW_PAIR : FAST_RAW) + 16 * (size_t)FAST_CAND * 8;
 }
+// Workgroups per CU by LDS: the dynamic request + the kernel's 32 B of static LDS (blk_nmin), rounded up to the allocation
+// granule (1280 B on gfx950: 160 KB / 128), against the CU's 160 KB.  One read per group: 31,488 + 32 -> 32,000 B, 5 per CU —
+// what fast_blocks_per_cu() budgets the registers of the default instances for.  PAIR: 39,680 + 32 -> 40,960 B, 4 per CU
+// (its registers are budgeted for 5 all the same: the LDS is the limit there until its raw-read staging shrinks).
+constexpr size_t FAST_LDS_GRANULE = 1280, FAST_LDS_STATIC = 32, CU_LDS_BYTES = 160 * 1024;
+constexpr size_t fast_lds_alloc(bool pair) { return (fast_lds_bytes(pair) + FAST_LDS_STATIC + FAST_LDS_GRANULE - 1) / FAST_LDS_GRANULE * FAST_LDS_GRANULE; }
+#if HULK_FAST_PAD == 0 && HULK_FAST_TAB == 128
+static_assert(fast_blocks_per_cu<9, false, true, 21>() == 5 && fast_blocks_per_cu<9, false, true, 31>() == 5, "the default instances are built for 5 workgroups per CU");
+static_assert(5 * fast_lds_alloc(false) <= CU_LDS_BYTES, "k_minimizer_fast: the LDS no longer admits the 5 workgroups per CU its registers are budgeted for");
+static_assert(4 * fast_lds_alloc(true) <= CU_LDS_BYTES, "k_minimizer_fast (PAIR): the LDS no longer admits 4 workgroups per CU");
+#endif
+size_t minimizer_fast_lds(uint32_t, bool pair) { return fast_lds_bytes(pair); }
 
 hipError_t launch_minimizer_fast(hipStream_t s, const uint8_t *d_bases, const uint64_t *d_offsets,
                                  uint64_t n_reads, MinimizerParams P, const MinimizerList &ml,

@@ -511,10 +511,10 @@ hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParam
         // ~131 k keys per part (16 parts per 100k-read interval, swept 49k..197k): a 4-bit counter then overflows only on
         // grossly repetitive input, which the exact kernels below pick up
         // Range size and workgroup shape: a workgroup of 1024 threads that holds 2^18 four-bit counters (up to 128 KB of LDS)
-        // reads every key once, but it only fits a CU that is free of k_minimizer_fast workgroups (4 x 39.7 KB) — and with two
+        // reads every key once, but it only fits a CU that is free of k_minimizer_fast workgroups (5 x 31.5 KB) — and with two
         // work lanes the OTHER lane's are always there: rocprofv3 showed this kernel at 216 us per launch beside them against
         // 41 us alone, waiting for CUs (profiles/r04_kernel_stats.md).  Ranges of 2^16 bins (32 KB) in workgroups of 256 threads
-        // slip in beside three of those; the keys are then read once per range (through the XCD's L2, see the kernel).
+        // slip in beside four of those; the keys are then read once per range (through the XCD's L2, see the kernel).
         static const int rlog = [] { const char *e = HULK_EXP_ENV("HULK_NIB_RLOG"); const int v = e ? atoi(e) : HULK_NIB_RLOG_DEFAULT; return v < 13 ? 13 : v > 18 ? 18 : v; }();
         static const int nib_block = [] { const char *e = HULK_EXP_ENV("HULK_NIB_BLOCK"); const int v = e ? atoi(e) : HULK_NIB_BLOCK_DEFAULT; return v == 256 || v == 512 ? v : 1024; }();
         const int32_t NIB_BINS = 1 << rlog, NIB_WORDS = NIB_BINS >> 3;
