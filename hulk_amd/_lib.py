@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "hulk_step_sliced", "hulk_gather_sketch", "hulk_get_comm_stats", "hulk_get_comm_health", "hulk_release_caches", "hulk_get_device_checks", "hulk_get_profile_table",
     "hulk_load_sketches", "hulk_sketch_set_free", "hulk_sketch_set_info", "hulk_sketch_set_mins", "hulk_sketch_set_weights", "hulk_sketch_set_path",
     "hulk_sketch_set_banner", "hulk_smash_files", "hulk_bgzf_inflate", "hulk_get_minhash", "hulk_minhash_merge",
+    "hulk_set_snapshots", "hulk_snapshot_count", "hulk_get_snapshots", "hulk_set_snapshot_callback", "hulk_poll_snapshots",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -80,6 +81,16 @@ BATCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes
                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64)
 # hulk_exchange_fn: (user, op, send, recv, bytes) -> 0 on success
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64)
+
+
+class SnapshotInfo(ctypes.Structure):
+    """hulk_snapshot_info: 1-based number of the flushed spectrum, reads of the stream when it closed."""
+    _fields_ = [("ordinal", ctypes.c_uint64), ("n_reads", ctypes.c_uint64)]
+
+
+# hulk_snapshot_fn: (user, info, mins, weights, sketch_size) -> 0 to go on
+SNAPSHOT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(SnapshotInfo), ctypes.POINTER(ctypes.c_uint64),
+                               ctypes.POINTER(ctypes.c_double), ctypes.c_uint32)
 
 
 class SmashStats(ctypes.Structure):
@@ -267,6 +278,11 @@ def load():
     L.hulk_release_caches.restype = ctypes.c_int; L.hulk_release_caches.argtypes = []
     L.hulk_get_minhash.restype = ctypes.c_int; L.hulk_get_minhash.argtypes = [vp, ctypes.c_int, vp, vp, vp]
     L.hulk_minhash_merge.restype = ctypes.c_int; L.hulk_minhash_merge.argtypes = [vp, ctypes.c_int, vp, u32]
+    L.hulk_set_snapshots.restype = ctypes.c_int; L.hulk_set_snapshots.argtypes = [vp, u32, u32]
+    L.hulk_snapshot_count.restype = ctypes.c_int; L.hulk_snapshot_count.argtypes = [vp, vp, vp]
+    L.hulk_get_snapshots.restype = ctypes.c_int; L.hulk_get_snapshots.argtypes = [vp, u64, u32, vp, vp, vp]
+    L.hulk_set_snapshot_callback.restype = ctypes.c_int; L.hulk_set_snapshot_callback.argtypes = [vp, SNAPSHOT_FN, vp]
+    L.hulk_poll_snapshots.restype = ctypes.c_int; L.hulk_poll_snapshots.argtypes = [vp, vp]
     _lib = L
     return L
 

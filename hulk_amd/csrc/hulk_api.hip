@@ -290,6 +290,7 @@ void hulk_destroy(hulk_ctx *c) {
     for (auto &H : c->h_long_desc) { if (H.p) hipHostFree(H.p); if (H.ev) hipEventDestroy(H.ev); }
     if (c->ev_long) hipEventDestroy(c->ev_long);
     comm_teardown(c);
+    snap_teardown(c);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
     fq_sweep_idle();
@@ -321,6 +322,7 @@ extern "C" {
 int hulk_add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n,
                           uint32_t max_read_len, uint64_t bases_bytes) {
     if (!c) return HULK_ERR_ARG;
+    if (c->snap.fn_failed) return fail(c, HULK_ERR_STATE, "snapshot callback failed");   // (the callback ended the run)
     if (c->finished) return fail(c, HULK_ERR_STATE, "context already finished");
     if (c->sticky != HULK_OK) return fail(c, c->sticky);
     if (n && (!d_bases || !d_offsets)) return fail(c, HULK_ERR_ARG, "NULL buffer");
@@ -341,11 +343,12 @@ int hulk_add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d
         c->seq_count += chunk; pos += chunk;
         if (I) {                                            // pipeline/sketch.go:211-215
             const uint32_t done = (uint32_t)((fill + chunk) / I);
-            rc = flush_batch(c, done);
+            rc = flush_batch(c, done, nullptr, false, false, FLUSH_INTERVAL);
             if (rc != HULK_OK) return rc;
             c->ring_base = (c->ring_base + done) % c->ring_n;
             if ((fill + chunk) % I == 0) { c->ring_base = 0; if (done) c->cur_ring ^= 1; }  // clean: next batch uses the other ring
         }
+        if (c->snap.fn) { rc = snap_deliver(c, false); if (rc != HULK_OK) return rc; }     // (event queries: snapshots of flushes that have run)
     }
     return HULK_OK;
 }
@@ -354,6 +357,7 @@ int hulk_bin_reads_device_at(hulk_ctx *c, const uint8_t *d_bases, const uint64_t
                              uint32_t max_read_len, uint64_t bases_bytes, uint64_t reads_per_spectrum, uint32_t first_spectrum) {
     if (!c) return HULK_ERR_ARG;
     { const int rcf = fatal_status(c); if (rcf != HULK_OK) return rcf; }
+    { const int rcs = snap_refuse(c, "hulk_bin_reads_device"); if (rcs != HULK_OK) return rcs; }
     if (c->finished) return fail(c, HULK_ERR_STATE, "context already finished");
     if (n && (!d_bases || !d_offsets)) return fail(c, HULK_ERR_ARG, "NULL buffer");
     if (c->ring_base != 0) return fail(c, HULK_ERR_STATE, "a partial interval is pending");
@@ -378,6 +382,7 @@ int hulk_bin_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d
 
 int hulk_flush_batch(hulk_ctx *c, uint32_t count) {
     if (!c) return HULK_ERR_ARG;
+    { const int rcs = snap_refuse(c, "hulk_flush_batch"); if (rcs != HULK_OK) return rcs; }
     if (c->finished) return fail(c, HULK_ERR_STATE, "context already finished");
     if (count > c->T || c->ring_base != 0) return fail(c, HULK_ERR_ARG, "batch count");
     if (count < c->bin_spectra) return fail(c, HULK_ERR_ARG, "fewer spectra flushed than hulk_bin_reads_device filled");
@@ -388,6 +393,7 @@ int hulk_flush_batch(hulk_ctx *c, uint32_t count) {
 
 int hulk_flush_batch_after(hulk_ctx *c, uint32_t count, void *dep_stream) {
     if (!c) return HULK_ERR_ARG;
+    { const int rcs = snap_refuse(c, "hulk_flush_batch"); if (rcs != HULK_OK) return rcs; }
     if (c->finished) return fail(c, HULK_ERR_STATE, "context already finished");
     if (count > c->T || c->ring_base != 0) return fail(c, HULK_ERR_ARG, "batch count");
     if (count < c->bin_spectra) return fail(c, HULK_ERR_ARG, "fewer spectra flushed than hulk_bin_reads_device filled");
@@ -402,6 +408,7 @@ uint32_t *hulk_histogram_device(hulk_ctx *c) { return c ? ring_hist(c) + (size_t
 
 int hulk_add_reads(hulk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n) {
     if (!c) return HULK_ERR_ARG;
+    if (c->snap.fn_failed) return fail(c, HULK_ERR_STATE, "snapshot callback failed");   // (the callback ended the run)
     if (c->finished) return fail(c, HULK_ERR_STATE, "context already finished");
     if (n == 0) return HULK_OK;
     if (!bases || !offsets) return fail(c, HULK_ERR_ARG, "NULL buffer");
@@ -445,12 +452,14 @@ int hulk_add_histogram(hulk_ctx *c, const uint32_t *bins) {
 
 int hulk_flush(hulk_ctx *c) {
     if (!c) return HULK_ERR_ARG;
+    if (c->snap.fn_failed) return fail(c, HULK_ERR_STATE, "snapshot callback failed");   // (the callback ended the run)
     if (c->finished) return fail(c, HULK_ERR_STATE, "context already finished");
     // after hulk_bin_reads_device filled several spectra a flush of ONE would leave the others behind for hulk_finish to
     // flush a second time: they go through hulk_flush_batch[_after]
     if (c->bin_spectra > 1) return fail(c, HULK_ERR_STATE, "hulk_bin_reads_device filled several spectra: use hulk_flush_batch");
     const int rc = flush_batch(c, 1);
     if (rc == HULK_OK) c->bin_spectra = 0;
+    if (rc == HULK_OK && c->snap.fn) return snap_deliver(c, false);
     return rc;
 }
 
@@ -460,13 +469,14 @@ int hulk_finish(hulk_ctx *c) {
     if (!c->finished) {
         // pipeline/sketch.go:219-221; a tail batch of hulk_bin_reads_device may span several spectra (ragged last
         // batch of a multi-GPU run): all of them are flushed, in order
-        int rc = flush_batch(c, c->bin_spectra > 1 ? c->bin_spectra : 1u);
+        int rc = flush_batch(c, c->bin_spectra > 1 ? c->bin_spectra : 1u, nullptr, false, false, FLUSH_EOF);
         if (rc != HULK_OK) return rc;
         c->bin_spectra = 0;
         c->finished = true;
     }
     int rc = check_device_error(c);
     if (rc != HULK_OK) return rc;
+    if (c->snap.fn) { rc = snap_deliver(c, true); if (rc != HULK_OK) return rc; }          // all that remain (every flush has run)
     // "no sequences received" (pipeline/sketch.go:237-239); the histogram test hook is exempt — and so is a rank of a sharded
     // run that happened to hold none of a short stream's intervals: the reference's count is over the global stream
     if (c->seq_count == 0 && !c->hist_hook_used && c->comm.global_intervals == 0) return fail(c, HULK_ERR_NO_SEQ);

@@ -190,6 +190,7 @@ namespace {
 int comm_setup_alloc(hulk_ctx *c, int kind, uint32_t rank, uint32_t world);
 // (a failure half-way leaves nothing behind: the call can be repeated — ADVICE r3)
 int comm_setup(hulk_ctx *c, int kind, uint32_t rank, uint32_t world) {
+    { const int rcs = snap_refuse(c, "hulk_comm_init"); if (rcs != HULK_OK) return rcs; }
     hulk_ctx::Comm &m = c->comm;
     if (m.kind != 0) return fail(c, HULK_ERR_STATE, "the context already has a communicator");
     if (world == 0 || rank >= world) return fail(c, HULK_ERR_ARG, "rank / world");
@@ -266,6 +267,7 @@ static int step_sharded_impl(hulk_ctx *c, const uint8_t *d_bases, const uint64_t
 int hulk_step_sharded(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n, uint32_t max_read_len,
                       uint64_t bases_bytes, uint32_t step_intervals) {
     if (!c) return HULK_ERR_ARG;
+    { const int rcs = snap_refuse(c, "hulk_step_sharded"); if (rcs != HULK_OK) return rcs; }
     const int rc = step_sharded_impl(c, d_bases, d_offsets, n, max_read_len, bases_bytes, step_intervals);
     // a runtime or exchange failure may have left this rank outside a collective its peers are inside of: the communicator is
     // not usable any more, and neither is the run — every later call reports the same status (argument errors, raised before
@@ -395,6 +397,7 @@ static int step_sharded_impl(hulk_ctx *c, const uint8_t *d_bases, const uint64_t
 
 int hulk_step_sharded_host(hulk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n, uint32_t step_intervals) {
     if (!c) return HULK_ERR_ARG;
+    { const int rcs = snap_refuse(c, "hulk_step_sharded_host"); if (rcs != HULK_OK) return rcs; }
     if (n && (!bases || !offsets)) return fail(c, HULK_ERR_ARG, "NULL buffer");
     if (n == 0) return hulk_step_sharded(c, nullptr, nullptr, 0, 0, 0, step_intervals);
     uint64_t max_len = 0;
@@ -409,6 +412,7 @@ int hulk_step_sharded_host(hulk_ctx *c, const uint8_t *bases, const uint64_t *of
 int hulk_step_sliced(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n, uint32_t max_read_len,
                      uint64_t bases_bytes, uint64_t reads_per_spectrum, uint32_t n_spectra) {
     if (!c) return HULK_ERR_ARG;
+    { const int rcs = snap_refuse(c, "hulk_step_sliced"); if (rcs != HULK_OK) return rcs; }
     if (c->comm.kind == 0) return fail(c, HULK_ERR_STATE, "hulk_step_sliced needs hulk_comm_init");
     if (n_spectra == 0 || n_spectra > c->T) return fail(c, HULK_ERR_ARG, "n_spectra");
     int rc = hulk_bin_reads_device_at(c, d_bases, d_offsets, n, max_read_len, bases_bytes, reads_per_spectrum, 0);

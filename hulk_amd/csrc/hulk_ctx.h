@@ -3,6 +3,7 @@
 //   hulk_tables.hip  count-min chain tables and the CWS parameter tables (newCWS, histosketch.go:95-126)
 //   hulk_flush.hip   orchestration of a batch: binning launches on the work stream(s), the spectrum rings, flushes on the
 //                    flush stream, host staging
+//   hulk_snapshot.hip  sketch snapshots: planning them into a flush, the ring, delivery (hulk_set_snapshots ...)
 //   hulk_comm.hip    multi-GPU: RCCL binding, host / loopback transports, hulk_step_sharded / hulk_step_sliced, gather
 // Host code only: every numeric step of the path runs in the kernels of hulk_minimizer / hulk_spectrum / hulk_countmin /
 // hulk_cws .hip; there is no CPU fallback.
@@ -60,6 +61,7 @@ struct hulk_ctx {
     bool pending_flush[2] = {false, false};
     int cur_ring = 0;
     struct PreparedFlush { bool armed = false; hulk::FlushBatch fb{}; int ring = 0;
+                           uint64_t snap_first = 0; uint32_t snap_n = 0;   // the snapshots this flush records (hulk_snapshot.hip)
                            bool use_dep = false;        // ev_binned was recorded on a caller's stream (hulk_flush_batch_after)
                            bool allreduce = false;      // hulk_step_sliced: the spectra are summed over the ranks first
     } deferred;   // a flush between its preparation (ev_binned recorded) and the queueing of its kernels
@@ -142,6 +144,23 @@ struct hulk_ctx {
     // hulk_add_reads_device only; h_off_chunk is that call's current piece.
     const uint64_t *h_off_hint = nullptr, *h_off_chunk = nullptr;
     uint64_t long_cap = 0, long_table_cap = 0;   // minimizer list of the short-read kernel (grow-only)
+    // hulk_set_snapshots: the sketch as it stands after a flushed spectrum, recorded by the flush kernels themselves into a device
+    // ring (hulk_snapshot.hip).  every == 0: the context records none, allocates none of this and launches what it always did.
+    struct Snapshots {
+        uint32_t every = 0, cap = 0;
+        unsigned long long *d_mins = nullptr; double *d_weights = nullptr;   // [cap][S]: entry of snapshot i is i % cap
+        uint64_t *h_mins = nullptr; double *h_weights = nullptr;             // pinned mirror of the ring (callback delivery)
+        std::vector<hulk_snapshot_info> info;                                // [cap]
+        uint64_t ordinal = 0;                                                // spectra flushed so far
+        uint64_t recorded = 0, delivered = 0;                                // snapshots planned into flushes / handed to fn
+        uint64_t reads_at_flush = 0, reads_at_snapshot = 0;                  // seq_count at the latest flush / recorded snapshot
+        hulk_snapshot_fn fn = nullptr; void *user = nullptr; bool fn_failed = false;
+        // callback delivery: the snapshots of one flush become deliverable together, when `ev` (recorded on the flush stream
+        // behind the flush kernels and the copies into the pinned mirror) has passed
+        struct Group { uint64_t first; uint32_t n; hipEvent_t ev; };
+        std::vector<Group> groups; size_t group_head = 0;                    // queued flushes whose snapshots are not delivered yet
+        std::vector<hipEvent_t> free_events;
+    } snap;
     // host-side run state
     uint64_t seq_count = 0, flush_index = 0;
     uint32_t T = 16, ring_n = 17, ring_base = 0;   // interval batch size and spectrum ring
@@ -192,7 +211,10 @@ int stage_mark_busy(hulk_ctx *c, hulk_ctx::HostStage &hs);
 int flush_kernels(hulk_ctx *c, hipStream_t s, uint32_t *hist, const FlushBatch &fb);
 bool no_overlap_mode(const hulk_ctx *c);
 hipStream_t flush_stream_of(hulk_ctx *c);
-int flush_batch(hulk_ctx *c, uint32_t count, hipStream_t dep_stream = nullptr, bool use_dep = false, bool allreduce = false);
+// what closed the spectra of a flush (for the snapshots' n_reads): an explicit hulk_flush, the interval rule, hulk_finish's EOF flush
+enum { FLUSH_EXPLICIT = 0, FLUSH_INTERVAL = 1, FLUSH_EOF = 2 };
+int flush_batch(hulk_ctx *c, uint32_t count, hipStream_t dep_stream = nullptr, bool use_dep = false, bool allreduce = false,
+                int closed_by = FLUSH_EXPLICIT);
 int check_device_error(hulk_ctx *c);
 int stage_host_reads(hulk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t i0, uint64_t i1,
                      hulk_ctx::HostStage **out);
@@ -206,6 +228,18 @@ struct ProfScope {
     explicit ProfScope(hulk_ctx *c);
     ~ProfScope();
 };
+
+// ---- hulk_snapshot.hip
+// the snapshot points among the `count` spectra of the flush being prepared: fills fb.snap_*, the infos, the ring bookkeeping;
+// with a callback, first delivers what the flush would overwrite (waiting for it: the one wait snapshots can cost a step)
+int snap_plan(hulk_ctx *c, FlushBatch &fb, uint32_t count, int closed_by, uint64_t *first, uint32_t *n);
+// behind the kernels of a flush that recorded snapshots [first, first + n): copies into the pinned mirror and the group's event
+int snap_flush_issued(hulk_ctx *c, hipStream_t s, uint64_t first, uint32_t n);
+// hands every snapshot whose flush has run to the callback (wait: all that are queued); no callback: nothing to do
+int snap_deliver(hulk_ctx *c, bool wait, uint32_t *delivered = nullptr);
+void snap_teardown(hulk_ctx *c);
+// the multi-rank entry points refuse a context that records snapshots
+int snap_refuse(hulk_ctx *c, const char *entry);
 
 // ---- hulk_comm.hip
 void comm_teardown(hulk_ctx *c);

@@ -3,6 +3,8 @@
 //   K4  k_cws_scan         fp32 pass over K = c*exp(b-r): per (interval, slot, tile) minimum, bound-pruned
 //       k_cws_resolve(+_drift)/k_cws_apply   exact fp64 re-evaluation with the literal formula of
 //                          src/histosketch/histosketch.go:30-33 and the slot update (histosketch.go:135-153)
+//       k_cws_apply_snap   ... of a context that records sketch snapshots (hulk_set_snapshots): the slot after every snapshot
+//                          point of the batch goes to the snapshot ring; k_cws_resolve_drift does the same with concept drift
 //       k_alfg_*/k_rng_candidates/k_cws_eval/k_cws_scatter/k_cws_beta/k_build_k32   the CWS tables (histosketch.go:95-126)
 //       k_smash            pairwise distances of `hulk smash`
 #include "hulk_device.h"
@@ -503,6 +505,36 @@ __global__ void k_cws_apply(const double *__restrict__ candA, const int32_t *__r
     weights[gs] = w; mins[gs] = m;
 }
 
+// Entry of the snapshot ring (hulk_set_snapshots) that spectrum t of the batch is recorded into; -1: t is no snapshot point.
+__device__ __forceinline__ int snap_entry(const FlushBatch &fb, int t) {
+    if (!((fb.snap_mask >> t) & 1u)) return -1;
+    return (int)((fb.snap_base + (uint32_t)__popc(fb.snap_mask & ((1u << t) - 1u))) % fb.snap_cap);
+}
+
+// k_cws_apply of a context that records snapshots (always the per-interval form): the running (m, w) of every snapshot
+// point t goes to the ring [snap_cap][sketch_size].  A batch k_flush_decide passed over (skip_exact) or an interval that did
+// not go leaves the sketch as it stands, and that is what its ring entries get — copies, without a look at the candidates.
+__global__ void k_cws_apply_snap(const double *__restrict__ candA, const int32_t *__restrict__ candB,
+                                 unsigned long long *__restrict__ mins, double *__restrict__ weights,
+                                 int slots, int slot_begin, const DevState *st, FlushBatch fb,
+                                 unsigned long long *__restrict__ snap_mins, double *__restrict__ snap_weights, uint32_t sketch_size) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= slots) return;
+    const bool skip = st->skip_exact[fb.parity] != 0u;
+    const int gs = slot_begin + slot;
+    double w = weights[gs]; unsigned long long m = mins[gs];
+    for (int t = 0; t < (int)fb.count; t++) {
+        if (!skip && flush_go(st, fb, t)) {
+            const double A = candA[(size_t)t * slots + slot];
+            const int32_t b = candB[(size_t)t * slots + slot];
+            if (b != 0x7fffffff && A < w) { w = A; m = (unsigned long long)b; }
+        }
+        const int e = snap_entry(fb, t);
+        if (e >= 0) { snap_mins[(size_t)e * sketch_size + gs] = m; snap_weights[(size_t)e * sketch_size + gs] = w; }
+    }
+    if (!skip) { weights[gs] = w; mins[gs] = m; }
+}
+
 // Minimum of a slot's tile minima per interval: slotmin[t][slot] = min over the wave tiles of tilemin[t][group][tile][row].
 // One coalesced pass over tilemin, so that k_cws_resolve_drift can pass over the (slot, interval) pairs that hold no
 // candidate without touching their rows (it used to stage every row — 8-float strides — behind two barriers per interval).
@@ -543,7 +575,9 @@ __global__ __launch_bounds__(256) void k_cws_resolve_drift(const double *__restr
                                                            int slot_begin, int ntiles, double decay_weight,
                                                            const float *__restrict__ slotmin,
                                                            const unsigned long long *__restrict__ scanmap, int wwords,
-                                                           const DevState *st, FlushBatch fb) {
+                                                           const DevState *st, FlushBatch fb,
+                                                           unsigned long long *__restrict__ snap_mins,
+                                                           double *__restrict__ snap_weights, uint32_t sketch_size) {
     extern __shared__ __align__(16) unsigned char smem[];
     float *tm = (float *)smem;                       // [wtiles]
     __shared__ int redi[4];
@@ -558,14 +592,20 @@ __global__ __launch_bounds__(256) void k_cws_resolve_drift(const double *__restr
     double w = weights[gs];
     unsigned long long wm = mins[gs];
     const uint32_t gomask = batch_gomask(st, fb);
+    // sketch snapshots (snap_mins != null): the slot as it stands at the end of interval t, whichever way the interval ends
+    // (w and wm are block-uniform; with snap_mask == 0 no interval is a snapshot point)
+    auto snapshot = [&](int t) {
+        const int e = snap_entry(fb, t);
+        if (e >= 0 && tid == 0) { snap_mins[(size_t)e * sketch_size + gs] = wm; snap_weights[(size_t)e * sketch_size + gs] = w; }
+    };
 
     for (int t = 0; t < (int)fb.count; t++) {
-        if (!((gomask >> t) & 1u)) continue;
+        if (!((gomask >> t) & 1u)) { snapshot(t); continue; }
         {   // no tile of this interval can hold a trigger for the current threshold (same screen as below): next interval
             const double thr0 = w / decay_weight;
-            if (thr0 != thr0) continue;
+            if (thr0 != thr0) { snapshot(t); continue; }
             const double lim0 = thr0 + 1e-5 * fabs(thr0) + 1e-37;
-            if (lim0 < INFINITY && !((double)slotmin[(size_t)t * ngroups * SCAN_ROWS + slot] <= lim0)) continue;   // block-uniform
+            if (lim0 < INFINITY && !((double)slotmin[(size_t)t * ngroups * SCAN_ROWS + slot] <= lim0)) { snapshot(t); continue; }   // block-uniform
         }
         __syncthreads();
         const float *tmin_t = tilemin + (((size_t)t * ngroups + slot / SCAN_ROWS) * wtiles) * SCAN_ROWS + (slot % SCAN_ROWS);
@@ -622,6 +662,7 @@ __global__ __launch_bounds__(256) void k_cws_resolve_drift(const double *__restr
             }
             from = first + 1;
         }
+        snapshot(t);
     }
     if (tid == 0) { weights[gs] = w; mins[gs] = wm; }
 }
@@ -1024,8 +1065,10 @@ hipError_t launch_cws_resolve(hipStream_t s, const double *d_rcb, const double *
                               const float *d_tilemin, double *d_candA, int32_t *d_candB,
                               unsigned long long *d_mins, double *d_weights,
                               int slots, int slot_begin, int ntiles, const unsigned long long *d_scanmap, DevState *st,
-                              const FlushBatch &fb) {
-    const int merged = scan_merge_off() ? 0 : 1;                 // (this launcher is the no-drift path)
+                              const FlushBatch &fb, unsigned long long *d_snap_mins, double *d_snap_weights, uint32_t sketch_size) {
+    // (this launcher is the no-drift path)  A context that records snapshots resolves per interval: the winner of a PREFIX of
+    // the batch can sit in a tile the merged resolve, which only looks inside the band of the batch-wide minimum, never opens
+    const int merged = (scan_merge_off() || d_snap_mins) ? 0 : 1;
     if (merged) {
         prof_mark(s, "k_cws_resolve");
         hipLaunchKernelGGL(k_cws_resolve<true>, dim3(slots, 1), dim3(256), (size_t)ntiles * 4 * sizeof(float), s,
@@ -1036,6 +1079,12 @@ hipError_t launch_cws_resolve(hipStream_t s, const double *d_rcb, const double *
         hipLaunchKernelGGL(k_cws_resolve<false>, dim3(slots, fb.count), dim3(256), (size_t)ntiles * 4 * sizeof(float), s,
                            d_rcb, d_f64, d_tilemin, d_candA, d_candB, slots, ntiles, d_scanmap, (ntiles * 4 + 63) / 64, st, fb);
     }
+    if (d_snap_mins) {
+        prof_mark(s, "k_cws_apply_snap");
+        hipLaunchKernelGGL(k_cws_apply_snap, dim3((slots + 255) / 256), dim3(256), 0, s, d_candA, d_candB, d_mins,
+                           d_weights, slots, slot_begin, st, fb, d_snap_mins, d_snap_weights, sketch_size);
+        return hipGetLastError();
+    }
     prof_mark(s, "k_cws_apply");
     hipLaunchKernelGGL(k_cws_apply, dim3((slots + 255) / 256), dim3(256), 0, s, d_candA, d_candB, d_mins,
                        d_weights, slots, slot_begin, st, fb, merged);
@@ -1045,7 +1094,8 @@ hipError_t launch_cws_resolve(hipStream_t s, const double *d_rcb, const double *
 hipError_t launch_cws_resolve_drift(hipStream_t s, const double *d_rcb, const double *d_f64,
                                     const float *d_tilemin, unsigned long long *d_mins, double *d_weights,
                                     int slots, int slot_begin, int ntiles, double decay_weight, float *d_slotmin,
-                                    const unsigned long long *d_scanmap, DevState *st, const FlushBatch &fb) {
+                                    const unsigned long long *d_scanmap, DevState *st, const FlushBatch &fb,
+                                    unsigned long long *d_snap_mins, double *d_snap_weights, uint32_t sketch_size) {
     const int ngroups = (slots + SCAN_ROWS - 1) / SCAN_ROWS, wwords = (ntiles * 4 + 63) / 64;
     prof_mark(s, "k_slot_tmin");
     hipLaunchKernelGGL(k_slot_tmin, dim3(ngroups, fb.count), dim3(256), 0, s, d_tilemin, d_slotmin, ntiles * 4, ngroups,
@@ -1053,7 +1103,7 @@ hipError_t launch_cws_resolve_drift(hipStream_t s, const double *d_rcb, const do
     prof_mark(s, "k_cws_resolve_drift");
     hipLaunchKernelGGL(k_cws_resolve_drift, dim3(slots), dim3(256), (size_t)ntiles * 4 * sizeof(float), s,
                        d_rcb, d_f64, d_tilemin, d_mins, d_weights, slots, slot_begin, ntiles, decay_weight, d_slotmin,
-                       d_scanmap, wwords, st, fb);
+                       d_scanmap, wwords, st, fb, d_snap_mins, d_snap_weights, sketch_size);
     return hipGetLastError();
 }
 

@@ -438,16 +438,18 @@ int flush_kernels(hulk_ctx *c, hipStream_t s, uint32_t *hist, const FlushBatch &
         HIPCHK(c, launch_cws_scan(s, c->d_k32, c->d_rcp32, c->d_tilemin, (int)c->slots, c->ntiles,
                                   c->row_stride, c->d_state, fb, c->prune ? c->d_kmin32 : nullptr, c->d_rext,
                                   c->d_weights, (int)c->slot_begin, c->d_visited, c->drift ? c->decay_weight : 0.0, c->d_scanmap,
-                                  c->drift /* per-interval minima: the drift resolve replays the stream in order */, c->d_rmm,
+                                  c->drift || c->snap.every /* per-interval minima: the drift resolve replays the stream in order, a snapshot is the sketch after a PREFIX of the batch */, c->d_rmm,
                                   c->d_scanlist, c->d_scanlist_n, pr.a, pr.b));     // (the brackets: around the scan kernel itself)
         c->scan_tiles_total += (uint64_t)((c->slots + SCAN_ROWS - 1) / SCAN_ROWS) * (uint64_t)c->ntiles * 4u;
         if ((c->profiling & 1)) c->prof.push_back(pr);
         if (c->drift)
             HIPCHK(c, launch_cws_resolve_drift(s, c->d_rcb, c->d_f64, c->d_tilemin, c->d_mins, c->d_weights, (int)c->slots,
-                                               (int)c->slot_begin, c->ntiles, c->decay_weight, c->d_slotmin, c->d_scanmap, c->d_state, fb));
+                                               (int)c->slot_begin, c->ntiles, c->decay_weight, c->d_slotmin, c->d_scanmap, c->d_state, fb,
+                                               c->snap.d_mins, c->snap.d_weights, c->S));
         else
         HIPCHK(c, launch_cws_resolve(s, c->d_rcb, c->d_f64, c->d_tilemin, c->d_candA, c->d_candB, c->d_mins, c->d_weights,
-                                     (int)c->slots, (int)c->slot_begin, c->ntiles, c->d_scanmap, c->d_state, fb));
+                                     (int)c->slots, (int)c->slot_begin, c->ntiles, c->d_scanmap, c->d_state, fb,
+                                     c->snap.d_mins, c->snap.d_weights, c->S));
     }
     return HULK_OK;
 }
@@ -473,13 +475,14 @@ int issue_flush(hulk_ctx *c, hipEvent_t gate) {
         if (rc != HULK_OK) return rc;
     }
     { const int rc = flush_kernels(c, s, hist, fb); if (rc != HULK_OK) return rc; }
+    if (c->deferred.snap_n) { const int rc = snap_flush_issued(c, s, c->deferred.snap_first, c->deferred.snap_n); if (rc != HULK_OK) return rc; }
     HIPCHK(c, hipEventRecord(c->ev_flushed[ring], s));
     c->pending_flush[ring] = true;
     return HULK_OK;
 }
 
 // Flush `count` consecutive spectra of the ring (starting at ring_base) through count-min + CWS.
-int flush_batch(hulk_ctx *c, uint32_t count, hipStream_t dep_stream, bool use_dep, bool allreduce) {
+int flush_batch(hulk_ctx *c, uint32_t count, hipStream_t dep_stream, bool use_dep, bool allreduce, int closed_by) {
     { const int rcf = fatal_status(c); if (rcf != HULK_OK) return rcf; }
     if (count == 0) return HULK_OK;
     int rc = ensure_tables(c);
@@ -489,10 +492,13 @@ int flush_batch(hulk_ctx *c, uint32_t count, hipStream_t dep_stream, bool use_de
     FlushBatch fb{};
     fb.ring_base = c->ring_base; fb.ring_n = c->ring_n; fb.count = count;
     fb.parity = (int)(c->flush_index & 1); fb.num_bins = c->B;
+    uint64_t snap_first = 0; uint32_t snap_n = 0;
+    if (c->snap.every) { rc = snap_plan(c, fb, count, closed_by, &snap_first, &snap_n); if (rc != HULK_OK) return rc; }
     // everything binned so far (or the caller's all-reduce on dep_stream) ends where this event is recorded
     HIPCHK(c, hipEventRecord(c->ev_binned, use_dep ? dep_stream : ring_stream(c)));
     c->deferred.armed = true; c->deferred.fb = fb; c->deferred.ring = c->cur_ring;
     c->deferred.use_dep = use_dep; c->deferred.allreduce = allreduce;
+    c->deferred.snap_first = snap_first; c->deferred.snap_n = snap_n;
     c->flush_index++;
     // Queued at once.  (Holding the flush back until the NEXT batch's minimizer kernel had run — so that its LDS-heavy
     // count-min kernels would meet k_jump_bin, which needs no LDS, instead of k_minimizer_fast — was measured: C3-shaped

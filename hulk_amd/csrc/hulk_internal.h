@@ -40,6 +40,9 @@ struct FlushBatch {
     int parity;
     int32_t num_bins;
     int prio = 0;       // wave priority (s_setprio) the latency-bound count-min replay kernels raise themselves to
+    // sketch snapshots (hulk_set_snapshots; all 0 without): bit t of snap_mask = the sketch as it stands after spectrum t of the
+    // batch goes to the snapshot ring, the n-th set bit into entry (snap_base + n) % snap_cap — host knowledge, by value
+    uint32_t snap_mask = 0, snap_base = 0, snap_cap = 0;
 };
 
 // Minimizer list written by k_minimizer_fast: one region of `rcap` entries per wave (16 reads).
@@ -170,14 +173,17 @@ hipError_t launch_cws_resolve(hipStream_t s, const double *d_rcb, const double *
                               const float *d_tilemin, double *d_candA, int32_t *d_candB,
                               unsigned long long *d_mins, double *d_weights,
                               int slots, int slot_begin, int ntiles, const unsigned long long *d_scanmap, DevState *st,
-                              const FlushBatch &fb);
+                              const FlushBatch &fb, unsigned long long *d_snap_mins = nullptr, double *d_snap_weights = nullptr,
+                              uint32_t sketch_size = 0);
 hipError_t launch_elem_index(hipStream_t s, const uint32_t *d_hists, uint32_t *d_blkcnt, uint32_t *d_eidx,
                              uint32_t *d_etot, const FlushBatch &fb, DevState *st);
 int elem_index_blocks(int32_t num_bins);
 hipError_t launch_cws_resolve_drift(hipStream_t s, const double *d_rcb, const double *d_f64,
                                     const float *d_tilemin, unsigned long long *d_mins, double *d_weights,
                                     int slots, int slot_begin, int ntiles, double decay_weight, float *d_slotmin,
-                                    const unsigned long long *d_scanmap, DevState *st, const FlushBatch &fb);
+                                    const unsigned long long *d_scanmap, DevState *st, const FlushBatch &fb,
+                                    unsigned long long *d_snap_mins = nullptr, double *d_snap_weights = nullptr,
+                                    uint32_t sketch_size = 0);
 hipError_t launch_cws_chunk(hipStream_t s, const uint64_t *d_pairs, uint64_t n_attempts, double *d_val,
                             uint32_t *d_blkcnt, unsigned long long *d_gamma_total, unsigned long long *d_chunk_base,
                             double *d_rcb, uint64_t num_bins, uint64_t slot_begin, uint64_t slots,

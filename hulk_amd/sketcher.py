@@ -45,8 +45,10 @@ class GpuSketcher:
 
     def __init__(self, k=21, w=9, sketch_size=50, interval=0, decay_ratio=1.0, num_bins=0,
                  device=0, slot_begin=0, slot_count=0, cws_source=_lib.HULK_CWS_GO_COMPAT,
-                 stream=None, flags=0, batch=0, work_lanes=0, host_copy_threads=0):
-        """batch: sketching intervals per flush batch (0 = the library's default, 16); work_lanes: 2 (the default) = consecutive
+                 stream=None, flags=0, batch=0, work_lanes=0, host_copy_threads=0, snapshots=0, snapshot_capacity=0):
+        """snapshots: N >= 1 records the sketch after every N-th flushed spectrum inside the batched flush (hulk_set_snapshots;
+        0 = off), snapshot_capacity: snapshots the device ring holds (0 = the library's default) — see snapshots() / on_snapshot().
+        batch: sketching intervals per flush batch (0 = the library's default, 16); work_lanes: 2 (the default) = consecutive
         batches are binned on two alternating work streams, 1 = one; host_copy_threads: see hulk_params (include/hulk_hip.h).
         stream: run on the caller's hipStream_t — the context then joins its second lane into that stream after every call."""
         self._L = _lib.load()
@@ -66,6 +68,14 @@ class GpuSketcher:
         self.slot_count = slot_count if slot_count else sketch_size
         if stream is not None:
             self.set_stream(stream)
+        self._snapshot_thunk = None
+        self._snapshot_error = None
+        if snapshots:
+            try:
+                self._chk(self._L.hulk_set_snapshots(self._ctx, snapshots, snapshot_capacity))
+            except HulkError:
+                self.close()
+                raise
 
     # ---- lifetime
     def close(self):
@@ -84,7 +94,55 @@ class GpuSketcher:
 
     def _chk(self, rc):
         if rc != 0:
-            raise HulkError(rc, self._L.hulk_last_error(self._ctx).decode())
+            err = HulkError(rc, self._L.hulk_last_error(self._ctx).decode())
+            cause, self._snapshot_error = getattr(self, "_snapshot_error", None), None
+            if cause is not None:                                  # the on_snapshot callable raised: that is why the run ended
+                raise err from cause
+            raise err
+
+    # ---- sketch snapshots (hulk_set_snapshots: the `snapshots=` argument)
+    def snapshot_count(self):
+        """(snapshots recorded so far, index of the oldest one the ring still holds) — host knowledge, no synchronisation."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.hulk_snapshot_count(self._ctx, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
+    def snapshots(self, first=0, n=None):
+        """Snapshots [first, first + n) in stream order (n=None: all recorded from `first` on; synchronises):
+        (info: list of {"ordinal", "n_reads"}, mins uint64[n][sketch_size], weights float64[n][sketch_size])."""
+        if n is None:
+            n = max(self.snapshot_count()[0] - first, 0)
+        info = (_lib.SnapshotInfo * max(n, 1))()
+        mins = np.zeros((n, self.sketch_size), dtype=np.uint64)
+        weights = np.zeros((n, self.sketch_size), dtype=np.float64)
+        self._chk(self._L.hulk_get_snapshots(self._ctx, first, n, ctypes.addressof(info), mins.ctypes.data, weights.ctypes.data))
+        return [{"ordinal": int(info[i].ordinal), "n_reads": int(info[i].n_reads)} for i in range(n)], mins, weights
+
+    def on_snapshot(self, fn):
+        """Deliver every snapshot to fn(info: dict, mins: np.uint64[sketch_size], weights: np.float64[sketch_size]) — copies —
+        in stream order, exactly once, from inside add_reads* / sketch_files / flush / poll_snapshots / finish, as soon as
+        its flush is found complete; nothing on the step path waits for it.  Set before the first read.  An exception in fn
+        (or a true return value) ends the run with HulkError."""
+        S = self.sketch_size
+
+        def thunk(_user, info, mins, weights, sketch_size):
+            try:
+                i = {"ordinal": int(info.contents.ordinal), "n_reads": int(info.contents.n_reads)}
+                m = np.ctypeslib.as_array(mins, shape=(S,)).copy()
+                w = np.ctypeslib.as_array(weights, shape=(S,)).copy()
+                return 1 if fn(i, m, w) else 0
+            except Exception as e:  # noqa: BLE001 — reported through the ABI's status code, chained to the HulkError
+                self._snapshot_error = e
+                return 1
+        thunk_c = _lib.SNAPSHOT_FN(thunk)
+        self._chk(self._L.hulk_set_snapshot_callback(self._ctx, thunk_c, None))
+        self._snapshot_thunk = thunk_c                             # keep the callback alive as long as the context
+
+    def poll_snapshots(self):
+        """Deliver the snapshots of every flush that has run to the on_snapshot callable; never blocks.  Returns how many."""
+        n = ctypes.c_uint32()
+        self._chk(self._L.hulk_poll_snapshots(self._ctx, ctypes.byref(n)))
+        return int(n.value)
 
     def set_stream(self, stream_handle):
         """Run on the caller's hipStream_t (0/None = the HIP null stream, torch's default)."""

@@ -11,6 +11,8 @@
 //   log.Fatalf("ERROR---> %v") via helpers.ErrorCheck   helpers.go:31-35  hulk::Error (what() = %v)
 //   SeqMinimizer.Run's loop with the read stream sharded over GPUs        hulk::Boss::Shard + AddSeq + StopWorkSharded
 //       pipeline/sketch.go:182-250                                          (RCCL inside libhulkhip.so)
+//   `--stream`: "prints the sketches ... after every interval"            hulk::Boss::EnableSnapshots / CollectSnapshots /
+//       cmd/sketch.go:56 (promised, read nowhere in src/pipeline)           OnSnapshot (recorded inside the batched flush)
 //
 // Header only; link with -lhulkhip.  A Boss is single-caller, like SeqMinimizer.Run's goroutine.
 #ifndef HULK_HPP
@@ -19,6 +21,9 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <exception>
+#include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -62,6 +67,9 @@ struct HistoSketch {
     bool ApplyConceptDrift = false;        // `concept_drift` (decayRatio != 1.0, histosketch.go:79-81)
 };
 
+// the histosketch as it stood after flushed spectrum `Ordinal` (1-based), `Reads` reads into the stream
+struct Snapshot { uint64_t Ordinal = 0, Reads = 0; HistoSketch Sketch; };
+
 struct IngestStats { uint64_t SeqCount = 0, LengthTotal = 0, Lines = 0, BytesIn = 0; double Seconds = 0; };
 
 class Boss {
@@ -70,7 +78,7 @@ class Boss {
     static Boss FindMinimizers(const SketchInfo &info) { return Boss(info); }
 
     Boss(Boss &&o) noexcept : ctx_(o.ctx_), info_(o.info_), bins_(o.bins_), sharded_(o.sharded_), bases_(std::move(o.bases_)),
-                              offsets_(std::move(o.offsets_)) { o.ctx_ = nullptr; }
+                              offsets_(std::move(o.offsets_)), snap_(std::move(o.snap_)) { o.ctx_ = nullptr; }
     Boss(const Boss &) = delete;
     Boss &operator=(const Boss &) = delete;
     ~Boss() { if (ctx_) hulk_destroy(ctx_); }
@@ -154,6 +162,36 @@ class Boss {
     void MergeKMVsketch(const std::vector<uint64_t> &mins) { push(); check(hulk_minhash_merge(ctx_, HULK_MINHASH_KMV, mins.data(), (uint32_t)mins.size())); }
     void MergeKHFsketch(const std::vector<uint64_t> &mins) { push(); check(hulk_minhash_merge(ctx_, HULK_MINHASH_KHF, mins.data(), (uint32_t)mins.size())); }
 
+    // ---- sketch snapshots (hulk_set_snapshots): the sketch after every `every`-th flushed spectrum, recorded on the GPU inside
+    // the batched flush — what batch = 1 and Sketch() after every interval would give, without giving up the batch.  Call before
+    // the first AddSeq; capacity = snapshots the device ring holds (0 = the library's default).  Not with Shard().
+    void EnableSnapshots(uint32_t every, uint32_t capacity = 0) { check(hulk_set_snapshots(ctx_, every, capacity)); }
+    // every snapshot the ring still holds, in stream order (synchronises, like Sketch())
+    std::vector<Snapshot> CollectSnapshots() {
+        push();
+        uint64_t recorded = 0, first = 0;
+        check(hulk_snapshot_count(ctx_, &recorded, &first));
+        const uint32_t n = (uint32_t)(recorded - first), S = info_.SketchSize;
+        std::vector<hulk_snapshot_info> inf(n ? n : 1);
+        std::vector<uint64_t> mins((size_t)n * S + 1);
+        std::vector<double> weights((size_t)n * S + 1);
+        check(hulk_get_snapshots(ctx_, first, n, inf.data(), mins.data(), weights.data()));
+        std::vector<Snapshot> out(n);
+        for (uint32_t i = 0; i < n; i++) fill(out[i], inf[i], mins.data() + (size_t)i * S, weights.data() + (size_t)i * S);
+        return out;
+    }
+    // fn gets every snapshot once, in stream order, on the caller's thread, from inside AddSeq / Flush / SketchFiles / PollSnapshots /
+    // StopWork as soon as the flush that recorded it is found complete (nothing on the step path waits for it).  An exception thrown
+    // by fn ends the run: it is rethrown from the call that delivered the snapshot.  After EnableSnapshots, before the first AddSeq.
+    void OnSnapshot(std::function<void(const Snapshot &)> fn) {
+        auto st = std::make_unique<SnapState>();
+        st->fn = std::move(fn); st->owner_info = info_; st->bins = bins_;
+        check(hulk_set_snapshot_callback(ctx_, &Boss::snap_thunk, st.get()));
+        snap_ = std::move(st);
+    }
+    // hands the snapshots of every flush that has run to the OnSnapshot function; never blocks; returns how many
+    uint32_t PollSnapshots() { uint32_t n = 0; check(hulk_poll_snapshots(ctx_, &n)); return n; }
+
     hulk_ctx *handle() { return ctx_; }
 
  private:
@@ -186,7 +224,23 @@ class Boss {
         bases_.clear(); offsets_.assign(1, 0);
         check(rc);
     }
-    void check(int rc) { if (rc != HULK_OK) throw Error(rc, hulk_last_error(ctx_)); }
+    void check(int rc) {
+        if (snap_ && snap_->thrown) { std::exception_ptr e = snap_->thrown; snap_->thrown = nullptr; std::rethrow_exception(e); }
+        if (rc != HULK_OK) throw Error(rc, hulk_last_error(ctx_));
+    }
+    struct SnapState { std::function<void(const Snapshot &)> fn; SketchInfo owner_info; int32_t bins = 0; std::exception_ptr thrown; };
+    static void fill(Snapshot &s, const SketchInfo &info, int32_t bins, const hulk_snapshot_info &inf, const uint64_t *mins, const double *weights) {
+        s.Ordinal = inf.ordinal; s.Reads = inf.n_reads;
+        s.Sketch.KmerSize = info.KmerSize; s.Sketch.SketchSize = info.SketchSize; s.Sketch.Dimensions = bins;
+        s.Sketch.ApplyConceptDrift = info.DecayRatio != 1.0;
+        s.Sketch.Sketch.assign(mins, mins + info.SketchSize); s.Sketch.SketchWeights.assign(weights, weights + info.SketchSize);
+    }
+    void fill(Snapshot &s, const hulk_snapshot_info &inf, const uint64_t *mins, const double *weights) { fill(s, info_, bins_, inf, mins, weights); }
+    static int snap_thunk(void *user, const hulk_snapshot_info *inf, const uint64_t *mins, const double *weights, uint32_t) {
+        SnapState *st = static_cast<SnapState *>(user);
+        try { Snapshot s; fill(s, st->owner_info, st->bins, *inf, mins, weights); st->fn(s); return 0; }
+        catch (...) { st->thrown = std::current_exception(); return 1; }             // (no exception crosses the C ABI)
+    }
     std::vector<uint64_t> collect(int algo) {
         push();
         std::vector<uint64_t> mins(info_.SketchSize ? info_.SketchSize : 1);
@@ -202,6 +256,7 @@ class Boss {
     bool sharded_ = false;
     std::vector<uint8_t> bases_;
     std::vector<uint64_t> offsets_;
+    std::unique_ptr<SnapState> snap_;      // OnSnapshot: lives on the heap, the library holds its address
 };
 
 // sketchio's pairwise distances over loaded sketches (cmd/smash.go:183-226): distances[s*N+q]

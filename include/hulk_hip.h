@@ -64,6 +64,8 @@ extern "C" {
  * 4: HULK_FLAG_CMS_CHAIN + hulk_get_device_checks (the count-min replay's hardware assumption is verified on the device by
  *    hulk_create), hulk_get_profile_table (hulk_set_profiling bit 32), hulk_load_sketches / hulk_smash_files (the directory form
  *    of `hulk smash`); the test hooks hulk_debug_inject / hulk_debug_read left the shipping library (profiling build only).
+ *    Additions since (no existing entry point changed): HULK_FLAG_KMV / HULK_FLAG_KHF with hulk_get_minhash / hulk_minhash_merge;
+ *    sketch snapshots (hulk_set_snapshots, hulk_snapshot_count, hulk_get_snapshots, hulk_set_snapshot_callback, hulk_poll_snapshots).
  * Bindings compare it with the value they were written for. */
 #define HULK_ABI_VERSION 4
 
@@ -424,6 +426,47 @@ int hulk_get_minhash(hulk_ctx *ctx, int algo, uint64_t *mins, uint32_t *n, uint6
 /* MinHash.Merge: fold a signature of the same kind (host array, n entries; KHF needs n == sketch_size, else HULK_ERR_ARG) into the
  * context's: KHF slot-wise minimum (khf.go:49-55), KMV the sketch_size smallest of the two multisets together. */
 int hulk_minhash_merge(hulk_ctx *ctx, int algo, const uint64_t *mins, uint32_t n);
+
+/* ---- sketch snapshots: the histosketch after every flushed spectrum, recorded inside the batched flush ---------------------------
+ * `hulk sketch --stream` promises "the sketches after every interval" (cmd/sketch.go:56); src/pipeline never reads the flag.  A
+ * context with snapshots on records the pair mins[sketch_size] / weights[sketch_size] exactly as hulk_get_sketch would return it
+ * right after one flushed spectrum was applied (slots the context does not own: 0 / MaxFloat64) — bit for bit what batch = 1 with
+ * hulk_get_sketch after every interval gives, but from inside the batch: the flush kernels walk those states anyway and store
+ * them into a device ring of `capacity` snapshots.  Without concept drift such a context scans and resolves per interval (the
+ * merged scan keeps one minimum per batch, and the winner of a PREFIX of the batch may sit elsewhere): the first, unpruned
+ * batches of a stream pay for that, the steady state (k_flush_decide passes the batch over) costs one small copy kernel per batch.
+ * Off by default; a context that never calls hulk_set_snapshots allocates nothing for it and launches what it always did.
+ * Not available on the multi-rank paths: on a context with snapshots hulk_bin_reads_device*, hulk_flush_batch*, hulk_comm_init*
+ * and hulk_step_* return HULK_ERR_STATE (a delta step of hulk_step_sharded does not run the flush kernels at all). */
+typedef struct hulk_snapshot_info {
+    uint64_t ordinal;   /* 1-based number of the flushed spectrum (interval rule, hulk_flush and hulk_finish's last one alike) */
+    uint64_t n_reads;   /* reads of the stream when that spectrum closed */
+} hulk_snapshot_info;
+/* Before the first read / flush (HULK_ERR_STATE afterwards).  every >= 1: a snapshot after each flushed spectrum whose ordinal is a
+ * multiple of `every`; every == 0: off.  hulk_finish's last flush is recorded whatever its ordinal if reads arrived since the last
+ * recorded snapshot, and not otherwise (a stream that ends on a recorded interval boundary gets no duplicate); it takes a new
+ * ordinal only if reads arrived since the last flush (the empty spectrum behind an interval boundary is not counted).
+ * capacity: snapshots the ring holds, 0 = default (64); device and pinned host memory of capacity * sketch_size * 16 bytes each are
+ * allocated here, none on the step path.  A flush never records more snapshots than the ring holds: the batch (hulk_batch_size)
+ * becomes min(batch, capacity * every) intervals. */
+int hulk_set_snapshots(hulk_ctx *ctx, uint32_t every, uint32_t capacity);
+/* Host knowledge, no synchronisation: snapshots recorded so far (queued with their flushes), index of the oldest one still held
+ * (recorded - capacity once the ring has wrapped).  Either pointer may be NULL. */
+int hulk_snapshot_count(hulk_ctx *ctx, uint64_t *recorded, uint64_t *first_held);
+/* Synchronises like the other getters.  Copies snapshots [first, first + n) (0-based, in stream order): info[n], mins[n][sketch_size],
+ * weights[n][sketch_size] (any of them may be NULL).  A snapshot the ring has dropped or that is not recorded yet: HULK_ERR_ARG. */
+int hulk_get_snapshots(hulk_ctx *ctx, uint64_t first, uint32_t n, hulk_snapshot_info *info, uint64_t *mins, double *weights);
+/* Delivery without a synchronisation.  fn is called on the caller's thread, in stream order, exactly once per snapshot, from inside
+ * hulk_add_reads*, hulk_sketch_files* (between blocks), hulk_flush, hulk_poll_snapshots and hulk_finish, for every recorded snapshot
+ * whose flush is found complete (event query, no wait); hulk_finish delivers all that remain.  mins / weights point into the library's
+ * pinned staging and are valid during the call only.  With a callback an undelivered snapshot is never overwritten: before a flush
+ * that would do so is queued the library waits for the pending ones and delivers them (without a callback the oldest are dropped).
+ * A non-zero return of fn ends the run: that call and every later one return HULK_ERR_STATE, "snapshot callback failed".
+ * Set it after hulk_set_snapshots and before the first read (HULK_ERR_STATE otherwise). */
+typedef int (*hulk_snapshot_fn)(void *user, const hulk_snapshot_info *info, const uint64_t *mins, const double *weights, uint32_t sketch_size);
+int hulk_set_snapshot_callback(hulk_ctx *ctx, hulk_snapshot_fn fn, void *user);
+/* Hands the snapshots of every flush that has run to the callback; never blocks.  *delivered (may be NULL): how many. */
+int hulk_poll_snapshots(hulk_ctx *ctx, uint32_t *delivered);
 
 /* Count-min counters as fp64 [7][2000] (test hook). */
 int hulk_get_cms(hulk_ctx *ctx, double *counters);

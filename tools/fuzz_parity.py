@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Randomised differential test: libhulkhip (GPU) vs the CPU oracle over random parameters and inputs.
-usage: fuzz_parity.py [n_cases] [seed]     (run on the GPU box; prints every mismatch and a summary)"""
+usage: fuzz_parity.py [n_cases] [seed]     (run on the GPU box; prints every mismatch and a summary)
+FUZZ_SNAPSHOTS=1: the GPU context records a sketch snapshot after every flushed spectrum (GpuSketcher(snapshots=1)) and every
+one of them is compared with the oracle fed the same reads one interval at a time; the draws of a seed do not change."""
 import os
 import sys
 import time
@@ -108,7 +110,10 @@ for case in range(n_cases):
         rng.integers(0, len(seqs) + 1, size=3)
         o.close()
         continue
-    g = hulk_amd.GpuSketcher(k, w, S, interval, decay, batch=batch, work_lanes=lanes)
+    snap = bool(os.environ.get("FUZZ_SNAPSHOTS"))
+    n_spectra = (len(seqs) + interval - 1) // interval if interval else 1
+    g = hulk_amd.GpuSketcher(k, w, S, interval, decay, batch=batch, work_lanes=lanes,
+                             **(dict(snapshots=1, snapshot_capacity=n_spectra + 1) if snap else {}))
     try:
         cuts = sorted(set([0, len(seqs)] + [int(x) for x in rng.integers(0, len(seqs) + 1, size=3)]))
         for x, y in zip(cuts[:-1], cuts[1:]):
@@ -131,6 +136,25 @@ for case in range(n_cases):
             ok = False; why = "weights differ: max rel %.3g" % float(np.max(np.abs(gw - ow) / np.abs(ow)))
         elif o.counters()["n_minimizers"] != g.counters()["n_minimizers"]:
             ok = False; why = "minimizer counts differ"
+        elif snap:
+            # the trajectory: a second oracle, fed one spectrum's reads at a time (the last one may be ragged: the EOF flush)
+            info, sm, sw = g.snapshots()
+            step = interval if interval else len(seqs)
+            want_reads = [min((t + 1) * step, len(seqs)) for t in range(n_spectra)]
+            if [x["n_reads"] for x in info] != want_reads or [x["ordinal"] for x in info] != list(range(1, n_spectra + 1)):
+                ok = False; why = f"snapshots recorded at {[(x['ordinal'], x['n_reads']) for x in info][:6]}..., expected reads {want_reads[:6]}..."
+            else:
+                o2 = pyorc.Sketcher(k, w, S, 0, decay, interval)
+                for t in range(n_spectra):
+                    o2.add_reads(bases, offsets[t * step:want_reads[t] + 1])
+                    if t == n_spectra - 1:
+                        o2.finish()
+                    tm, tw = o2.sketch()
+                    if not np.array_equal(tm, sm[t]):
+                        ok = False; why = f"snapshot {t + 1} of {n_spectra}: {int((tm != sm[t]).sum())} of {S} mins differ"; break
+                    if not np.allclose(sw[t], tw, rtol=1e-7 if decay != 1.0 else 1e-9, atol=0):
+                        ok = False; why = f"snapshot {t + 1} of {n_spectra}: weights differ"; break
+                o2.close()
     if oerr is not None:
         n_err += 1; errs[oerr] = errs.get(oerr, 0) + 1
     if not ok:
