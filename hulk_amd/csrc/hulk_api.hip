@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cfloat>
 
 using namespace hulk;
 
@@ -313,6 +314,18 @@ int hulk_set_private_stream(hulk_ctx *c) {
 int hulk_set_cws_tables(hulk_ctx *c, const double *r, const double *cc, const double *b) {
     if (!c || !r || !cc || !b) return fail(c, HULK_ERR_ARG, "NULL table");
     if (c->seq_count || c->flush_index) return fail(c, HULK_ERR_STATE, "tables must be set before the first read");
+    // the fp32 screen of the flush works on K = c * exp(b - r) rounded to fp32: it orders tiles by K / f and cannot do that
+    // with +-Inf or NaN (a slot whose row held one would silently keep its old content).  newCWS never draws such a value
+    // (b < r, so |K| < |c|); tables from outside are checked here, over the rows this context owns.
+    const size_t B = (size_t)c->B;
+    for (uint32_t s = 0; s < c->slots; s++) {
+        const size_t at = (size_t)(c->slot_begin + s) * B;
+        for (size_t j = 0; j < B; j++) {
+            const double K = cc[at + j] * std::exp(b[at + j] - r[at + j]);
+            if (!(std::fabs(K) <= (double)FLT_MAX))
+                return fail(c, HULK_ERR_ARG, "c * exp(b - r) is not finite in fp32");
+        }
+    }
     return install_tables(c, r, cc, b);
 }
 

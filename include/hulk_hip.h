@@ -180,7 +180,11 @@ int hulk_set_stream(hulk_ctx *ctx, void *hip_stream);
 int hulk_set_private_stream(hulk_ctx *ctx);
 
 /* Supply r, c, b ([sketch_size][num_bins] row-major fp64, full matrices, host memory) when
- * cws_source == HULK_CWS_EXTERNAL.  Must be called before the first read. */
+ * cws_source == HULK_CWS_EXTERNAL.  Must be called before the first read.
+ * Domain: K = c * exp(b - r) must be finite in fp32 (|K| <= FLT_MAX, no NaN) for every entry of the rows the context
+ * owns — the flush screens candidates with K in fp32; HULK_ERR_ARG otherwise.  newCWS's own tables have |K| < |c|.
+ * The check is one exp per entry on the host, single-threaded: sketch_size * num_bins of them, i.e. seconds at
+ * sketch_size 1024 and k = 31 (1e9 entries), next to the upload of the same 24 GB. */
 int hulk_set_cws_tables(hulk_ctx *ctx, const double *r, const double *c, const double *b);
 
 /* AddSeq for a batch.  Read i is bases[offsets[i] .. offsets[i+1]) (ASCII, any case).

@@ -354,12 +354,17 @@ typedef struct orc_sketcher {
     /* counters (pipeline/sketch.go:186-208, boss.go:93) */
     uint64_t seqCount, lengthTotal, minimizerCounter, flushes, elements;
     uint64_t *scratch; int32_t scratch_cap;
+    /* test aid: the AddElement stream as (flush ordinal, bin, estiFreq) — orc_trace_enable */
+    int trace_on;
+    uint64_t trace_n, trace_cap;
+    uint32_t *trace_flush; int32_t *trace_bin; double *trace_f;
 } orc_sketcher;
 
 void orc_free(orc_sketcher *o) {
     if (!o) return;
     free(o->bins); free(o->sketch); free(o->weights);
     free(o->r); free(o->c); free(o->b); free(o->cms.ctr); free(o->scratch);
+    free(o->trace_flush); free(o->trace_bin); free(o->trace_f);
     free(o);
 }
 
@@ -400,9 +405,43 @@ static inline double cws_sample(const orc_sketcher *o, uint64_t i, uint32_t j, d
     return o->c[at] / (Yka * exp(o->r[at]));
 }
 
+/* test aid (no counterpart in the reference): every AddElement call leaves (flushes done before it, bin, estiFreq).
+ * estiFreq does not depend on the CWS tables, so a test can read it first and choose tables afterwards. */
+static void trace_push(orc_sketcher *o, uint64_t bin, double f) {
+    if (o->trace_n == o->trace_cap) {
+        uint64_t cap = o->trace_cap ? o->trace_cap * 2 : 1 << 16;
+        uint32_t *nf = (uint32_t *)realloc(o->trace_flush, cap * sizeof *nf);
+        if (nf) o->trace_flush = nf;
+        int32_t *nb = (int32_t *)realloc(o->trace_bin, cap * sizeof *nb);
+        if (nb) o->trace_bin = nb;
+        double *nv = (double *)realloc(o->trace_f, cap * sizeof *nv);
+        if (nv) o->trace_f = nv;
+        if (!nf || !nb || !nv) { o->trace_on = -1; return; }    /* orc_trace_len reports the failure */
+        o->trace_cap = cap;
+    }
+    o->trace_flush[o->trace_n] = (uint32_t)o->flushes;
+    o->trace_bin[o->trace_n] = (int32_t)bin;
+    o->trace_f[o->trace_n] = f;
+    o->trace_n++;
+}
+void orc_trace_enable(orc_sketcher *o, int on) { if (o->trace_on >= 0) o->trace_on = on ? 1 : 0; }
+/* records so far, or -1 if the trace ran out of memory */
+int64_t orc_trace_len(const orc_sketcher *o) { return o->trace_on < 0 ? -1 : (int64_t)o->trace_n; }
+void orc_trace_get(const orc_sketcher *o, uint32_t *flush, int32_t *bin, double *f) {
+    memcpy(flush, o->trace_flush, o->trace_n * sizeof *flush);
+    memcpy(bin, o->trace_bin, o->trace_n * sizeof *bin);
+    memcpy(f, o->trace_f, o->trace_n * sizeof *f);
+}
+/* test aid: replace the tables of newCWS by the caller's ([slot][bin] row-major, like orc_cws_r/c/b) */
+void orc_set_cws_tables(orc_sketcher *o, const double *r, const double *c, const double *b) {
+    size_t n = (size_t)o->S * (size_t)o->B;
+    memcpy(o->r, r, n * sizeof(double)); memcpy(o->c, c, n * sizeof(double)); memcpy(o->b, b, n * sizeof(double));
+}
+
 /* HistoSketch.AddElement — histosketch.go:129-155 */
 void orc_add_element(orc_sketcher *o, uint64_t bin, double value) {
     double estiFreq = cms_add(&o->cms, bin, value);
+    if (o->trace_on > 0) trace_push(o, bin, estiFreq);
     for (uint32_t slot = 0; slot < o->S; slot++) {
         double Aka = cws_sample(o, bin, slot, estiFreq);
         double curMin;

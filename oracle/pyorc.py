@@ -73,6 +73,10 @@ def lib():
         L.orc_get_counters.argtypes = [vp] * 6
         for n in ("orc_cws_r", "orc_cws_c", "orc_cws_b"):
             getattr(L, n).restype = ctypes.POINTER(ctypes.c_double); getattr(L, n).argtypes = [vp]
+        L.orc_set_cws_tables.argtypes = [vp, vp, vp, vp]
+        L.orc_trace_enable.argtypes = [vp, ctypes.c_int]
+        L.orc_trace_len.restype = i64; L.orc_trace_len.argtypes = [vp]
+        L.orc_trace_get.argtypes = [vp, vp, vp, vp]
         L.orc_smash_matrix.argtypes = [vp, vp, u32, u32, ctypes.c_int, vp]
         _lib = L
     return _lib
@@ -200,6 +204,26 @@ class Sketcher:
         n = self.S * self.B
         return tuple(np.ctypeslib.as_array(getattr(lib(), f)(self._p), shape=(n,)).reshape(self.S, self.B).copy()
                      for f in ("orc_cws_r", "orc_cws_c", "orc_cws_b"))
+
+    def set_cws_tables(self, r, c, b):
+        """Replace the tables newCWS drew by [sketch_size][num_bins] arrays of the caller (before the first flush)."""
+        r, c, b = (np.ascontiguousarray(x, dtype=np.float64) for x in (r, c, b))
+        assert r.shape == c.shape == b.shape and r.size == self.S * self.B
+        lib().orc_set_cws_tables(self._p, r.ctypes.data, c.ctypes.data, b.ctypes.data)
+
+    def trace(self, on=True):
+        """Record (flush ordinal, bin, estiFreq) of every AddElement call from now on — read with get_trace()."""
+        lib().orc_trace_enable(self._p, int(on))
+
+    def get_trace(self):
+        """(flush uint32[n], bin int32[n], estiFreq float64[n]) in stream order."""
+        n = lib().orc_trace_len(self._p)
+        if n < 0:
+            raise OracleError(-20)
+        fl = np.zeros(n, dtype=np.uint32); bn = np.zeros(n, dtype=np.int32); f = np.zeros(n)
+        if n:
+            lib().orc_trace_get(self._p, fl.ctypes.data, bn.ctypes.data, f.ctypes.data)
+        return fl, bn, f
 
 
 def smash_matrix(mins, weights, metric="jaccard"):
