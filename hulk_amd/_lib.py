@@ -28,6 +28,9 @@ HULK_CWS_EXTERNAL = 1
 HULK_FLAG_GAMMA_CPYTHON, HULK_FLAG_NO_PRUNE, HULK_FLAG_NO_SKIP, HULK_FLAG_SHARD_FULL, HULK_FLAG_NO_OVERLAP, HULK_FLAG_NO_PRERESERVE, HULK_FLAG_CMS_CHAIN = 1, 2, 4, 8, 16, 32, 64
 HULK_FLAG_KMV, HULK_FLAG_KHF = 128, 256     # feed the bottom-k / k-hash-functions MinHash sketches (hulk_get_minhash)
 HULK_MINHASH_KMV, HULK_MINHASH_KHF = 0, 1
+HULK_METRIC_JACCARD, HULK_METRIC_WEIGHTED_JACCARD = 0, 1
+HULK_PANEL_ROW, HULK_PANEL_COLUMN = 0, 1    # hulk_set_panel: the snapshot is the subject (its row of the smash matrix) / the panel sketch is
+HULK_PANEL_MAX = 65536
 HULK_MINHASH_MAX_SKETCH = 4096
 HULK_MAX_BINS = 1 << 20
 HULK_INJECT_NONE, HULK_INJECT_STALE_SEAL, HULK_INJECT_STALE_STAGE = 0, 1, 2
@@ -46,6 +49,7 @@ ABI_SYMBOLS = (
     "hulk_load_sketches", "hulk_sketch_set_free", "hulk_sketch_set_info", "hulk_sketch_set_mins", "hulk_sketch_set_weights", "hulk_sketch_set_path",
     "hulk_sketch_set_banner", "hulk_smash_files", "hulk_bgzf_inflate", "hulk_get_minhash", "hulk_minhash_merge",
     "hulk_set_snapshots", "hulk_snapshot_count", "hulk_get_snapshots", "hulk_set_snapshot_callback", "hulk_poll_snapshots",
+    "hulk_set_panel", "hulk_get_snapshot_distances", "hulk_set_snapshot_panel_callback", "hulk_panel_distances",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -91,6 +95,11 @@ class SnapshotInfo(ctypes.Structure):
 # hulk_snapshot_fn: (user, info, mins, weights, sketch_size) -> 0 to go on
 SNAPSHOT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(SnapshotInfo), ctypes.POINTER(ctypes.c_uint64),
                                ctypes.POINTER(ctypes.c_double), ctypes.c_uint32)
+
+
+# hulk_snapshot_panel_fn: (user, info, mins, weights, sketch_size, distances, n_panel) -> 0 to go on
+SNAPSHOT_PANEL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(SnapshotInfo), ctypes.POINTER(ctypes.c_uint64),
+                                     ctypes.POINTER(ctypes.c_double), ctypes.c_uint32, ctypes.POINTER(ctypes.c_double), ctypes.c_uint32)
 
 
 class SmashStats(ctypes.Structure):
@@ -283,6 +292,11 @@ def load():
     L.hulk_get_snapshots.restype = ctypes.c_int; L.hulk_get_snapshots.argtypes = [vp, u64, u32, vp, vp, vp]
     L.hulk_set_snapshot_callback.restype = ctypes.c_int; L.hulk_set_snapshot_callback.argtypes = [vp, SNAPSHOT_FN, vp]
     L.hulk_poll_snapshots.restype = ctypes.c_int; L.hulk_poll_snapshots.argtypes = [vp, vp]
+    L.hulk_set_panel.restype = ctypes.c_int; L.hulk_set_panel.argtypes = [vp, vp, vp, u32, u32, ctypes.c_int, ctypes.c_int]
+    L.hulk_get_snapshot_distances.restype = ctypes.c_int; L.hulk_get_snapshot_distances.argtypes = [vp, u64, u32, vp]
+    L.hulk_set_snapshot_panel_callback.restype = ctypes.c_int; L.hulk_set_snapshot_panel_callback.argtypes = [vp, SNAPSHOT_PANEL_FN, vp]
+    L.hulk_panel_distances.restype = ctypes.c_int
+    L.hulk_panel_distances.argtypes = [ctypes.c_int, vp, vp, u32, vp, vp, u32, u32, ctypes.c_int, ctypes.c_int, vp]
     _lib = L
     return L
 

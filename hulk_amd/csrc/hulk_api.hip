@@ -361,7 +361,7 @@ int hulk_add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d
             c->ring_base = (c->ring_base + done) % c->ring_n;
             if ((fill + chunk) % I == 0) { c->ring_base = 0; if (done) c->cur_ring ^= 1; }  // clean: next batch uses the other ring
         }
-        if (c->snap.fn) { rc = snap_deliver(c, false); if (rc != HULK_OK) return rc; }     // (event queries: snapshots of flushes that have run)
+        if (c->snap.has_fn()) { rc = snap_deliver(c, false); if (rc != HULK_OK) return rc; }     // (event queries: snapshots of flushes that have run)
     }
     return HULK_OK;
 }
@@ -472,7 +472,7 @@ int hulk_flush(hulk_ctx *c) {
     if (c->bin_spectra > 1) return fail(c, HULK_ERR_STATE, "hulk_bin_reads_device filled several spectra: use hulk_flush_batch");
     const int rc = flush_batch(c, 1);
     if (rc == HULK_OK) c->bin_spectra = 0;
-    if (rc == HULK_OK && c->snap.fn) return snap_deliver(c, false);
+    if (rc == HULK_OK && c->snap.has_fn()) return snap_deliver(c, false);
     return rc;
 }
 
@@ -489,7 +489,7 @@ int hulk_finish(hulk_ctx *c) {
     }
     int rc = check_device_error(c);
     if (rc != HULK_OK) return rc;
-    if (c->snap.fn) { rc = snap_deliver(c, true); if (rc != HULK_OK) return rc; }          // all that remain (every flush has run)
+    if (c->snap.has_fn()) { rc = snap_deliver(c, true); if (rc != HULK_OK) return rc; }          // all that remain (every flush has run)
     // "no sequences received" (pipeline/sketch.go:237-239); the histogram test hook is exempt — and so is a rank of a sharded
     // run that happened to hold none of a short stream's intervals: the reference's count is over the global stream
     if (c->seq_count == 0 && !c->hist_hook_used && c->comm.global_intervals == 0) return fail(c, HULK_ERR_NO_SEQ);

@@ -155,6 +155,15 @@ struct hulk_ctx {
         uint64_t recorded = 0, delivered = 0;                                // snapshots planned into flushes / handed to fn
         uint64_t reads_at_flush = 0, reads_at_snapshot = 0;                  // seq_count at the latest flush / recorded snapshot
         hulk_snapshot_fn fn = nullptr; void *user = nullptr; bool fn_failed = false;
+        hulk_snapshot_panel_fn pfn = nullptr;                                // ... or the callback that also receives the distances
+        bool has_fn() const { return fn || pfn; }
+        // hulk_set_panel: reference sketches every snapshot is scored against where it is recorded (k_snap_panel, behind the
+        // kernels of the flush).  n == 0: no panel, none of this is allocated and nothing more is launched.
+        struct Panel {
+            uint32_t n = 0; int metric = 0, role = 0;
+            double *d_mT = nullptr, *d_wT = nullptr;                         // [S][smash_padded_n(n)]: (double)min, |w|, slot-major
+            double *d_dist = nullptr, *h_dist = nullptr;                     // [cap][n]: entry of snapshot i is i % cap; pinned mirror
+        } panel;
         // callback delivery: the snapshots of one flush become deliverable together, when `ev` (recorded on the flush stream
         // behind the flush kernels and the copies into the pinned mirror) has passed
         struct Group { uint64_t first; uint32_t n; hipEvent_t ev; };
@@ -238,6 +247,8 @@ int snap_flush_issued(hulk_ctx *c, hipStream_t s, uint64_t first, uint32_t n);
 // hands every snapshot whose flush has run to the callback (wait: all that are queued); no callback: nothing to do
 int snap_deliver(hulk_ctx *c, bool wait, uint32_t *delivered = nullptr);
 void snap_teardown(hulk_ctx *c);
+// behind the kernels of a flush that recorded snapshots: scores them against the panel (nothing without one)
+int snap_panel_flush(hulk_ctx *c, hipStream_t s, const FlushBatch &fb);
 // the multi-rank entry points refuse a context that records snapshots
 int snap_refuse(hulk_ctx *c, const char *entry);
 

@@ -451,6 +451,8 @@ int flush_kernels(hulk_ctx *c, hipStream_t s, uint32_t *hist, const FlushBatch &
                                      (int)c->slots, (int)c->slot_begin, c->ntiles, c->d_scanmap, c->d_state, fb,
                                      c->snap.d_mins, c->snap.d_weights, c->S));
     }
+    // (the snapshots of this flush are in the ring now, whichever of the kernels above stored them: score them against the panel)
+    if (fb.snap_mask && c->snap.panel.n) { const int rc = snap_panel_flush(c, s, fb); if (rc != HULK_OK) return rc; }
     return HULK_OK;
 }
 

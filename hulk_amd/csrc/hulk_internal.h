@@ -198,6 +198,14 @@ hipError_t launch_cws_beta(hipStream_t s, const uint64_t *d_uraw, uint64_t first
 hipError_t launch_smash(hipStream_t s, const unsigned long long *d_mins, const double *d_weights, uint32_t N, uint32_t S,
                         int metric, double *d_out, double *d_mT, double *d_wT);     // d_mT, d_wT: scratch [S][smash_padded_n(N)]
 uint32_t smash_padded_n(uint32_t N);
+// hulk_set_panel / hulk_panel_distances (k_snap_panel): the panel slot-major as k_smash_prep lays it out, d_pmT / d_pwT
+// [S][smash_padded_n(P)]; the snapshots in entries (base + m) % cap, m < M <= SCAN_BATCH_MAX, of the ring [cap][S] -> the same
+// entries of d_out [cap][P].  role 0: the snapshot is the subject, 1: the panel sketch is
+hipError_t launch_panel_prep(hipStream_t s, const unsigned long long *d_mins, const double *d_weights, uint32_t P, uint32_t S,
+                             double *d_pmT, double *d_pwT);
+hipError_t launch_snap_panel(hipStream_t s, const unsigned long long *d_snap_mins, const double *d_snap_weights, uint32_t S,
+                             uint32_t base, uint32_t cap, uint32_t M, const double *d_pmT, const double *d_pwT, uint32_t P,
+                             int metric, int role, double *d_out);
 hipError_t launch_build_k32(hipStream_t s, const double *d_rcb, float *d_k32, int slots,
                             int32_t num_bins, size_t row_stride);
 hipError_t launch_selftest_rcp(hipStream_t s, unsigned long long *d_mismatches);

@@ -8,6 +8,9 @@
 //   delivery         hulk_get_snapshots (synchronises), or a callback: behind the kernels of a flush that recorded snapshots the
 //                    flush stream copies their entries into a pinned mirror and records an event; the entry points of the step
 //                    path query the events of the queued flushes and hand what has arrived to the callback from the mirror
+//   the panel        hulk_set_panel: reference sketches held on the device slot-major; behind the kernels of a flush that recorded
+//                    snapshots k_snap_panel (hulk_cws.hip) scores them against it into a distance ring [cap][n_panel] that
+//                    shares the snapshot ring's indices, mirror and delivery
 #include "hulk_ctx.h"
 
 #include <algorithm>
@@ -23,8 +26,16 @@ int snap_refuse(hulk_ctx *c, const char *entry) {
     return fail(c, HULK_ERR_STATE, std::string(entry) + " is not available on a context that records snapshots (hulk_set_snapshots)");
 }
 
+static void panel_teardown(hulk_ctx *c) {
+    hulk_ctx::Snapshots::Panel &P = c->snap.panel;
+    hipFree(P.d_mT); hipFree(P.d_wT); hipFree(P.d_dist);
+    if (P.h_dist) hipHostFree(P.h_dist);
+    P = hulk_ctx::Snapshots::Panel{};
+}
+
 void snap_teardown(hulk_ctx *c) {
     hulk_ctx::Snapshots &S = c->snap;
+    panel_teardown(c);
     hipFree(S.d_mins); hipFree(S.d_weights);
     if (S.h_mins) hipHostFree(S.h_mins);
     if (S.h_weights) hipHostFree(S.h_weights);
@@ -47,7 +58,9 @@ static int deliver_front(hulk_ctx *c, bool wait, bool *ready, uint32_t *count) {
     const size_t SS = c->S;
     for (uint32_t i = 0; i < g.n; i++) {
         const size_t at = (size_t)((g.first + i) % S.cap);
-        const int r = S.fn(S.user, &S.info[at], S.h_mins + at * SS, S.h_weights + at * SS, c->S);
+        const int r = S.pfn ? S.pfn(S.user, &S.info[at], S.h_mins + at * SS, S.h_weights + at * SS, c->S,
+                                    S.panel.n ? S.panel.h_dist + at * S.panel.n : nullptr, S.panel.n)
+                            : S.fn(S.user, &S.info[at], S.h_mins + at * SS, S.h_weights + at * SS, c->S);
         S.delivered++;
         if (count) (*count)++;
         if (r != 0) { S.fn_failed = true; c->sticky = HULK_ERR_STATE; return snap_failed(c); }
@@ -62,7 +75,7 @@ int snap_deliver(hulk_ctx *c, bool wait, uint32_t *delivered) {
     hulk_ctx::Snapshots &S = c->snap;
     if (delivered) *delivered = 0;
     if (S.fn_failed) return snap_failed(c);
-    if (!S.fn) return HULK_OK;
+    if (!S.has_fn()) return HULK_OK;
     while (S.group_head < S.groups.size()) {
         bool ready = false;
         const int rc = deliver_front(c, wait, &ready, delivered);
@@ -98,7 +111,7 @@ int snap_plan(hulk_ctx *c, FlushBatch &fb, uint32_t count, int closed_by, uint64
     if (!k) return HULK_OK;
     // (hulk_set_snapshots bounded the batch: k <= cap)  With a callback an undelivered snapshot is never overwritten: the
     // flushes that hold the entries this one takes are waited for and delivered first.  Every earlier flush is queued by now.
-    if (S.fn) {
+    if (S.has_fn()) {
         while (S.delivered + S.cap < S.recorded + k) {
             if (S.group_head >= S.groups.size()) return fail(c, HULK_ERR_STATE, "snapshot ring: undelivered snapshots without a queued flush");
             bool ready = false;
@@ -115,8 +128,12 @@ int snap_plan(hulk_ctx *c, FlushBatch &fb, uint32_t count, int closed_by, uint64
 
 int snap_flush_issued(hulk_ctx *c, hipStream_t s, uint64_t first, uint32_t n) {
     hulk_ctx::Snapshots &S = c->snap;
-    if (!S.fn || !n) return HULK_OK;
+    if (!S.has_fn() || !n) return HULK_OK;
     const size_t SS = c->S, at = (size_t)(first % S.cap), run = std::min<size_t>(n, S.cap - at);
+    if (const size_t PN = S.panel.n) {                           // (k_snap_panel has been queued in front of this: flush_kernels)
+        HIPCHK(c, hipMemcpyAsync(S.panel.h_dist + at * PN, S.panel.d_dist + at * PN, run * PN * 8, hipMemcpyDeviceToHost, s));
+        if (run < n) HIPCHK(c, hipMemcpyAsync(S.panel.h_dist, S.panel.d_dist, (n - run) * PN * 8, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(c, hipMemcpyAsync(S.h_mins + at * SS, S.d_mins + at * SS, run * SS * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(S.h_weights + at * SS, S.d_weights + at * SS, run * SS * 8, hipMemcpyDeviceToHost, s));
     if (run < n) {                                               // the ring wraps inside this flush
@@ -129,6 +146,14 @@ int snap_flush_issued(hulk_ctx *c, hipStream_t s, uint64_t first, uint32_t n) {
     const hipError_t e = hipEventRecord(ev, s);
     if (e != hipSuccess) { S.free_events.push_back(ev); return fail_hip(c, e, "hipEventRecord(snapshot)"); }
     S.groups.push_back(hulk_ctx::Snapshots::Group{first, n, ev});
+    return HULK_OK;
+}
+
+int snap_panel_flush(hulk_ctx *c, hipStream_t s, const FlushBatch &fb) {
+    const hulk_ctx::Snapshots &S = c->snap;
+    if (!S.panel.n || !fb.snap_mask) return HULK_OK;
+    HIPCHK(c, launch_snap_panel(s, S.d_mins, S.d_weights, c->S, fb.snap_base, fb.snap_cap, (uint32_t)__builtin_popcount(fb.snap_mask),
+                                S.panel.d_mT, S.panel.d_wT, S.panel.n, S.panel.metric, S.panel.role, S.panel.d_dist));
     return HULK_OK;
 }
 
@@ -170,8 +195,103 @@ int hulk_set_snapshot_callback(hulk_ctx *c, hulk_snapshot_fn fn, void *user) {
     if (!c) return HULK_ERR_ARG;
     if (!c->snap.every) return fail(c, HULK_ERR_STATE, "the context records no snapshots (hulk_set_snapshots)");
     if (c->seq_count || c->flush_index || c->finished) return fail(c, HULK_ERR_STATE, "the snapshot callback must be set before the first read");
-    c->snap.fn = fn; c->snap.user = user;
+    c->snap.fn = fn; c->snap.pfn = nullptr; c->snap.user = user;
     return HULK_OK;
+}
+
+int hulk_set_snapshot_panel_callback(hulk_ctx *c, hulk_snapshot_panel_fn fn, void *user) {
+    if (!c) return HULK_ERR_ARG;
+    if (!c->snap.every) return fail(c, HULK_ERR_STATE, "the context records no snapshots (hulk_set_snapshots)");
+    if (c->seq_count || c->flush_index || c->finished) return fail(c, HULK_ERR_STATE, "the snapshot callback must be set before the first read");
+    c->snap.pfn = fn; c->snap.fn = nullptr; c->snap.user = user;
+    return HULK_OK;
+}
+
+int hulk_set_panel(hulk_ctx *c, const uint64_t *mins, const double *weights, uint32_t n_panel, uint32_t sketch_size, int metric, int role) {
+    if (!c) return HULK_ERR_ARG;
+    if (!c->snap.every) return fail(c, HULK_ERR_STATE, "the context records no snapshots (hulk_set_snapshots)");
+    if (c->seq_count || c->flush_index || c->finished) return fail(c, HULK_ERR_STATE, "the panel must be set before the first read");
+    if (n_panel == 0) { panel_teardown(c); return HULK_OK; }
+    if (!mins || !weights) return fail(c, HULK_ERR_ARG, "NULL");
+    if (metric != HULK_METRIC_JACCARD && metric != HULK_METRIC_WEIGHTED_JACCARD) return fail(c, HULK_ERR_ARG, "metric");
+    if (role != HULK_PANEL_ROW && role != HULK_PANEL_COLUMN) return fail(c, HULK_ERR_ARG, "panel role");
+    if (sketch_size != c->S) return fail(c, HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(c->S) + " vs " + std::to_string(sketch_size) + "\n");
+    if (n_panel > HULK_PANEL_MAX) return fail(c, HULK_ERR_ARG, "panel of " + std::to_string(n_panel) + " sketches (at most " + std::to_string(HULK_PANEL_MAX) + ")");
+    panel_teardown(c);
+    hulk_ctx::Snapshots::Panel &P = c->snap.panel;
+    const size_t NS = (size_t)n_panel * sketch_size, NT = (size_t)smash_padded_n(n_panel) * sketch_size, ND = (size_t)c->snap.cap * n_panel;
+    unsigned long long *d_m = nullptr; double *d_w = nullptr;
+    auto bail = [&](hipError_t e, const char *what) {
+        const int rc = fail_hip(c, e, what); const std::string msg = c->last_error;
+        hipFree(d_m); hipFree(d_w); panel_teardown(c); c->last_error = msg; return rc;
+    };
+    hipError_t e;
+    if ((e = hipMalloc((void **)&d_m, NS * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
+    if ((e = hipMalloc((void **)&d_w, NS * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
+    if ((e = hipMalloc((void **)&P.d_mT, NT * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
+    if ((e = hipMalloc((void **)&P.d_wT, NT * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
+    if ((e = hipMalloc((void **)&P.d_dist, ND * 8)) != hipSuccess) return bail(e, "hipMalloc(panel distances)");
+    if ((e = hipHostMalloc((void **)&P.h_dist, ND * 8, hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc(panel distances)");
+    if ((e = hipMemcpy(d_m, mins, NS * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(panel)");
+    if ((e = hipMemcpy(d_w, weights, NS * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(panel)");
+    if ((e = hipMemsetAsync(P.d_dist, 0, ND * 8, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync(panel distances)");
+    if ((e = launch_panel_prep(c->stream, d_m, d_w, n_panel, sketch_size, P.d_mT, P.d_wT)) != hipSuccess) return bail(e, "k_smash_prep(panel)");
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize(panel)");
+    hipFree(d_m); hipFree(d_w);
+    P.n = n_panel; P.metric = metric; P.role = role;
+    return HULK_OK;
+}
+
+int hulk_get_snapshot_distances(hulk_ctx *c, uint64_t first, uint32_t n, double *out) {
+    if (!c) return HULK_ERR_ARG;
+    if (!c->snap.every) return fail(c, HULK_ERR_STATE, "the context records no snapshots (hulk_set_snapshots)");
+    if (!c->snap.panel.n) return fail(c, HULK_ERR_STATE, "the context has no panel (hulk_set_panel)");
+    { const int rcs = sync_all(c); if (rcs != HULK_OK) return rcs; }
+    const hulk_ctx::Snapshots &S = c->snap;
+    const uint64_t held = S.recorded > S.cap ? S.recorded - S.cap : 0;
+    if (first < held) return fail(c, HULK_ERR_ARG, "snapshot " + std::to_string(first) + " was dropped from the ring (oldest held: " + std::to_string(held) + ")");
+    if (first + n > S.recorded) return fail(c, HULK_ERR_ARG, "snapshots [" + std::to_string(first) + ", " + std::to_string(first + n) + ") asked for, " + std::to_string(S.recorded) + " recorded");
+    if (!n) return HULK_OK;
+    if (!out) return fail(c, HULK_ERR_ARG, "NULL");
+    const size_t PN = S.panel.n;
+    for (uint32_t i = 0; i < n; ) {
+        const size_t at = (size_t)((first + i) % S.cap), run = std::min<size_t>(n - i, S.cap - at);
+        HIPCHK(c, hipMemcpyAsync(out + (size_t)i * PN, S.panel.d_dist + at * PN, run * PN * 8, hipMemcpyDeviceToHost, c->stream));
+        i += (uint32_t)run;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HULK_OK;
+}
+
+int hulk_panel_distances(int device, const uint64_t *snap_mins, const double *snap_weights, uint32_t m, const uint64_t *panel_mins,
+                         const double *panel_weights, uint32_t n_panel, uint32_t sketch_size, int metric, int role, double *out) {
+    if (metric != HULK_METRIC_JACCARD && metric != HULK_METRIC_WEIGHTED_JACCARD) return fail(nullptr, HULK_ERR_ARG, "metric");
+    if (role != HULK_PANEL_ROW && role != HULK_PANEL_COLUMN) return fail(nullptr, HULK_ERR_ARG, "panel role");
+    if (n_panel > HULK_PANEL_MAX) return fail(nullptr, HULK_ERR_ARG, "panel of " + std::to_string(n_panel) + " sketches (at most " + std::to_string(HULK_PANEL_MAX) + ")");
+    if (!sketch_size) return fail(nullptr, HULK_ERR_ARG, "sketch_size");
+    if (!m || !n_panel) return HULK_OK;
+    if (!snap_mins || !snap_weights || !panel_mins || !panel_weights || !out) return fail(nullptr, HULK_ERR_ARG, "NULL");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, HULK_ERR_NO_DEVICE);
+    if (device < 0 || device >= ndev) return fail(nullptr, HULK_ERR_ARG, "device ordinal");
+    const size_t S = sketch_size, MS = (size_t)m * S, NS = (size_t)n_panel * S, NT = (size_t)smash_padded_n(n_panel) * S, MP = (size_t)m * n_panel;
+    unsigned long long *d_sm = nullptr, *d_pm = nullptr; double *d_sw = nullptr, *d_pw = nullptr, *d_mT = nullptr, *d_wT = nullptr, *d_out = nullptr;
+    auto done = [&](int rc) { hipFree(d_sm); hipFree(d_sw); hipFree(d_pm); hipFree(d_pw); hipFree(d_mT); hipFree(d_wT); hipFree(d_out); return rc; };
+#define PD_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return done(fail_hip(nullptr, e_, #call)); } while (0)
+    PD_CHK(hipSetDevice(device));
+    PD_CHK(hipMalloc((void **)&d_sm, MS * 8)); PD_CHK(hipMalloc((void **)&d_sw, MS * 8));
+    PD_CHK(hipMalloc((void **)&d_pm, NS * 8)); PD_CHK(hipMalloc((void **)&d_pw, NS * 8));
+    PD_CHK(hipMalloc((void **)&d_mT, NT * 8)); PD_CHK(hipMalloc((void **)&d_wT, NT * 8));
+    PD_CHK(hipMalloc((void **)&d_out, MP * 8));
+    PD_CHK(hipMemcpy(d_sm, snap_mins, MS * 8, hipMemcpyHostToDevice)); PD_CHK(hipMemcpy(d_sw, snap_weights, MS * 8, hipMemcpyHostToDevice));
+    PD_CHK(hipMemcpy(d_pm, panel_mins, NS * 8, hipMemcpyHostToDevice)); PD_CHK(hipMemcpy(d_pw, panel_weights, NS * 8, hipMemcpyHostToDevice));
+    PD_CHK(launch_panel_prep(nullptr, d_pm, d_pw, n_panel, sketch_size, d_mT, d_wT));
+    for (uint32_t i = 0; i < m; i += SCAN_BATCH_MAX)              // a flush's worth of snapshots per launch; "ring" = this chunk, no wrap
+        PD_CHK(launch_snap_panel(nullptr, d_sm + (size_t)i * S, d_sw + (size_t)i * S, sketch_size, 0, 0xffffffffu,
+                                 std::min<uint32_t>(m - i, SCAN_BATCH_MAX), d_mT, d_wT, n_panel, metric, role, d_out + (size_t)i * n_panel));
+    PD_CHK(hipMemcpy(out, d_out, MP * 8, hipMemcpyDeviceToHost));
+#undef PD_CHK
+    return done(HULK_OK);
 }
 
 int hulk_snapshot_count(hulk_ctx *c, uint64_t *recorded, uint64_t *first_held) {

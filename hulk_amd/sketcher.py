@@ -70,6 +70,7 @@ class GpuSketcher:
             self.set_stream(stream)
         self._snapshot_thunk = None
         self._snapshot_error = None
+        self.n_panel = 0
         if snapshots:
             try:
                 self._chk(self._L.hulk_set_snapshots(self._ctx, snapshots, snapshot_capacity))
@@ -136,6 +137,54 @@ class GpuSketcher:
                 return 1
         thunk_c = _lib.SNAPSHOT_FN(thunk)
         self._chk(self._L.hulk_set_snapshot_callback(self._ctx, thunk_c, None))
+        self._snapshot_thunk = thunk_c                             # keep the callback alive as long as the context
+
+    # ---- a panel of reference sketches every snapshot is scored against where it is recorded (hulk_set_panel)
+    def set_panel(self, mins, weights, metric="jaccard", role="row"):
+        """Hold the panel mins / weights [n_panel][sketch_size] on the device; from then on every recorded snapshot carries its
+        distances to the panel's sketches — HULKdata.GetDistance as `smash` computes it.  metric: "jaccard" | "weightedjaccard";
+        role "row": the snapshot is the subject (its row of the matrix smash would print, the snapshot's weights), "column": each
+        panel sketch is (its column, the panel's weights).  After snapshots= and before the first read; an empty panel removes it."""
+        if metric not in ("jaccard", "weightedjaccard"):
+            raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: ['jaccard', 'weightedjaccard']")
+        if role not in ("row", "column"):
+            raise ValueError("role must be 'row' or 'column'")
+        mins = np.ascontiguousarray(mins, dtype=np.uint64)
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if mins.ndim != 2 or mins.shape != weights.shape:
+            raise ValueError("mins/weights must be [n_panel][sketch_size]")
+        n, s = mins.shape
+        self._chk(self._L.hulk_set_panel(self._ctx, mins.ctypes.data, weights.ctypes.data, n, s,
+                                         _lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+                                         _lib.HULK_PANEL_COLUMN if role == "column" else _lib.HULK_PANEL_ROW))
+        self.n_panel = n
+
+    def snapshot_distances(self, first=0, n=None):
+        """float64[n][n_panel]: the distances of snapshots [first, first + n) to the panel (n=None: all recorded from `first`
+        on; synchronises) — row i belongs to snapshots()'s entry i."""
+        if n is None:
+            n = max(self.snapshot_count()[0] - first, 0)
+        out = np.zeros((n, self.n_panel), dtype=np.float64)
+        self._chk(self._L.hulk_get_snapshot_distances(self._ctx, first, n, out.ctypes.data))
+        return out
+
+    def on_snapshot_scored(self, fn):
+        """on_snapshot with the snapshot's distances to the panel: fn(info, mins, weights, distances: np.float64[n_panel])
+        (an empty array without a panel).  Replaces an on_snapshot callable, as on_snapshot replaces this one."""
+        S = self.sketch_size
+
+        def thunk(_user, info, mins, weights, sketch_size, distances, n_panel):
+            try:
+                i = {"ordinal": int(info.contents.ordinal), "n_reads": int(info.contents.n_reads)}
+                m = np.ctypeslib.as_array(mins, shape=(S,)).copy()
+                w = np.ctypeslib.as_array(weights, shape=(S,)).copy()
+                d = np.ctypeslib.as_array(distances, shape=(n_panel,)).copy() if n_panel else np.zeros(0)
+                return 1 if fn(i, m, w, d) else 0
+            except Exception as e:  # noqa: BLE001 — reported through the ABI's status code, chained to the HulkError
+                self._snapshot_error = e
+                return 1
+        thunk_c = _lib.SNAPSHOT_PANEL_FN(thunk)
+        self._chk(self._L.hulk_set_snapshot_panel_callback(self._ctx, thunk_c, None))
         self._snapshot_thunk = thunk_c                             # keep the callback alive as long as the context
 
     def poll_snapshots(self):

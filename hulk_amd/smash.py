@@ -55,6 +55,31 @@ def distance_matrix(mins, weights, metric="jaccard", device=0, timing=None):
     return out
 
 
+def panel_distances(snap_mins, snap_weights, panel_mins, panel_weights, metric="jaccard", role="row", device=0):
+    """distances[i, p] between sketch i of snap_* [m][S] and sketch p of panel_* [n_panel][S], on the GPU with the kernel that
+    scores sketch snapshots against a panel (hulk_panel_distances): role "row" = sketch i is the subject (the block
+    distance_matrix([snap; panel])[:m, m:]), "column" = panel sketch p is (the block [m:, :m] transposed).  One against many."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if role not in ("row", "column"):
+        raise ValueError("role must be 'row' or 'column'")
+    sm = np.ascontiguousarray(snap_mins, dtype=np.uint64); sw = np.ascontiguousarray(snap_weights, dtype=np.float64)
+    pm = np.ascontiguousarray(panel_mins, dtype=np.uint64); pw = np.ascontiguousarray(panel_weights, dtype=np.float64)
+    if sm.ndim != 2 or pm.ndim != 2 or sm.shape != sw.shape or pm.shape != pw.shape:
+        raise ValueError("mins/weights must be [n][sketch_size]")
+    if sm.shape[1] != pm.shape[1]:
+        raise HulkError(-30, f"sketch length mismatch: {sm.shape[1]} vs {pm.shape[1]}\n")
+    out = np.zeros((sm.shape[0], pm.shape[0]), dtype=np.float64)
+    L = _lib.load()
+    rc = L.hulk_panel_distances(device, sm.ctypes.data, sw.ctypes.data, sm.shape[0], pm.ctypes.data, pw.ctypes.data, pm.shape[0],
+                                sm.shape[1], _lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+                                _lib.HULK_PANEL_COLUMN if role == "column" else _lib.HULK_PANEL_ROW, out.ctypes.data)
+    if rc != 0:
+        raise HulkError(rc, L.hulk_last_error(None).decode())
+    return out
+
+
 def go_format_f2(v: float) -> str:
     """strconv.FormatFloat(v, 'f', 2, 64)"""
     if v != v:

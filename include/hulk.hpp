@@ -68,7 +68,10 @@ struct HistoSketch {
 };
 
 // the histosketch as it stood after flushed spectrum `Ordinal` (1-based), `Reads` reads into the stream
-struct Snapshot { uint64_t Ordinal = 0, Reads = 0; HistoSketch Sketch; };
+struct Snapshot {
+    uint64_t Ordinal = 0, Reads = 0; HistoSketch Sketch;
+    std::vector<double> Distances;      // to the sketches of Boss::SetPanel, in the panel's order; empty without a panel
+};
 
 struct IngestStats { uint64_t SeqCount = 0, LengthTotal = 0, Lines = 0, BytesIn = 0; double Seconds = 0; };
 
@@ -77,8 +80,8 @@ class Boss {
     // findMinimizers + NewHistoSketch: throws hulk::Error with the reference's message
     static Boss FindMinimizers(const SketchInfo &info) { return Boss(info); }
 
-    Boss(Boss &&o) noexcept : ctx_(o.ctx_), info_(o.info_), bins_(o.bins_), sharded_(o.sharded_), bases_(std::move(o.bases_)),
-                              offsets_(std::move(o.offsets_)), snap_(std::move(o.snap_)) { o.ctx_ = nullptr; }
+    Boss(Boss &&o) noexcept : ctx_(o.ctx_), info_(o.info_), bins_(o.bins_), sharded_(o.sharded_), panel_(o.panel_), bases_(std::move(o.bases_)),
+                              offsets_(std::move(o.offsets_)), snap_(std::move(o.snap_)) { o.ctx_ = nullptr; o.panel_ = 0; }
     Boss(const Boss &) = delete;
     Boss &operator=(const Boss &) = delete;
     ~Boss() { if (ctx_) hulk_destroy(ctx_); }
@@ -165,7 +168,10 @@ class Boss {
     // ---- sketch snapshots (hulk_set_snapshots): the sketch after every `every`-th flushed spectrum, recorded on the GPU inside
     // the batched flush — what batch = 1 and Sketch() after every interval would give, without giving up the batch.  Call before
     // the first AddSeq; capacity = snapshots the device ring holds (0 = the library's default).  Not with Shard().
-    void EnableSnapshots(uint32_t every, uint32_t capacity = 0) { check(hulk_set_snapshots(ctx_, every, capacity)); }
+    void EnableSnapshots(uint32_t every, uint32_t capacity = 0) {
+        check(hulk_set_snapshots(ctx_, every, capacity));
+        panel_ = 0;                        // (setting the snapshots again drops a panel: hulk_set_panel)
+    }
     // every snapshot the ring still holds, in stream order (synchronises, like Sketch())
     std::vector<Snapshot> CollectSnapshots() {
         push();
@@ -176,9 +182,32 @@ class Boss {
         std::vector<uint64_t> mins((size_t)n * S + 1);
         std::vector<double> weights((size_t)n * S + 1);
         check(hulk_get_snapshots(ctx_, first, n, inf.data(), mins.data(), weights.data()));
+        std::vector<double> dist((size_t)n * panel_ + 1);
+        if (panel_) check(hulk_get_snapshot_distances(ctx_, first, n, dist.data()));
         std::vector<Snapshot> out(n);
-        for (uint32_t i = 0; i < n; i++) fill(out[i], inf[i], mins.data() + (size_t)i * S, weights.data() + (size_t)i * S);
+        for (uint32_t i = 0; i < n; i++) {
+            fill(out[i], inf[i], mins.data() + (size_t)i * S, weights.data() + (size_t)i * S);
+            out[i].Distances.assign(dist.data() + (size_t)i * panel_, dist.data() + (size_t)(i + 1) * panel_);
+        }
         return out;
+    }
+    // ---- a panel of reference sketches (hulk_set_panel): every snapshot is scored against it on the GPU, where it is recorded,
+    // and carries the result in Snapshot::Distances — HULKdata.GetDistance as Smash() computes it.  metric: "jaccard" |
+    // "weightedjaccard"; snapshotIsSubject: the snapshot's row of the matrix smash would print (its weights), else its column
+    // (the panel's weights).  After EnableSnapshots, before the first AddSeq; an empty panel removes it.
+    void SetPanel(const std::vector<HistoSketch> &panel, const std::string &metric = "jaccard", bool snapshotIsSubject = true) {
+        if (metric != "jaccard" && metric != "weightedjaccard") throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+        const uint32_t N = (uint32_t)panel.size(), S = N ? panel[0].SketchSize : info_.SketchSize;
+        std::vector<uint64_t> mins((size_t)N * S + 1);
+        std::vector<double> weights((size_t)N * S + 1);
+        for (uint32_t i = 0; i < N; i++) {
+            if (panel[i].Sketch.size() != S || panel[i].SketchWeights.size() != S) throw Error(HULK_ERR_ARG, "sketch length mismatch");
+            std::copy(panel[i].Sketch.begin(), panel[i].Sketch.end(), mins.begin() + (size_t)i * S);
+            std::copy(panel[i].SketchWeights.begin(), panel[i].SketchWeights.end(), weights.begin() + (size_t)i * S);
+        }
+        check(hulk_set_panel(ctx_, mins.data(), weights.data(), N, S, metric == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD,
+                             snapshotIsSubject ? HULK_PANEL_ROW : HULK_PANEL_COLUMN));
+        panel_ = N;
     }
     // fn gets every snapshot once, in stream order, on the caller's thread, from inside AddSeq / Flush / SketchFiles / PollSnapshots /
     // StopWork as soon as the flush that recorded it is found complete (nothing on the step path waits for it).  An exception thrown
@@ -186,7 +215,7 @@ class Boss {
     void OnSnapshot(std::function<void(const Snapshot &)> fn) {
         auto st = std::make_unique<SnapState>();
         st->fn = std::move(fn); st->owner_info = info_; st->bins = bins_;
-        check(hulk_set_snapshot_callback(ctx_, &Boss::snap_thunk, st.get()));
+        check(hulk_set_snapshot_panel_callback(ctx_, &Boss::snap_thunk, st.get()));     // (Distances stay empty without a panel)
         snap_ = std::move(st);
     }
     // hands the snapshots of every flush that has run to the OnSnapshot function; never blocks; returns how many
@@ -236,9 +265,14 @@ class Boss {
         s.Sketch.Sketch.assign(mins, mins + info.SketchSize); s.Sketch.SketchWeights.assign(weights, weights + info.SketchSize);
     }
     void fill(Snapshot &s, const hulk_snapshot_info &inf, const uint64_t *mins, const double *weights) { fill(s, info_, bins_, inf, mins, weights); }
-    static int snap_thunk(void *user, const hulk_snapshot_info *inf, const uint64_t *mins, const double *weights, uint32_t) {
+    static int snap_thunk(void *user, const hulk_snapshot_info *inf, const uint64_t *mins, const double *weights, uint32_t,
+                          const double *distances, uint32_t n_panel) {
         SnapState *st = static_cast<SnapState *>(user);
-        try { Snapshot s; fill(s, st->owner_info, st->bins, *inf, mins, weights); st->fn(s); return 0; }
+        try {
+            Snapshot s; fill(s, st->owner_info, st->bins, *inf, mins, weights);
+            if (n_panel) s.Distances.assign(distances, distances + n_panel);
+            st->fn(s); return 0;
+        }
         catch (...) { st->thrown = std::current_exception(); return 1; }             // (no exception crosses the C ABI)
     }
     std::vector<uint64_t> collect(int algo) {
@@ -254,6 +288,7 @@ class Boss {
     SketchInfo info_;
     int32_t bins_ = 0;
     bool sharded_ = false;
+    uint32_t panel_ = 0;                   // SetPanel: sketches in the panel
     std::vector<uint8_t> bases_;
     std::vector<uint64_t> offsets_;
     std::unique_ptr<SnapState> snap_;      // OnSnapshot: lives on the heap, the library holds its address

@@ -65,7 +65,9 @@ extern "C" {
  *    hulk_create), hulk_get_profile_table (hulk_set_profiling bit 32), hulk_load_sketches / hulk_smash_files (the directory form
  *    of `hulk smash`); the test hooks hulk_debug_inject / hulk_debug_read left the shipping library (profiling build only).
  *    Additions since (no existing entry point changed): HULK_FLAG_KMV / HULK_FLAG_KHF with hulk_get_minhash / hulk_minhash_merge;
- *    sketch snapshots (hulk_set_snapshots, hulk_snapshot_count, hulk_get_snapshots, hulk_set_snapshot_callback, hulk_poll_snapshots).
+ *    sketch snapshots (hulk_set_snapshots, hulk_snapshot_count, hulk_get_snapshots, hulk_set_snapshot_callback, hulk_poll_snapshots);
+ *    a panel the snapshots are scored against (hulk_set_panel, hulk_get_snapshot_distances, hulk_set_snapshot_panel_callback,
+ *    hulk_panel_distances).
  * Bindings compare it with the value they were written for. */
 #define HULK_ABI_VERSION 4
 
@@ -441,7 +443,9 @@ int hulk_minhash_merge(hulk_ctx *ctx, int algo, const uint64_t *mins, uint32_t n
  * batches of a stream pay for that, the steady state (k_flush_decide passes the batch over) costs one small copy kernel per batch.
  * Off by default; a context that never calls hulk_set_snapshots allocates nothing for it and launches what it always did.
  * Not available on the multi-rank paths: on a context with snapshots hulk_bin_reads_device*, hulk_flush_batch*, hulk_comm_init*
- * and hulk_step_* return HULK_ERR_STATE (a delta step of hulk_step_sharded does not run the flush kernels at all). */
+ * and hulk_step_* return HULK_ERR_STATE (a delta step of hulk_step_sharded does not run the flush kernels at all).
+ * Calling hulk_set_snapshots again (before the first read) starts over: the ring, the callback and a panel set with hulk_set_panel
+ * are dropped. */
 typedef struct hulk_snapshot_info {
     uint64_t ordinal;   /* 1-based number of the flushed spectrum (interval rule, hulk_flush and hulk_finish's last one alike) */
     uint64_t n_reads;   /* reads of the stream when that spectrum closed */
@@ -471,6 +475,43 @@ typedef int (*hulk_snapshot_fn)(void *user, const hulk_snapshot_info *info, cons
 int hulk_set_snapshot_callback(hulk_ctx *ctx, hulk_snapshot_fn fn, void *user);
 /* Hands the snapshots of every flush that has run to the callback; never blocks.  *delivered (may be NULL): how many. */
 int hulk_poll_snapshots(hulk_ctx *ctx, uint32_t *delivered);
+
+/* ---- a panel of reference sketches: every snapshot is scored where it is recorded ------------------------------------------------
+ * The panel — n_panel histosketches of sketch_size slots, host arrays [n_panel][sketch_size] — is uploaded once and kept on the device
+ * slot-major.  Behind the kernels of every flush that records snapshots one more kernel (k_snap_panel) compares the flush's <= 16
+ * snapshots with all of it: distances[p] = HULKdata.GetDistance (src/sketchio/sketchio.go:259-306) exactly as hulk_smash computes it —
+ * mins compared as float64, jaccard = 1 - equal / sketch_size, weightedjaccard = GetWJD with both weight vectors the SUBJECT's,
+ * |w| = max(max(w,0), max(-w,0)), the fp64 sums taken over the slots in ascending order — so a snapshot's distances are bit for bit
+ * what `smash` prints for it if its file lay in the panel's directory (a weighted distance that is 0 / 0 or Inf / Inf is the NaN with
+ * the sign bit set, 0xFFF8000000000000, which the reference's division gives on amd64; hulk_smash leaves the GPU's unsigned one):
+ *   HULK_PANEL_ROW     the snapshot is the subject (its row of that matrix; the snapshot's weights)
+ *   HULK_PANEL_COLUMN  each panel sketch is the subject (its column; the panel's weights).  For jaccard the two are the same.
+ * The distances go to a device ring [capacity][n_panel] next to the snapshot ring and travel with the snapshots: same indices, same
+ * dropping, same delivery; no synchronisation and no allocation on the step path.  A context without a panel allocates none of this
+ * and launches what it always did. */
+#define HULK_PANEL_ROW 0
+#define HULK_PANEL_COLUMN 1
+#define HULK_PANEL_MAX 65536u
+/* After hulk_set_snapshots and before the first read / flush (HULK_ERR_STATE otherwise).  metric: HULK_METRIC_JACCARD /
+ * HULK_METRIC_WEIGHTED_JACCARD.  sketch_size other than the context's: HULK_ERR_ARG, "sketch length mismatch: %d vs %d\n" (the
+ * context's, the panel's; sketchio.go:274-277).  n_panel > HULK_PANEL_MAX: HULK_ERR_ARG.  n_panel == 0 removes the panel.  Allocates
+ * the panel (n_panel * sketch_size * 16 bytes of device memory) and the distance ring with its pinned mirror (capacity * n_panel * 8
+ * bytes each).  A later hulk_set_panel replaces the panel; a later hulk_set_snapshots drops it (the ring it was sized for is gone). */
+int hulk_set_panel(hulk_ctx *ctx, const uint64_t *mins, const double *weights, uint32_t n_panel, uint32_t sketch_size, int metric,
+                   int role);
+/* Synchronises like hulk_get_snapshots and fails like it for a dropped or not yet recorded snapshot: out[n][n_panel], the distances of
+ * snapshots [first, first + n).  HULK_ERR_STATE on a context without a panel. */
+int hulk_get_snapshot_distances(hulk_ctx *ctx, uint64_t first, uint32_t n, double *out);
+/* hulk_set_snapshot_callback's rules (stream order, exactly once, no overwrite of an undelivered snapshot, a non-zero return ends the
+ * run), with the snapshot's distances[n_panel] (pinned staging, valid during the call; NULL / 0 without a panel).  A context has ONE
+ * callback: setting either kind replaces the other. */
+typedef int (*hulk_snapshot_panel_fn)(void *user, const hulk_snapshot_info *info, const uint64_t *mins, const double *weights,
+                                      uint32_t sketch_size, const double *distances, uint32_t n_panel);
+int hulk_set_snapshot_panel_callback(hulk_ctx *ctx, hulk_snapshot_panel_fn fn, void *user);
+/* The same kernel on host arrays, without a context: out[m][n_panel] = the distance of snapshot i (snap_mins / snap_weights
+ * [m][sketch_size]) and panel sketch p in the given role; the snapshots are taken 16 at a time.  A one-against-many query. */
+int hulk_panel_distances(int device, const uint64_t *snap_mins, const double *snap_weights, uint32_t m, const uint64_t *panel_mins,
+                         const double *panel_weights, uint32_t n_panel, uint32_t sketch_size, int metric, int role, double *out);
 
 /* Count-min counters as fp64 [7][2000] (test hook). */
 int hulk_get_cms(hulk_ctx *ctx, double *counters);
