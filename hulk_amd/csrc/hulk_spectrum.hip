@@ -16,11 +16,16 @@ namespace {
 // with its own chain of ~ln(k^4) fp64 steps (no lock-step tail per 64 values); 8 waves/SIMD.
 // Output: key = spectrum slot << 20 | bin  (k^4 < 2^20 for k <= 31).
 // ------------------------------------------------------------------------------------------
-// The step loop of k_jump_bin in assembly (fixed registers v40..v57, s60..s63): hipcc's version of the same loop
-// carries two v_mov_b64 and a dozen scalar mask instructions per pair of steps; this one is the 17 VALU
-// instructions of a step (16 since r * 2^-31 = ((key >> 33) + 1) * 2^-31 is ONE fma(float64(key >> 33), 2^-31, 2^-31) instead of an
-// integer add before the conversion and an exponent adjustment after it) plus v_cmp / s_and and the exit test, the LCG state ping-ponging between v[40:41] and
-// v[42:43].  Lanes that reach p >= n leave the exec mask and keep their t.  The loop ends when at most `cut`
+// The step loop of the jump kernels in assembly (fixed registers v40..v58, s60..s63): hipcc's version of the same loop
+// carries two v_mov_b64 and a dozen scalar mask instructions per pair of steps; this one is the 14 VALU instructions of a
+// step (v_cmp and v_trunc_f64 among them) plus s_and and the exit test, the LCG state ping-ponging between v[40:41] and v[42:43].
+//  * key * a + 1: the upper dword's two cross products are two chained v_mad_u64_u32 (0 + lo * a_hi, then + hi * a_lo; only the
+//    lower dword of the sum is used) and one v_add_u32 onto the upper dword of lo * a_lo + 1.
+//  * r * 2^-31 = ((key >> 33) + 1) * 2^-31 without a conversion: the shift result m is written into the lower dword of a pair
+//    whose upper dword is held at 0x43300000, which IS the double 2^52 + m, and ONE fma(2^52 + m, 2^-31, 2^-31 - 2^21) gives
+//    (m + 1) * 2^-31 exactly (the product 2^21 + m * 2^-31 is exact inside the fma, the sum is representable, and so is the
+//    constant 2^-31 - 2^21: 52 significant bits).  VOP3 takes one scalar operand: the constant lives in v[56:57].
+// Lanes that reach p >= n leave the exec mask and keep their t.  The loop ends when at most `cut`
 // lanes are still running (cut = 0: when none is): chains take 12.8 +- 3.5 steps, so the last few lanes of a round
 // of 64 would keep the whole wave busy for ~24 — they are handed over instead (`left` = their mask, key/t = their
 // state at a step boundary) and finished by k_jump_left in a denser wave.
@@ -30,25 +35,25 @@ __device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, d
                                                  unsigned long long &left) {
     uint32_t tlo, thi, mlo, mhi, olo, ohi;
     const uint64_t fb = (uint64_t)__double_as_longlong(fn), tb = (uint64_t)__double_as_longlong(t0);
-    const uint32_t flo = (uint32_t)fb, fhi = (uint32_t)(fb >> 32), t0lo = (uint32_t)tb, t0hi = (uint32_t)(tb >> 32);
+    const uint32_t fhi = (uint32_t)(fb >> 32), t0lo = (uint32_t)tb, t0hi = (uint32_t)(tb >> 32);
+    const uint64_t cb = (uint64_t)__double_as_longlong(0x1p-31 - 0x1p21);       // exact: 2^21 - 2^-31 is a double
 #define HULK_JSTEP(KS_LO, KS_HI, KD, KD_HI, EXIT)                                    \
+    "v_mad_u64_u32 v[52:53], s[62:63], " KS_LO ", %[ahi], 0\n\t"                     \
+    "v_mad_u64_u32 v[54:55], s[62:63], " KS_HI ", %[alo], v[52:53]\n\t"              \
     "v_mad_u64_u32 " KD ", s[62:63], " KS_LO ", %[alo], 1\n\t"                       \
-    "v_mul_lo_u32 v54, " KS_LO ", %[ahi]\n\t"                                        \
-    "v_mul_lo_u32 v55, " KS_HI ", %[alo]\n\t"                                        \
-    "v_add3_u32 " KD_HI ", v55, " KD_HI ", v54\n\t"                                  \
-    "v_lshrrev_b32 v54, 1, " KD_HI "\n\t"                                            \
-    "v_cvt_f64_u32 v[46:47], v54\n\t"                                                \
-    "v_fma_f64 v[46:47], v[46:47], %[p31], %[p31]\n\t"                               \
-    "v_rcp_f64 v[48:49], v[46:47]\n\t"                                               \
+    "v_add_u32 " KD_HI ", " KD_HI ", v54\n\t"                                        \
+    "v_lshrrev_b32 v46, 1, " KD_HI "\n\t"                                            \
+    "v_fma_f64 v[48:49], v[46:47], %[p31], v[56:57]\n\t"                             \
+    "v_rcp_f64 v[50:51], v[48:49]\n\t"                                               \
     "s_nop 0\n\t"                                                                    \
-    "v_fma_f64 v[50:51], -v[46:47], v[48:49], 1.0\n\t"                               \
-    "v_fma_f64 v[48:49], v[48:49], v[50:51], v[48:49]\n\t"                           \
-    "v_fma_f64 v[50:51], -v[46:47], v[48:49], 1.0\n\t"                               \
-    "v_fma_f64 v[48:49], v[48:49], v[50:51], v[48:49]\n\t"                           \
-    "v_fma_f64 v[52:53], v[44:45], v[48:49], v[48:49]\n\t"                           \
-    "v_cmp_lt_u32 vcc, v53, v57\n\t"                                                 \
+    "v_fma_f64 v[52:53], -v[48:49], v[50:51], 1.0\n\t"                               \
+    "v_fma_f64 v[50:51], v[50:51], v[52:53], v[50:51]\n\t"                           \
+    "v_fma_f64 v[52:53], -v[48:49], v[50:51], 1.0\n\t"                               \
+    "v_fma_f64 v[50:51], v[50:51], v[52:53], v[50:51]\n\t"                           \
+    "v_fma_f64 v[54:55], v[44:45], v[50:51], v[50:51]\n\t"                           \
+    "v_cmp_lt_u32 vcc, v55, v58\n\t"                                                 \
     "s_and_b64 exec, exec, vcc\n\t"                                                  \
-    "v_trunc_f64 v[44:45], v[52:53]\n\t"                                             \
+    "v_trunc_f64 v[44:45], v[54:55]\n\t"                                             \
     "s_bcnt1_i32_b64 s62, exec\n\t"                                                  \
     "s_cmp_le_u32 s62, %[cut]\n\t"                                                   \
     "s_cbranch_scc1 " EXIT "\n\t"
@@ -56,8 +61,10 @@ __device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, d
         "s_mov_b64 s[60:61], exec\n\t"
         "v_mov_b32 v40, %[klo]\n\t"
         "v_mov_b32 v41, %[khi]\n\t"
-        "v_mov_b32 v56, %[flo]\n\t"
-        "v_mov_b32 v57, %[fhi]\n\t"
+        "v_mov_b32 v47, 0x43300000\n\t"
+        "v_mov_b32 v56, %[clo]\n\t"
+        "v_mov_b32 v57, %[chi]\n\t"
+        "v_mov_b32 v58, %[fhi]\n\t"
         "v_mov_b32 v44, %[t0lo]\n\t"
         "v_mov_b32 v45, %[t0hi]\n\t"
         "1:\n\t"
@@ -76,10 +83,11 @@ __device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, d
         "v_mov_b32 %[olo], v40\n\t"
         "v_mov_b32 %[ohi], v41\n\t"
         : [tlo] "=v"(tlo), [thi] "=v"(thi), [olo] "=v"(olo), [ohi] "=v"(ohi), [mlo] "=s"(mlo), [mhi] "=s"(mhi)
-        : [klo] "v"(klo), [khi] "v"(khi), [flo] "v"(flo), [fhi] "v"(fhi), [t0lo] "v"(t0lo), [t0hi] "v"(t0hi),
+        : [klo] "v"(klo), [khi] "v"(khi), [fhi] "v"(fhi), [t0lo] "v"(t0lo), [t0hi] "v"(t0hi),
+          [clo] "s"((uint32_t)cb), [chi] "s"((uint32_t)(cb >> 32)),
           [alo] "s"(0x87B0B0FDu), [ahi] "s"(0x27BB2EE6u), [cut] "s"(cut), [p31] "s"(0x3E00000000000000ull /* 2^-31 */)
         : "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55",
-          "v56", "v57", "s60", "s61", "s62", "s63", "vcc", "scc", "memory");
+          "v56", "v57", "v58", "s60", "s61", "s62", "s63", "vcc", "scc", "memory");
 #undef HULK_JSTEP
     klo = olo; khi = ohi;
     left = ((unsigned long long)mhi << 32) | mlo;
