@@ -280,7 +280,7 @@ void hulk_destroy(hulk_ctx *c) {
         hipFree(ln.d_slow_list); hipFree(ln.d_slow_count);
         hulk::MinimizerList &ml = ln.ml;
         hipFree(ml.x); hipFree(ml.slot); hipFree(ml.key); hipFree(ml.cnt); hipFree(ml.off); hipFree(ml.bsum); hipFree(ml.partial);
-        hipFree(ml.nib); hipFree(ml.nib_over); hipFree(ml.lo); hipFree(ml.lo_cnt); hipFree(ml.dmask); hipFree(ml.dsum);
+        hipFree(ml.nib); hipFree(ml.nib_over); hipFree(ml.dmask); hipFree(ml.dsum);
     }
     for (int i = 0; i < 2; i++) if (c->ev_heavy[i]) hipEventDestroy(c->ev_heavy[i]);
     if (c->ev_hold) hipEventDestroy(c->ev_hold);
@@ -783,7 +783,7 @@ int hulk_get_profile(hulk_ctx *c, const char *kernel, uint64_t *launches, double
     int which = 0;
     if (kernel && strcmp(kernel, "k_minimizer_fast") == 0) which = 1;
     else if (kernel && strcmp(kernel, "k_jump_bin") == 0) which = 2;
-    else if (kernel && strcmp(kernel, "k_jump_left") == 0) which = 3;
+    else if (kernel && strcmp(kernel, "k_jump_left") == 0) which = 3;      // gone (its chains are pooled inside k_jump_bin): a valid name with zero launches
     else if (kernel && strcmp(kernel, "k_cmsd_freq") == 0) which = 4;
     else if (kernel && strcmp(kernel, "k_cws_scan") != 0)
         return fail(c, HULK_ERR_ARG, "instrumented kernels: k_cws_scan, k_minimizer_fast, k_jump_bin, k_jump_left, k_cmsd_freq");

@@ -41,7 +41,7 @@ static inline hipError_t poison_host_malloc(void **p, size_t n, unsigned flags) 
 namespace hulk {
 constexpr uint64_t MAX_READS_PER_LAUNCH = 4u << 20;   // 4 Mi reads -> <= ~7 GB of minimizer list at w = 9
 struct ProfMark { hipEvent_t e; const char *kernel; hipStream_t s; };   // hulk_set_profiling bit 32 (prof_mark)
-struct ProfileRec { hipEvent_t a, b; int which; };   // which: 0 = k_cws_scan, 1 = k_minimizer_fast, 2 = k_jump_bin, 3 = k_jump_left, 4 = k_cmsd_freq
+struct ProfileRec { hipEvent_t a, b; int which; };   // which: 0 = k_cws_scan, 1 = k_minimizer_fast, 2 = k_jump_bin, 4 = k_cmsd_freq (3 was k_jump_left: no records)
 }  // namespace hulk
 
 struct hulk_ctx {
@@ -177,7 +177,7 @@ struct hulk_ctx {
     bool tables_ready = false, finished = false, hist_hook_used = false;
     int sticky = HULK_OK;
     std::string last_error;
-    int profiling = 0;   /* bit 0 k_cws_scan, bit 1 k_minimizer_fast, bit 2 k_jump_bin + k_jump_left, bit 3 k_cmsd_freq (hulk_set_profiling) */
+    int profiling = 0;   /* bit 0 k_cws_scan, bit 1 k_minimizer_fast, bit 2 k_jump_bin, bit 3 k_cmsd_freq (hulk_set_profiling) */
     std::vector<hulk::ProfileRec> prof;
     std::vector<hulk::ProfMark> marks;
 };

@@ -39,7 +39,7 @@ uint32_t *ring_hist(hulk_ctx *c) { return c->d_hist + (size_t)c->cur_ring * (siz
 // The work lane of spectrum ring r.  With two lanes (hulk_params.work_lanes, the default) every launch that touches ring r —
 // binning, the deferred reads' generic kernel, the test hook — runs on lane r's stream, so consecutive batches, which
 // alternate between the rings, alternate between two streams and are NOT ordered against each other: batch n+1's
-// k_minimizer_fast (VALU + LDS, 5 waves per SIMD) runs beside batch n's k_jump_bin / k_jump_left / spectrum kernels (tails,
+// k_minimizer_fast (VALU + LDS, 5 waves per SIMD) runs beside batch n's k_jump_bin / spectrum kernels (tails,
 // low occupancy) and the two fill each other's issue bubbles — what two independent contexts fed alternately measured as
 // +11 % (tools/archive/two_ctx_overlap.py).  Lane 0 is the context's stream, lane 1 a stream of its own (same priority).
 hipStream_t lane_stream(hulk_ctx *c, int ring) {
@@ -207,7 +207,7 @@ static int lane_reserve(hulk_ctx *c, hulk_ctx::BinLane &ln, hipStream_t s, uint6
     if (regions > ln.ml_regions || ml.rcap != rcap) {
         HIPCHK(c, hipStreamSynchronize(s));
         hipFree(ml.x); hipFree(ml.slot); hipFree(ml.key); hipFree(ml.cnt); hipFree(ml.off); hipFree(ml.bsum);
-        hipFree(ml.lo); hipFree(ml.lo_cnt); hipFree(ml.dmask); hipFree(ml.dsum);
+        hipFree(ml.dmask); hipFree(ml.dsum);
         uint32_t *keep_partial = ml.partial; const uint32_t keep_parts = ml.max_parts;
         uint32_t *keep_nib = ml.nib, *keep_over = ml.nib_over; const uint32_t keep_np = ml.nib_parts;
         ml = MinimizerList{}; ln.ml_regions = 0;
@@ -220,8 +220,6 @@ static int lane_reserve(hulk_ctx *c, hulk_ctx::BinLane &ln, hipStream_t s, uint6
         HIPCHK(c, hipMalloc((void **)&ml.cnt, cap * 4));
         HIPCHK(c, hipMalloc((void **)&ml.off, (cap + 1) * 4));
         HIPCHK(c, hipMalloc((void **)&ml.bsum, (cap / 1024 + 2) * 4));
-        HIPCHK(c, hipMalloc((void **)&ml.lo, cap * JUMP_LO_CAP * sizeof(uint4)));
-        HIPCHK(c, hipMalloc((void **)&ml.lo_cnt, cap * 4));
         HIPCHK(c, hipMalloc((void **)&ml.dmask, cap * 4));
         HIPCHK(c, hipMalloc((void **)&ml.dsum, (cap / 1024 + 2) * 4));
         if (!ml.nib) {
@@ -241,7 +239,7 @@ static int lane_reserve(hulk_ctx *c, hulk_ctx::BinLane &ln, hipStream_t s, uint6
 }
 
 // A launch chain of the short-read kernels on stream s with lane ln's buffers: k_minimizer_fast -> region scan ->
-// k_jump_bin / k_jump_left -> spectrum kernels -> the generic kernel over the reads the fast one deferred.
+// k_jump_bin -> spectrum kernels -> the generic kernel over the reads the fast one deferred.
 // spectra_gate (may be null): the flush that last read this ring — only the histogram kernels wait for it (the minimizer
 // and jump-hash kernels do not touch the spectra)
 static int bin_fast(hulk_ctx *c, hulk_ctx::BinLane &ln, hipStream_t s, const uint8_t *d_bases, const uint64_t *d_offsets,
@@ -280,13 +278,11 @@ static int bin_fast(hulk_ctx *c, hulk_ctx::BinLane &ln, hipStream_t s, const uin
         c->stagger = 2;
     }
     ProfileRec pj{}; pj.which = 2;
-    ProfileRec pl{}; pl.which = 3;
     if ((c->profiling & 4)) {
         HIPCHK(c, hipEventCreateWithFlags(&pj.a, PROFILE_EVENT_FLAGS)); HIPCHK(c, hipEventCreateWithFlags(&pj.b, PROFILE_EVENT_FLAGS));
-        HIPCHK(c, hipEventCreateWithFlags(&pl.a, PROFILE_EVENT_FLAGS)); HIPCHK(c, hipEventCreateWithFlags(&pl.b, PROFILE_EVENT_FLAGS));
     }
-    HIPCHK(c, launch_minimizer_post(s, n, P, ln.ml, hist, ln.d_slow_list, ln.d_slow_count, pj.a, pj.b, spectra_gate, pl.a, pl.b));
-    if ((c->profiling & 4)) { c->prof.push_back(pj); c->prof.push_back(pl); }
+    HIPCHK(c, launch_minimizer_post(s, n, P, ln.ml, hist, ln.d_slow_list, ln.d_slow_count, pj.a, pj.b, spectra_gate));
+    if ((c->profiling & 4)) c->prof.push_back(pj);
     int threads = 256;
     pick_config(c->p.k, max_len, P, threads);      // (the fast path implies max_len <= 512: always fits)
     // the list is normally empty or short; its length is only known on the device, so the grid is fixed: enough
@@ -325,7 +321,7 @@ static int lane_open(hulk_ctx *c, int li) {
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     return HULK_OK;
 }
-// hulk_create: the work lanes' buffers (minimizer list, hand-over areas, 4-bit histogram parts: ~3 GB per lane at the
+// hulk_create: the work lanes' buffers (minimizer list, 4-bit histogram parts: ~3 GB per lane at the
 // defaults) sized for the largest batch the interval rule hands to bin_reads, so that no call of the stream allocates.
 // (hipMalloc in the middle of a stream was measured at anything between 0.1 ms and 1.8 SECONDS, depending on what the
 // process freed before: profiles/r04_bench_ramp.txt.)  Without an interval a call may be of any size: the first one sizes

@@ -47,7 +47,6 @@ struct FlushBatch {
 
 // Minimizer list written by k_minimizer_fast: one region of `rcap` entries per wave (16 reads).
 constexpr int FAST_READS_PER_WAVE = 16;
-constexpr int JUMP_LO_CAP = 64;        // unfinished chains a region may hand to k_jump_left (one round of a wave)
 struct MinimizerList {
     uint64_t *x;        // [regions][rcap] distinct minimizer values
     uint8_t *slot;      // [regions][rcap] spectrum (ring slot) of the read each value came from
@@ -59,8 +58,6 @@ struct MinimizerList {
     uint32_t *bsum;     // [regions / 1024 + 1] per-block sums for the prefix
     uint32_t *partial;  // [max_parts][ring_n][num_bins] per-part spectra of k_range_hist
     uint32_t max_parts;
-    uint4 *lo;          // [regions][JUMP_LO_CAP] unfinished jump chains of k_jump_bin: {key lo, key hi, float-as-int t, idx | slot << 16}
-    uint32_t *lo_cnt;   // [regions]
     uint32_t *nib;      // [nib_parts][ring_n][nranges][NIB_WORDS] per-part spectra of k_nibble_hist, 8 four-bit counters per word
     uint32_t *nib_over; // [RING_MAX] a 4-bit counter overflowed in this spectrum: k_range_hist recounts it
     uint32_t nib_parts;
@@ -125,8 +122,7 @@ hipError_t launch_minimizer_fast(hipStream_t s, const uint8_t *d_bases, const ui
 hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParams P, const MinimizerList &ml,
                                  uint32_t *d_hists, uint32_t *d_slow_list, uint32_t *d_slow_count,
                                  hipEvent_t jump_begin = nullptr, hipEvent_t jump_end = nullptr,
-                                 hipEvent_t wait_before_spectra = nullptr, hipEvent_t left_begin = nullptr,
-                                 hipEvent_t left_end = nullptr);
+                                 hipEvent_t wait_before_spectra = nullptr);
 uint32_t minimizer_list_rcap(uint32_t w, bool pair);
 hipError_t launch_long_group(hipStream_t s, const uint8_t *d_bases, const LongSeqDesc *d_desc, uint32_t n_seqs,
                              uint64_t max_npos, MinimizerParams P, uint64_t *d_xs, uint8_t *d_valid, uint64_t *d_table,

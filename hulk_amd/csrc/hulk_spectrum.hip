@@ -1,5 +1,5 @@
 // hulk_spectrum.hip — minimizer list -> k-mer spectrum (reference: src/kmerspectrum/kmerspectrum.go:67-81, go-jump).
-//   K1b k_jump_bin / k_jump_left   jump hash of the list (exact fp64 reciprocal, assembly step loop)
+//   K1b k_jump_bin   jump hash of the list (exact fp64 reciprocal, assembly step loop)
 //   K1c k_nibble_hist/k_nibble_merge, k_range_hist/k_merge_hist   spectrum in LDS, no global atomics
 #include "hulk_device.h"
 
@@ -11,9 +11,10 @@ namespace hulk {
 namespace {
 
 // ------------------------------------------------------------------------------------------
-// K1b: jump hash of the minimizer list.  One wave per region; lanes take the region's values
-// round-robin (lane l: l, l+64, ...) with the next value prefetched, so every lane stays busy
-// with its own chain of ~ln(k^4) fp64 steps (no lock-step tail per 64 values); 8 waves/SIMD.
+// K1b: jump hash of the minimizer list.  A wave takes a few regions, one after the other; lanes take a
+// region's values round-robin (lane l: l, l+64, ...) with the next value prefetched, so every lane stays busy
+// with its own chain of ~ln(k^4) fp64 steps; the slowest chains of a round are pooled per wave and run
+// again densely (no lock-step tail per 64 values); no LDS, 8 waves/SIMD.
 // Output: key = spectrum slot << 20 | bin  (k^4 < 2^20 for k <= 31).
 // ------------------------------------------------------------------------------------------
 // The step loop of the jump kernels in assembly (fixed registers v40..v58, s60..s63): hipcc's version of the same loop
@@ -28,7 +29,7 @@ namespace {
 // Lanes that reach p >= n leave the exec mask and keep their t.  The loop ends when at most `cut`
 // lanes are still running (cut = 0: when none is): chains take 12.8 +- 3.5 steps, so the last few lanes of a round
 // of 64 would keep the whole wave busy for ~24 — they are handed over instead (`left` = their mask, key/t = their
-// state at a step boundary) and finished by k_jump_left in a denser wave.
+// state at a step boundary) and finished in a denser round of the wave's pool (below).
 // p >= n is tested on the upper dwords alone: p is a non-negative finite double and n < 2^20 is an integer whose
 // double has a zero lower dword, so bits(p) >= bits(n) <=> hi(p) >= hi(n)  (v_cmp_lt_u32 instead of v_cmp_nge_f64).
 __device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, double fn, double t0, uint32_t cut,
@@ -94,81 +95,116 @@ __device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, d
     return __longlong_as_double((long long)(((uint64_t)thi << 32) | tlo));
 }
 
-__global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_regions, int32_t num_bins, int use_c,
-                                                  uint32_t cut) {
-    const int lane = lane_id();
-    const uint32_t region = (uint32_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (region >= n_regions) return;
-    const uint32_t cnt = ml.cnt[region];
-    const uint64_t *xl = ml.x + (size_t)region * ml.rcap;
-    const uint8_t *sl = ml.slot + (size_t)region * ml.rcap;
-    uint32_t *kl = ml.key + ml.off[region];                   // dense: regions back to back
-    uint4 *lo = ml.lo + (size_t)region * JUMP_LO_CAP;
-    uint32_t nleft = 0;                                        // wave-uniform: chains handed to k_jump_left so far
-    uint32_t idx = (uint32_t)lane;
-    uint64_t nx = 0; uint32_t ns = 0;
-    if (idx < cnt) { nx = xl[idx]; ns = sl[idx]; }
-    const double fn = (double)num_bins;
-    while (idx < cnt) {
-        uint64_t key = nx; const uint32_t slot = ns;
-        const uint32_t nidx = idx + 64;
-        if (nidx < cnt) { nx = xl[nidx]; ns = sl[nidx]; }      // prefetch the lane's next value
-        // Literally the reference's step: j = int64(float64(b+1) * (float64(1<<31) / float64(r))).  float64(b) = t is
-        // carried; (t + 1) * q is ONE fma(t, q, q) — the exact product rounded once, as the multiplication is —
-        // so a step needs no add and no ldexp.
-        double t = 0.0;                                         // float64(b), b = 0 before the first step
-        if (!use_c) {
-            uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-            unsigned long long left = 0;
-            t = jump_steps_asm(klo, khi, fn, 0.0, cut, left);
-            const bool mine = (left >> lane) & 1ull;            // this lane's chain is not finished
-            if (left) {
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(left >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)left, 0u));
-                const uint32_t pos = nleft + rank;
-                bool stored = false;
-                if (mine && pos < (uint32_t)JUMP_LO_CAP) {
-                    lo[pos] = make_uint4(klo, khi, (uint32_t)(int32_t)t, idx | (slot << 16));
-                    stored = true;
-                }
-                const unsigned long long spill = __ballot(mine && !stored);
-                if (spill) {                                    // the region's hand-over area is full: finish here
-                    if (mine && !stored) { unsigned long long none; t = jump_steps_asm(klo, khi, fn, t, 0u, none); }
-                }
-                nleft += (uint32_t)__popcll(left);
-                if (mine && stored) { idx = nidx; continue; }
-            }
-        } else
-        for (;;) {
-            key = key * 2862933555777941757ull + 1;
-            double q = quot31_exact((uint32_t)(key >> 33) + 1u);
-            double p = __builtin_fma(t, q, q);
-            if (p >= fn) break;                                 // j >= n: t is the bucket
-            t = __builtin_trunc(p);                             // j = int64(p): exact, < 2^31
-            key = key * 2862933555777941757ull + 1;
-            q = quot31_exact((uint32_t)(key >> 33) + 1u);
-            p = __builtin_fma(t, q, q);
-            if (p >= fn) break;
-            t = __builtin_trunc(p);
-        }
-        const int32_t res = (int32_t)t;
-        kl[idx] = (slot << 20) | (uint32_t)res;
-        idx = nidx;
+// The pool: the slow chains of a wave, kept in four registers per lane — {key lo, key hi, slot << 20 | t, index into ml.key} in
+// pool position = lane, positions [0, pc) in use, pc wave-uniform.  The index is global and the slot travels with the entry, so
+// one pool holds chains of several regions and spectra; the third word is the output word once the chain has ended.
+// Chains change lanes with ds_permute_b32: it goes through the LDS crossbar and allocates no LDS.  Only lanes in EXEC send or
+// receive, so every move below is a true permutation of all 64 lanes, made in wave-uniform control flow.
+__device__ __forceinline__ void permute4(uint32_t dest, uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) {
+    const int addr = (int)(dest << 2);
+    a = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)a);
+    b = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)b);
+    c = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)c);
+    d = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)d);
+}
+__device__ __forceinline__ uint32_t rank_in(unsigned long long m) {       // set bits of m below this lane
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+constexpr int JUMP_CUT_DEFAULT = 24, JUMP_PCUT_DEFAULT = 32, JUMP_REGIONS_DEFAULT = 4;     // swept: profiles/k1b_pool.md
+struct JumpPool { uint32_t klo, khi, word, at, pc; };
+
+// the chains of the lanes in m (pc + popcount(m) <= 64) go to pool positions pc, pc + 1, ... in lane order; the other lanes
+// take the remaining positions, whose owners keep what they had
+__device__ __forceinline__ void pool_push(JumpPool &p, unsigned long long m, uint32_t klo, uint32_t khi, uint32_t word, uint32_t at,
+                                          int lane) {
+    const uint32_t n = (uint32_t)__popcll(m), rank = rank_in(m), others = (uint32_t)lane - rank;
+    const uint32_t dest = ((m >> lane) & 1ull) ? p.pc + rank : (others < p.pc ? others : others + n);
+    permute4(dest, klo, khi, word, at);
+    if ((uint32_t)lane - p.pc < n) { p.klo = klo; p.khi = khi; p.word = word; p.at = at; }
+    p.pc += n;
+}
+// one dense round over the pool: runs until at most pcut of its chains are live, stores the keys of those that ended and
+// moves the survivors to the front
+__device__ __forceinline__ void pool_round(JumpPool &p, uint32_t *__restrict__ key, double fn, uint32_t pcut, int lane) {
+    bool live = false;
+    if ((uint32_t)lane < p.pc) {
+        unsigned long long left = 0;
+        const double t = jump_steps_asm(p.klo, p.khi, fn, (double)(int32_t)(p.word & 0xFFFFFu), pcut, left);
+        live = (left >> lane) & 1ull;
+        p.word = (p.word & ~0xFFFFFu) | (uint32_t)(int32_t)t;
+        if (!live) key[p.at] = p.word;
     }
-    if (lane == 0) ml.lo_cnt[region] = nleft < (uint32_t)JUMP_LO_CAP ? nleft : (uint32_t)JUMP_LO_CAP;
+    const unsigned long long m = __ballot(live);
+    const uint32_t n = (uint32_t)__popcll(m);
+    if (m) {
+        const uint32_t rank = rank_in(m);
+        permute4(live ? rank : n + (uint32_t)lane - rank, p.klo, p.khi, p.word, p.at);
+    }
+    p.pc = n;
 }
 
-// finishes the chains k_jump_bin handed over: one wave per region, at most one round
-__global__ __launch_bounds__(256) void k_jump_left(MinimizerList ml, uint32_t n_regions, int32_t num_bins) {
+// A wave owns R consecutive regions (wave v: [R v, R v + R)).  Main rounds of 64 values end when <= cut chains are live; those
+// go to the wave's pool.  A hand-over that would take the pool past 64 fills it to 64, runs a pool round (survivors <= pcut)
+// and then hands over the rest, whose state is still in the senders' own registers: cut + pcut <= 64, so it fits.  After its
+// last region the wave drains the pool.  cut == 0 (and the C++ loop, use_c): every round runs to its last chain, no pool.
+__global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_regions, int32_t num_bins, int use_c,
+                                                  uint32_t cut, uint32_t pcut, uint32_t R) {
     const int lane = lane_id();
-    const uint32_t region = (uint32_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (region >= n_regions) return;
-    const uint32_t n = ml.lo_cnt[region];
-    if ((uint32_t)lane >= n) return;
-    const uint4 st = ml.lo[(size_t)region * JUMP_LO_CAP + lane];
-    uint32_t klo = st.x, khi = st.y;
-    unsigned long long none;
-    const double t = jump_steps_asm(klo, khi, (double)num_bins, (double)(int32_t)st.z, 0u, none);
-    ml.key[ml.off[region] + (st.w & 0xffffu)] = ((st.w >> 16) << 20) | (uint32_t)(int32_t)t;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const uint32_t r0 = wave * R;
+    if (r0 >= n_regions) return;
+    const uint32_t r1 = n_regions - r0 < R ? n_regions : r0 + R;
+    const double fn = (double)num_bins;
+    JumpPool pool{0u, 0u, 0u, 0u, 0u};
+    for (uint32_t region = r0; region < r1; region++) {
+        const uint32_t cnt = ml.cnt[region];
+        const uint64_t *xl = ml.x + (size_t)region * ml.rcap;
+        const uint8_t *sl = ml.slot + (size_t)region * ml.rcap;
+        const uint32_t base = ml.off[region];                     // dense: regions back to back
+        uint64_t nx = 0; uint32_t ns = 0;
+        if ((uint32_t)lane < cnt) { nx = xl[lane]; ns = sl[lane]; }
+        for (uint32_t first = 0; first < cnt; first += 64) {      // wave-uniform: lane 0 is active in every round
+            const uint32_t idx = first + (uint32_t)lane;
+            const uint64_t key = nx;
+            uint32_t word = ns << 20;
+            if (idx + 64 < cnt) { nx = xl[idx + 64]; ns = sl[idx + 64]; }      // prefetch the lane's next value
+            uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
+            bool mine = false;                                     // this lane's chain is not finished
+            if (idx < cnt) {
+                // Literally the reference's step: j = int64(float64(b+1) * (float64(1<<31) / float64(r))).  float64(b) = t is
+                // carried; (t + 1) * q is ONE fma(t, q, q) — the exact product rounded once, as the multiplication is —
+                // so a step needs no add and no ldexp.
+                double t = 0.0;                                     // float64(b), b = 0 before the first step
+                if (!use_c) {
+                    unsigned long long left = 0;
+                    t = jump_steps_asm(klo, khi, fn, 0.0, cut, left);
+                    mine = (left >> lane) & 1ull;
+                } else {
+                    uint64_t kk = key;
+                    for (;;) {
+                        kk = kk * 2862933555777941757ull + 1;
+                        const double q = quot31_exact((uint32_t)(kk >> 33) + 1u);
+                        const double p = __builtin_fma(t, q, q);
+                        if (p >= fn) break;                         // j >= n: t is the bucket
+                        t = __builtin_trunc(p);                     // j = int64(p): exact, < 2^31
+                    }
+                }
+                word |= (uint32_t)(int32_t)t;
+                if (!mine) ml.key[base + idx] = word;
+            }
+            unsigned long long send = __ballot(mine);
+            if (send) {
+                if (pool.pc + (uint32_t)__popcll(send) > 64u) {
+                    const unsigned long long head = __ballot(mine && rank_in(send) < 64u - pool.pc);
+                    if (head) pool_push(pool, head, klo, khi, word, base + idx, lane);
+                    pool_round(pool, ml.key, fn, pcut, lane);
+                    send &= ~head;
+                }
+                pool_push(pool, send, klo, khi, word, base + idx, lane);
+            }
+        }
+    }
+    while (pool.pc) pool_round(pool, ml.key, fn, 0u, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -470,7 +506,7 @@ __global__ void k_add_hist(uint32_t *hist, const uint32_t *add, int32_t n) {
 // K1b: jump hash of the list (dense key array); K1c: spectrum ranges in LDS, merged without atomics
 hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParams P, const MinimizerList &ml,
                                  uint32_t *d_hists, uint32_t *d_slow_list, uint32_t *d_slow_count, hipEvent_t jump_begin,
-                                 hipEvent_t jump_end, hipEvent_t wait_before_spectra, hipEvent_t left_begin, hipEvent_t left_end) {
+                                 hipEvent_t jump_end, hipEvent_t wait_before_spectra) {
     if (n_reads == 0) return hipSuccess;
     hipError_t e = hipSuccess;
     const uint32_t n_regions = (uint32_t)((n_reads + FAST_READS_PER_WAVE - 1) / FAST_READS_PER_WAVE);
@@ -486,16 +522,21 @@ hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParam
     if (jump_lds < 0) { const char *e = HULK_EXP_ENV("HULK_JUMP_LDS"); jump_lds = e ? atoi(e) : 0; }
     static int jump_c = -1;
     if (jump_c < 0) { const char *ec = HULK_EXP_ENV("HULK_JUMP_C"); jump_c = ec ? atoi(ec) : 0; }
+    // cut / pcut / R: swept on the profiling build (profiles/k1b_pool.md)
     static int jump_cut = -1;
-    if (jump_cut < 0) { const char *ec = HULK_EXP_ENV("HULK_JUMP_CUT"); jump_cut = ec ? atoi(ec) : 10; }
-    const uint32_t cut = (jump_c || !ml.lo) ? 0u : (uint32_t)jump_cut;
-    if (jump_begin) { e = hipEventRecord(jump_begin, s); if (e != hipSuccess) return e; }      // bench.py: k_jump_bin alone ...
+    if (jump_cut < 0) { const char *ec = HULK_EXP_ENV("HULK_JUMP_CUT"); jump_cut = ec ? atoi(ec) : JUMP_CUT_DEFAULT; if (jump_cut < 0) jump_cut = 0; if (jump_cut > 63) jump_cut = 63; }
+    static int jump_pcut = -1;
+    if (jump_pcut < 0) { const char *ec = HULK_EXP_ENV("HULK_JUMP_PCUT"); jump_pcut = ec ? atoi(ec) : JUMP_PCUT_DEFAULT; }
+    static int jump_regions = -1;
+    if (jump_regions < 0) { const char *ec = HULK_EXP_ENV("HULK_JUMP_REGIONS"); jump_regions = ec ? atoi(ec) : JUMP_REGIONS_DEFAULT; if (jump_regions < 1) jump_regions = 1; if (jump_regions > 64) jump_regions = 64; }
+    const uint32_t cut = jump_c ? 0u : (uint32_t)jump_cut;
+    const uint32_t pcut = std::min<uint32_t>((uint32_t)std::max(jump_pcut, 0), 64u - cut);     // cut + pcut <= 64: see the kernel
+    const uint32_t R = (uint32_t)jump_regions;
+    if (jump_begin) { e = hipEventRecord(jump_begin, s); if (e != hipSuccess) return e; }      // bench.py: k_jump_bin alone
     prof_mark(s, "k_jump_bin");
-    hipLaunchKernelGGL(k_jump_bin, dim3((n_regions + 3) / 4), dim3(256), (size_t)jump_lds, s, ml, n_regions, P.num_bins, jump_c, cut);
+    hipLaunchKernelGGL(k_jump_bin, dim3((n_regions + 4 * R - 1) / (4 * R)), dim3(256), (size_t)jump_lds, s, ml, n_regions, P.num_bins, jump_c,
+                       cut, pcut, R);
     if (jump_end) { e = hipEventRecord(jump_end, s); if (e != hipSuccess) return e; }
-    if (left_begin) { e = hipEventRecord(left_begin, s); if (e != hipSuccess) return e; }      // ... and k_jump_left alone
-    if (cut) { prof_mark(s, "k_jump_left"); hipLaunchKernelGGL(k_jump_left, dim3((n_regions + 3) / 4), dim3(256), 0, s, ml, n_regions, P.num_bins); }
-    if (left_end) { e = hipEventRecord(left_end, s); if (e != hipSuccess) return e; }
     // the kernels below write the spectra of the ring: the flush that last read them has to be done
     if (wait_before_spectra) { e = hipStreamWaitEvent(s, wait_before_spectra, 0); if (e != hipSuccess) return e; }
     const uint32_t n_spectra = P.interval ? (uint32_t)((P.fill + n_reads + P.interval - 1) / P.interval) : 1u;

@@ -580,9 +580,11 @@ int hulk_selftest_reciprocal(hulk_ctx *ctx, uint64_t *mismatches);
 int hulk_get_scan_stats(hulk_ctx *ctx, uint64_t *tiles_visited, uint64_t *tiles_total);
 
 /* Per-kernel timing for bench.py: when enabled, hipEvents bracket every launch of the heavy kernels
- * ("k_minimizer_fast", "k_jump_bin", "k_jump_left", "k_cws_scan", "k_cmsd_freq"; each alone) on the stream they are launched on.
- * enabled: 0 off, 1 all of them, otherwise a mask (2 k_minimizer_fast, 4 k_jump_bin and k_jump_left, 8 k_cws_scan, 16 k_cmsd_freq,
+ * ("k_minimizer_fast", "k_jump_bin", "k_cws_scan", "k_cmsd_freq"; each alone) on the stream they are launched on.
+ * enabled: 0 off, 1 all of them, otherwise a mask (2 k_minimizer_fast, 4 k_jump_bin, 8 k_cws_scan, 16 k_cmsd_freq,
  * 32 every launch: hulk_get_profile_table)
+ * "k_jump_left" stays a valid name for hulk_get_profile (ABI 4): that kernel is gone, its chains are finished inside k_jump_bin,
+ * so it reports zero launches and 0 ms.
  * — every bracketed launch costs the stream two event records (~3 % of a C2 step for all of them), so the timed pass of
  * bench.py brackets nothing and the durations come from a separate pass. */
 int hulk_set_profiling(hulk_ctx *ctx, int enabled);
