@@ -118,7 +118,7 @@ int hulk_create(const hulk_params *params, hulk_ctx **out) {
     if (!strstr(prop.gcnArchName, "gfx950"))
         return fail(nullptr, HULK_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName);
 
-    fq_sweep_idle();                                             // (the device FASTQ parser's pooled buffers: hulk_ingest.hip)
+    fq_sweep_idle();                                             // (the device FASTQ parser's pooled buffers: hulk_ingest_device.hip)
     hulk_ctx *c = new hulk_ctx();
     c->p = p; c->B = (int32_t)bins; c->S = p.sketch_size; c->slot_begin = p.slot_begin; c->slots = p.slot_count;
     c->drift = p.decay_ratio != 1.0;
@@ -331,9 +331,9 @@ int hulk_set_cws_tables(hulk_ctx *c, const double *r, const double *cc, const do
 
 }  // extern "C"
 
-extern "C" {
-int hulk_add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n,
-                          uint32_t max_read_len, uint64_t bases_bytes) {
+namespace hulk {
+int add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n, uint32_t max_read_len,
+                     uint64_t bases_bytes, const uint64_t *h_off) {
     if (!c) return HULK_ERR_ARG;
     if (c->snap.fn_failed) return fail(c, HULK_ERR_STATE, "snapshot callback failed");   // (the callback ended the run)
     if (c->finished) return fail(c, HULK_ERR_STATE, "context already finished");
@@ -341,8 +341,6 @@ int hulk_add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d
     if (n && (!d_bases || !d_offsets)) return fail(c, HULK_ERR_ARG, "NULL buffer");
     const uint64_t I = c->p.interval;
     uint64_t pos = 0;
-    const uint64_t *h_off = c->h_off_hint;                         // (ctx_hint_host_offsets: for this call only)
-    c->h_off_hint = nullptr;
     struct Clear { hulk_ctx *c; ~Clear() { c->h_off_chunk = nullptr; } } clear_hint{c};
     while (pos < n) {
         c->h_off_chunk = h_off ? h_off + pos : nullptr;
@@ -364,6 +362,13 @@ int hulk_add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d
         if (c->snap.has_fn()) { rc = snap_deliver(c, false); if (rc != HULK_OK) return rc; }     // (event queries: snapshots of flushes that have run)
     }
     return HULK_OK;
+}
+}  // namespace hulk
+
+extern "C" {
+int hulk_add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n,
+                          uint32_t max_read_len, uint64_t bases_bytes) {
+    return hulk::add_reads_device(c, d_bases, d_offsets, n, max_read_len, bases_bytes, nullptr);
 }
 
 int hulk_bin_reads_device_at(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n,
@@ -443,8 +448,7 @@ int hulk_add_reads(hulk_ctx *c, const uint8_t *bases, const uint64_t *offsets, u
         hulk_ctx::HostStage *hsp = nullptr;
         { const int rcs = stage_host_reads(c, bases, offsets, i0, i1, &hsp); if (rcs != HULK_OK) return rcs; }
         hulk_ctx::HostStage &hs = *hsp;
-        ctx_hint_host_offsets(c, hs.h_off);                         // (the long-sequence path reads the lengths here)
-        const int rc = hulk_add_reads_device(c, hs.d_bases, hs.d_off, cn, (uint32_t)cmax, hs.cap_bases);
+        const int rc = add_reads_device(c, hs.d_bases, hs.d_off, cn, (uint32_t)cmax, hs.cap_bases, hs.h_off);   // (the long-sequence path reads the lengths there)
         if (rc != HULK_OK) return rc;
         { const int rcb = stage_mark_busy(c, hs); if (rcb != HULK_OK) return rcb; }
         i0 = i1;

@@ -139,10 +139,10 @@ struct hulk_ctx {
     // the descriptors and the set tables on the device are ONE set per context: a group queued on one work lane waits for the group
     // queued before it on the other (the kernels of a group fill the chip: nothing is lost)
     hipEvent_t ev_long = nullptr; hipStream_t long_last_stream = nullptr; bool long_pending = false;
-    // A caller that holds the batch's offsets in host memory says so (ctx_hint_host_offsets): the long-sequence path then reads the
-    // lengths there instead of fetching them from the device behind everything queued on the lane.  Valid for the next
-    // hulk_add_reads_device only; h_off_chunk is that call's current piece.
-    const uint64_t *h_off_hint = nullptr, *h_off_chunk = nullptr;
+    // A caller that holds the batch's offsets in host memory passes them to add_reads_device (h_offsets): the long-sequence path
+    // then reads the lengths there instead of fetching them from the device behind everything queued on the lane.  h_off_chunk is
+    // the running call's current piece of them (nullptr outside a call, or when the caller has none).
+    const uint64_t *h_off_chunk = nullptr;
     uint64_t long_cap = 0, long_table_cap = 0;   // minimizer list of the short-read kernel (grow-only)
     // hulk_set_snapshots: the sketch as it stands after a flushed spectrum, recorded by the flush kernels themselves into a device
     // ring (hulk_snapshot.hip).  every == 0: the context records none, allocates none of this and launches what it always did.

@@ -1,4 +1,4 @@
-// hulk_fastq.h — the device FASTQ parser's interface between its kernels (hulk_fastq.hip) and the ingest (hulk_ingest.hip).
+// hulk_fastq.h — the device FASTQ parser's interface between its kernels (hulk_fastq.hip) and the ingest (hulk_ingest_device.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -21,7 +21,7 @@
 // What the device does NOT decide (FASTQ): anything the reference turns into an error or that outgrows the fixed buffers — a header
 // line that does not begin with '@' (seqio.go:38-40), a line of 64 KiB or more (bufio.Scanner: token too long), more lines
 // than the index holds, a tail longer than the porch.  The block is then flagged `need_host` and the host parser
-// (hulk_ingest.hip, the comparator of tools/fuzz_ingest.py) takes the stream over from the last record boundary, with the
+// (hulk_ingest_host.hip, the comparator of tools/fuzz_ingest.py) takes the stream over from the last record boundary, with the
 // reference's messages and their order.
 #include "hulk_fastq.h"
 

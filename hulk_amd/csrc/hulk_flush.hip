@@ -99,7 +99,7 @@ bool pick_config(uint32_t k, uint32_t max_len, MinimizerParams &P, int &threads)
 // sequences with more than GENERIC_XCAP_MAX k-mer positions: grouped launches of the long-sequence kernels
 int bin_long_reads(hulk_ctx *c, hipStream_t s, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n, MinimizerParams P,
                    uint32_t *hist, const uint64_t *h_offsets) {
-    // the lengths: from the caller's host copy of the offsets when there is one (ctx_hint_host_offsets), else fetched from the
+    // the lengths: from the caller's host copy of the offsets when there is one (add_reads_device's h_offsets), else fetched from the
     // device — which waits for everything queued on the lane before
     std::vector<uint64_t> fetched;
     const uint64_t *off = h_offsets;
@@ -517,7 +517,7 @@ int check_device_error(hulk_ctx *c) {
 }
 
 
-// internal accessors for hulk_ingest.hip (not part of the ABI)
+// internal accessors for hulk_ingest_device.hip (not part of the ABI)
 hipStream_t ctx_stream(hulk_ctx *c) { return c->stream; }
 uint64_t ctx_min_read_len(const hulk_ctx *c) { return (uint64_t)c->p.w + c->p.k - 1; }
 int ctx_fail(hulk_ctx *c, int code, const char *full_message) {
@@ -609,7 +609,6 @@ int ctx_stage_acquire(hulk_ctx *c, size_t nbytes, uint64_t n, StageSet *out) {
     return HULK_OK;
 }
 int ctx_device(const hulk_ctx *c) { return c->p.device; }
-void ctx_hint_host_offsets(hulk_ctx *c, const uint64_t *h_offsets) { c->h_off_hint = h_offsets; }
 int ctx_wait_event(hulk_ctx *c, hipEvent_t e) {
     HIPCHK(c, hipStreamWaitEvent(c->stream, e, 0));
     c->copies_pending = true;                                   // (lane 1 is told through the fork in front of its next batch)

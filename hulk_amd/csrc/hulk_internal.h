@@ -7,7 +7,7 @@
 // Experiment switches (HULK_JUMP_*, HULK_NIB_*, HULK_NO_FMIN, HULK_K1_DEBUG, HULK_POISON, the HULK_NO_* / HULK_BATCH overrides
 // of hulk_params fields ... docs/EXPERIMENTS.md) exist only in the profiling build, `make EXPERIMENTS=1` ->
 // libhulkhip_exp.so (tools/ select it with HULK_LIB).  The shipping library reads the environment in two places only:
-// HULK_RCCL_LIB (which RCCL to bind) and the ingest overrides of hulk_ingest_opts (hulk_ingest.hip, once per run).
+// HULK_RCCL_LIB (which RCCL to bind) and the ingest overrides of hulk_ingest_opts (hulk_ingest_host.hip, once per run).
 #ifdef HULK_EXPERIMENTS
 #define HULK_EXP_ENV(name) getenv(name)
 #else
@@ -214,7 +214,7 @@ hipError_t launch_add_hist(hipStream_t s, uint32_t *d_hist, const uint32_t *d_ad
 // next mark on the same stream ("-" closes a chain).  Meant for the one-stream mode (HULK_FLAG_NO_OVERLAP): every kernel alone.
 void prof_mark(hipStream_t s, const char *kernel);
 
-// context accessors for hulk_ingest.hip (defined in hulk_flush.hip; not part of the ABI)
+// context accessors for hulk_ingest_device.hip (defined in hulk_flush.hip; not part of the ABI)
 }  // namespace hulk
 struct hulk_ctx;
 namespace hulk {
@@ -229,17 +229,19 @@ int ctx_fail(hulk_ctx *c, int code, const char *full_message);
 struct StageSet { uint8_t *h_bases, *d_bases; uint64_t *h_off, *d_off; size_t cap_bases; };
 int ctx_stage_acquire(hulk_ctx *c, size_t nbytes, uint64_t n, StageSet *out);
 int ctx_stage_release(hulk_ctx *c);
-// for the device FASTQ parser of hulk_sketch_files (hulk_ingest.hip / hulk_fastq.hip)
+// for the device FASTQ parser of hulk_sketch_files (hulk_ingest_device.hip / hulk_fastq.hip)
 int ctx_device(const hulk_ctx *c);
-void fq_release_idle();      // hulk_release_caches: the idle buffer sets of the process (hulk_ingest.hip)
+void fq_release_idle();      // hulk_release_caches: the idle buffer sets of the process (hulk_ingest_device.hip)
 void fq_sweep_idle();        // ... those idle for more than 10 s only (hulk_create / hulk_destroy / hulk_sketch_files)
 // the context's stream waits for `e` (a parse that filled device buffers the next hulk_add_reads_device reads)
 int ctx_wait_event(hulk_ctx *c, hipEvent_t e);
 // record e0 on the context's stream and, if there is a second work lane, e1 on it: both passed = the kernels queued so far
 // have read their inputs.  *has1 says whether e1 was recorded.
 int ctx_record_busy(hulk_ctx *c, hipEvent_t e0, hipEvent_t e1, bool *has1);
-// offsets[0 .. n] of the NEXT hulk_add_reads_device as the caller holds them in host memory (read during that call only): the
-// long-sequence path then takes the lengths from there instead of fetching them from the device behind everything queued
-void ctx_hint_host_offsets(hulk_ctx *c, const uint64_t *h_offsets);
+// hulk_add_reads_device for a caller that also holds offsets[0 .. n] in host memory (h_offsets, read during the call only; nullptr:
+// it does not): the long-sequence path then takes the lengths from there instead of fetching them from the device behind
+// everything queued
+int add_reads_device(hulk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n, uint32_t max_read_len,
+                     uint64_t bases_bytes, const uint64_t *h_offsets);
 
 }  // namespace hulk

@@ -12,7 +12,7 @@
 // non-final dynamic block whose three code sets are complete and whose literal codes are text bytes only (FASTQ / FASTA is
 // text: a block of anything else is simply never found, and the caller falls back to the one-thread reader).  A position that
 // passes is only a CANDIDATE: the caller accepts a chunk's output only if the decoder of the chunk in front of it arrived,
-// at a block boundary, at exactly that bit (hulk_ingest.hip, GzPar) — a false candidate costs time, never correctness.
+// at a block boundary, at exactly that bit (hulk_ingest_gzip.hip, GzPar) — a false candidate costs time, never correctness.
 //
 // A decoder stops in front of the final block (SPEC_FINAL).  The caller may then decode that one block with the window it
 // knows by then (`through_final`) and check the trailer itself, to go on with a member that follows; whenever anything about

@@ -139,6 +139,43 @@ def test_device_parser_host_parser_and_released_caches_agree(tmp_path):
         assert np.array_equal(r[3][0], res[0][3][0]) and np.array_equal(r[3][1], res[0][3][1])
 
 
+def test_host_takes_over_behind_held_blocks(tmp_path, capfd):
+    """A successful take-over by the host parser while the device still holds DEPTH queued blocks.  About seven 128 KiB blocks
+    of clean records, then one record whose header is followed by 1,200,000 empty lines (skipped in slots 0 to 2, so legal)
+    before its sequence: the tail outgrows the device's porch / line index, the device raises need_host, and the host parser
+    finishes the stream from the last record boundary — the held blocks first, then 9,000 more records.  Same reads, lines,
+    sketch and counters as the run that parses on the host from the start, and the line pump's sequences."""
+    from hulk_amd import _lib, synth
+    from oracle import linepump
+    n, L = 12001, 150
+    bases, _ = synth.reads_numpy(7, n, L)
+    raw = bases[:n * L].tobytes()
+
+    def rec(i, gap=b""):
+        return b"@r%d\n" % i + gap + raw[i * L:(i + 1) * L] + b"\n+\n" + b"I" * L + b"\n"
+    p = str(tmp_path / "gap.fq")
+    with open(p, "wb") as fh:
+        fh.write(b"".join(rec(i) for i in range(3000)))
+        fh.write(b"@gap\n" + b"\n" * 1200000 + raw[3000 * L:3001 * L] + b"\n+\n" + b"I" * L + b"\n")
+        fh.write(b"".join(rec(i) for i in range(3001, n)))
+    want = linepump.sequences([p])
+    assert len(want) == 12001 and sum(len(s) for s in want) == 1800150
+    res = []
+    for flags in (_lib.HULK_INGEST_TRACE, _lib.HULK_INGEST_HOST_PARSER):
+        capfd.readouterr()
+        g = gpu().GpuSketcher(21, 9, 64, interval=5000)                    # (2,001 reads in the last, partial interval)
+        st = g.sketch_files([p], opts={"flags": flags, "block_bytes": 131072})
+        g.finish()
+        res.append((st["n_seqs"], st["total_len"], st["n_lines"], g.sketch(), g.counters()))
+        g.close()
+        if flags == _lib.HULK_INGEST_TRACE:
+            assert "host parser took over" in capfd.readouterr().err       # (the branch was taken, not an all-device run)
+    dev, host = res
+    assert dev[:3] == (12001, 1800150, 1248004)
+    assert dev[:3] == host[:3] and dev[4] == host[4]
+    assert np.array_equal(dev[3][0], host[3][0]) and np.array_equal(dev[3][1], host[3][1])
+
+
 def _fa_run(paths, flags, k=11, w=5, S=32, interval=0, block=131072):
     """(stats triple, sketch, counters) of one hulk_sketch_files(--fasta) run, or the error's (code, message)"""
     from hulk_amd._lib import HulkError

@@ -576,7 +576,7 @@ def test_fasta_parallel_pieces_equal_the_restatement(tmp_path, threads, block):
 
 def test_recycled_buffers_carry_nothing_over(tmp_path):
     """The ingest path's large buffers (block, piece and batch regions) go back to a pool of the PROCESS and are handed out again
-    with their old contents (hulk_ingest.hip RegionPool).  A long FASTA file, then a shorter one with other bases, then FASTQ,
+    with their old contents (hulk_ingest_source.hip RegionPool).  A long FASTA file, then a shorter one with other bases, then FASTQ,
     with and without hulk_release_caches() in between: every parse equals the restatement."""
     from hulk_amd import _lib
     rng = np.random.default_rng(77)

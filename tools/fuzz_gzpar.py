@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised differential test of the parallel single-member gzip reader (GzPar, hulk_ingest.hip / par_inflate.h) against
+"""Randomised differential test of the parallel single-member gzip reader (GzPar, hulk_ingest_gzip.hip / par_inflate.h) against
 the one-thread reader (HULK_GZ_PAR=0), which tests/test_ingest_cpu.py and tools/fuzz_ingest.py hold against the restated
 reference: FASTQ-like text of 0.2-6 MB deflated at random levels / strategies / memLevels (block sizes), as one member,
 several members (the parallel reader ends a member itself and goes on with the next), with stored and fixed blocks, sync-flush points (empty stored blocks, as pigz writes them), trailing bytes,

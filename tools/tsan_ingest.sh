@@ -1,5 +1,6 @@
 #!/bin/bash
-# ThreadSanitizer run of the host ingest path (worker teams, the three gzip readers, block reader, parser): hulk_ingest.hip is
+# ThreadSanitizer run of the host ingest path (worker teams, the three gzip readers, block reader, parser): the units that use
+# neither a context nor the HIP runtime — hulk_ingest_gzip.hip, hulk_ingest_source.hip, hulk_ingest_host.hip — are
 # compiled as host C++ by ROCm's clang with -fsanitize=thread, linked with tools/tsan/ingest_stubs.cpp and the counting driver
 # tools/ubench/parse_rate.c, and run on the files given (default: a synthetic FASTQ as plain / one-member .gz / two-member .gz
 # / bgzip-like members are the caller's to supply).  CPU only.  usage: tools/tsan_ingest.sh [file ...]
@@ -7,10 +8,13 @@ set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=$ROOT/.scratch/tsan; mkdir -p $OUT
 CXX=/opt/rocm/lib/llvm/bin/clang++; CC=/opt/rocm/lib/llvm/bin/clang
 F="-O1 -g -fsanitize=thread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include"
-$CXX -x c++ -std=c++17 $F -fPIC -c $ROOT/hulk_amd/csrc/hulk_ingest.hip -o $OUT/ingest_tsan.o
+UNITS=""
+for u in gzip source host; do
+  $CXX -x c++ -std=c++17 $F -fPIC -c $ROOT/hulk_amd/csrc/hulk_ingest_$u.hip -o $OUT/ingest_${u}_tsan.o; UNITS="$UNITS $OUT/ingest_${u}_tsan.o"
+done
 $CXX -x c++ -std=c++17 $F -I$ROOT -c $ROOT/tools/tsan/ingest_stubs.cpp -o $OUT/stubs.o
 $CC -O1 -g -fsanitize=thread -I$ROOT/include -c $ROOT/tools/ubench/parse_rate.c -o $OUT/main.o
-$CXX -fsanitize=thread -o $OUT/parse_tsan $OUT/main.o $OUT/ingest_tsan.o $OUT/stubs.o -lz -lpthread
+$CXX -fsanitize=thread -o $OUT/parse_tsan $OUT/main.o $UNITS $OUT/stubs.o -lz -lpthread
 if [ $# -eq 0 ]; then
   python3 - <<PY
 import gzip, random
