@@ -31,6 +31,8 @@ HULK_MINHASH_KMV, HULK_MINHASH_KHF = 0, 1
 HULK_METRIC_JACCARD, HULK_METRIC_WEIGHTED_JACCARD = 0, 1
 HULK_PANEL_ROW, HULK_PANEL_COLUMN = 0, 1    # hulk_set_panel: the snapshot is the subject (its row of the smash matrix) / the panel sketch is
 HULK_PANEL_MAX = 65536
+HULK_SEARCH_MAX_K = 64          # hulk_search: hits per query
+HULK_SEARCH_SELF = 1            # ... the database is the query set itself, the pair (i, i) left out
 HULK_MINHASH_MAX_SKETCH = 4096
 HULK_MAX_BINS = 1 << 20
 HULK_INJECT_NONE, HULK_INJECT_STALE_SEAL, HULK_INJECT_STALE_STAGE = 0, 1, 2
@@ -50,6 +52,7 @@ ABI_SYMBOLS = (
     "hulk_sketch_set_banner", "hulk_smash_files", "hulk_bgzf_inflate", "hulk_get_minhash", "hulk_minhash_merge",
     "hulk_set_snapshots", "hulk_snapshot_count", "hulk_get_snapshots", "hulk_set_snapshot_callback", "hulk_poll_snapshots",
     "hulk_set_panel", "hulk_get_snapshot_distances", "hulk_set_snapshot_panel_callback", "hulk_panel_distances",
+    "hulk_search", "hulk_search_files",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -105,6 +108,17 @@ SNAPSHOT_PANEL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINT
 class SmashStats(ctypes.Structure):
     _fields_ = [("seconds_load", ctypes.c_double), ("seconds_matrix", ctypes.c_double), ("seconds_csv", ctypes.c_double),
                 ("kernel_ms", ctypes.c_double), ("n_sketches", ctypes.c_uint32), ("sketch_size", ctypes.c_uint32)]
+
+
+class SearchOpts(ctypes.Structure):
+    """hulk_search_opts (include/hulk_hip.h)."""
+    _fields_ = [("k", ctypes.c_uint32), ("metric", ctypes.c_int), ("role", ctypes.c_int), ("flags", ctypes.c_uint32),
+                ("max_distance", ctypes.c_double), ("scratch_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class SearchStats(ctypes.Structure):
+    _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_dist", ctypes.c_double), ("kernel_ms_select", ctypes.c_double),
+                ("strips", ctypes.c_uint32), ("query_blocks", ctypes.c_uint32)]
 
 
 class HulkError(RuntimeError):
@@ -297,6 +311,11 @@ def load():
     L.hulk_set_snapshot_panel_callback.restype = ctypes.c_int; L.hulk_set_snapshot_panel_callback.argtypes = [vp, SNAPSHOT_PANEL_FN, vp]
     L.hulk_panel_distances.restype = ctypes.c_int
     L.hulk_panel_distances.argtypes = [ctypes.c_int, vp, vp, u32, vp, vp, u32, u32, ctypes.c_int, ctypes.c_int, vp]
+    L.hulk_search.restype = ctypes.c_int
+    L.hulk_search.argtypes = [ctypes.c_int, vp, vp, u32, vp, vp, u32, u32, ctypes.POINTER(SearchOpts), vp, vp, vp, ctypes.POINTER(SearchStats)]
+    L.hulk_search_files.restype = ctypes.c_int
+    L.hulk_search_files.argtypes = [ctypes.c_int, cpp, u32, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, u32, dbl, u32, u32,
+                                    ctypes.c_char_p, vp, vp, vp, ctypes.POINTER(SearchStats), ctypes.c_char_p, u64]
     _lib = L
     return L
 

@@ -490,10 +490,10 @@ struct hulk_sketch_set {
     bool histosketch = false;
 };
 
-extern "C" {
-
-int hulk_load_sketches(const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, uint32_t threads,
-                       hulk_sketch_set **out, char *errbuf, uint64_t errbuf_len) {
+// the loader behind hulk_load_sketches and hulk_search_files.  at_least_two: smash's rule (cmd/smash.go:175-177); a search takes a
+// set of one sketch
+static int load_sketch_set(const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, uint32_t threads, bool at_least_two,
+                           hulk_sketch_set **out, char *errbuf, uint64_t errbuf_len) {
     if (out) *out = nullptr;
     if (!out || !algo || (n_paths && !paths)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
     for (uint32_t i = 0; i < n_paths; i++) if (!paths[i]) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL path");
@@ -510,8 +510,9 @@ int hulk_load_sketches(const char *const *paths, uint32_t n_paths, uint32_t ksiz
     // (:175-177); FindSketch failures surface in makeMatrix, pair by pair in sorted order: the first file that has one
     for (const Loaded &L : set->files)
         if (!L.error.empty() && !L.find_stage) { const std::string e = L.error; delete set; return put_err(errbuf, errbuf_len, HULK_ERR_ARG, e); }
-    if (set->files.size() < 2) {
-        const std::string e = std::to_string(set->files.size()) + " sketches found in the supplied directory, HULK needs at least 2 to smash!\n";
+    if (set->files.size() < (at_least_two ? 2u : 1u)) {
+        const std::string e = at_least_two ? std::to_string(set->files.size()) + " sketches found in the supplied directory, HULK needs at least 2 to smash!\n"
+                                           : std::string("no sketch files supplied\n");
         delete set;
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, e);
     }
@@ -547,6 +548,13 @@ int hulk_load_sketches(const char *const *paths, uint32_t n_paths, uint32_t ksiz
     }
     *out = set;
     return HULK_OK;
+}
+
+extern "C" {
+
+int hulk_load_sketches(const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, uint32_t threads,
+                       hulk_sketch_set **out, char *errbuf, uint64_t errbuf_len) {
+    return load_sketch_set(paths, n_paths, ksize, algo, threads, true, out, errbuf, errbuf_len);
 }
 
 void hulk_sketch_set_free(hulk_sketch_set *set) { delete set; }
@@ -622,6 +630,68 @@ int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uin
     if (stats) {
         stats->seconds_load = t1 - t0; stats->seconds_matrix = t2 - t1; stats->seconds_csv = now_s() - t2; stats->kernel_ms = kernel_ms;
         stats->n_sketches = n; stats->sketch_size = S;
+    }
+    return HULK_OK;
+}
+
+int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, const char *const *db_paths, uint32_t n_db,
+                      uint32_t ksize, const char *algo, const char *metric, int role, uint32_t k, double max_distance, uint32_t flags,
+                      uint32_t threads, const char *csv_path, uint32_t *hit_index, double *hit_distance, uint32_t *hit_count,
+                      hulk_search_stats *stats, char *errbuf, uint64_t errbuf_len) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    const std::string metric_s = metric, algo_s = algo;
+    if (metric_s != "jaccard" && metric_s != "weightedjaccard")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard]");
+    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (k == 0 || k > HULK_SEARCH_MAX_K) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
+    if (role != HULK_PANEL_ROW && role != HULK_PANEL_COLUMN) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: role");
+    if (flags & ~HULK_SEARCH_SELF) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: unknown flags");
+    const bool self = (flags & HULK_SEARCH_SELF) != 0;
+    if (self && (db_paths || n_db)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: HULK_SEARCH_SELF takes no database");
+    if (!self && !db_paths) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: no database (and no HULK_SEARCH_SELF)");
+    hulk_sketch_set *qs = nullptr, *ds = nullptr;
+    { const int rc = load_sketch_set(query_paths, n_q, ksize, algo, threads, false, &qs, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
+    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } gq{qs}, gd{nullptr};
+    if (!self) {
+        const int rc = load_sketch_set(db_paths, n_db, ksize, algo, threads, false, &ds, errbuf, errbuf_len);
+        if (rc != HULK_OK) return rc;
+        gd.s = ds;
+        if (qs->size != ds->size)                                   // sketchio.go:274-277
+            return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(qs->size) + " vs " + std::to_string(ds->size) + "\n");
+    }
+    if (metric_s == "weightedjaccard" && !qs->histosketch)          // sketchio.go:287-293
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    const hulk_sketch_set *db = self ? qs : ds;
+    const uint32_t m = (uint32_t)qs->files.size();
+    std::vector<uint32_t> own_i, own_c; std::vector<double> own_d;
+    if (!hit_index) { own_i.resize((size_t)m * k); hit_index = own_i.data(); }
+    if (!hit_distance) { own_d.resize((size_t)m * k); hit_distance = own_d.data(); }
+    if (!hit_count) { own_c.resize(m); hit_count = own_c.data(); }
+    hulk_search_opts o;
+    memset(&o, 0, sizeof o);
+    o.k = k; o.metric = metric_s == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD; o.role = role; o.flags = flags;
+    o.max_distance = max_distance;
+    {
+        const int rc = hulk_search(device, qs->mins.data(), qs->weights.data(), m, self ? nullptr : ds->mins.data(), self ? nullptr : ds->weights.data(),
+                                   self ? 0 : (uint32_t)ds->files.size(), qs->size, &o, hit_index, hit_distance, hit_count, stats);
+        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
+    }
+    if (csv_path) {
+        std::vector<std::string> rows((size_t)m + 1);
+        rows[0] = "query,rank,hit,similarity\n";
+        parallel_for(m, pick_threads(threads, m), [&](size_t i) {
+            std::string &r = rows[i + 1];
+            for (uint32_t j = 0; j < hit_count[i]; j++) {
+                csv_field(r, qs->files[i].path); r += ','; r += std::to_string(j + 1); r += ',';
+                csv_field(r, db->files[hit_index[i * (size_t)k + j]].path); r += ',';
+                format_f2(r, 100 - (hit_distance[i * (size_t)k + j] * 100));       // cmd/smash.go:217
+                r += '\n';
+            }
+        });
+        std::string err;
+        if (!write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     }
     return HULK_OK;
 }

@@ -3,6 +3,8 @@
 Reference: cmd/smash.go:60-226 (parameter checks, CollectJSONs, makeMatrix), HULKdata.GetDistance
 (src/sketchio/sketchio.go:259-306), distances.GetDistance/GetWJD (src/distances/distances.go).
 The N x N x S comparison runs in libhulkhip (hulk_smash); this module only loads, orders and writes.
+search / search_files: for every query sketch the k closest sketches of a database (hulk_search, hulk_search_files) — the same
+distance, selected on the GPU while the database streams through it.
 """
 import fnmatch
 import glob
@@ -78,6 +80,93 @@ def panel_distances(snap_mins, snap_weights, panel_mins, panel_weights, metric="
     if rc != 0:
         raise HulkError(rc, L.hulk_last_error(None).decode())
     return out
+
+
+def _search_consts(metric, role):
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if role not in ("row", "column"):
+        raise ValueError("role must be 'row' or 'column'")
+    return (_lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+            _lib.HULK_PANEL_COLUMN if role == "column" else _lib.HULK_PANEL_ROW)
+
+
+def _stats_dict(st):
+    return dict(seconds_total=st.seconds_total, kernel_ms_dist=st.kernel_ms_dist, kernel_ms_select=st.kernel_ms_select,
+                strips=st.strips, query_blocks=st.query_blocks)
+
+
+def search(q_mins, q_weights, db_mins, db_weights, k, metric="jaccard", role="row", max_distance=None, self_search=False,
+           scratch_bytes=0, device=0, stats=None):
+    """For every query sketch the k closest sketches of a database, on the GPU (hulk_search): -> (index[m][k] uint32,
+    distance[m][k], count[m]).  The distance is distance_matrix's for that pair — role "row": the query is the subject, "column":
+    the database sketch is — and a query's hits are the pairs whose distance is not NaN (and <= max_distance, if given in [0, 1]),
+    ordered by (distance, database index), cut to k; behind count[i] the entries are 0xFFFFFFFF / NaN.  self_search: db_mins and
+    db_weights are None, the queries are searched among themselves and the pair (i, i) is left out.  The database streams through
+    the device in strips sized by scratch_bytes (0 = 1 GiB): no m x n_db array exists.  stats: a dict that receives
+    seconds_total, kernel_ms_dist, kernel_ms_select, strips, query_blocks."""
+    import ctypes
+    metric_c, role_c = _search_consts(metric, role)
+    qm = np.ascontiguousarray(q_mins, dtype=np.uint64); qw = np.ascontiguousarray(q_weights, dtype=np.float64)
+    if qm.ndim != 2 or qm.shape != qw.shape:
+        raise ValueError("mins/weights must be [n][sketch_size]")
+    if self_search:
+        if db_mins is not None or db_weights is not None:
+            raise ValueError("self_search takes no database")
+        dm = dw = None
+    else:
+        dm = np.ascontiguousarray(db_mins, dtype=np.uint64); dw = np.ascontiguousarray(db_weights, dtype=np.float64)
+        if dm.ndim != 2 or dm.shape != dw.shape:
+            raise ValueError("mins/weights must be [n][sketch_size]")
+        if qm.shape[1] != dm.shape[1]:
+            raise HulkError(-30, f"sketch length mismatch: {qm.shape[1]} vs {dm.shape[1]}\n")
+    m, k = qm.shape[0], int(k)
+    o = _lib.SearchOpts(k=k if 0 <= k < 2 ** 32 else 0, metric=metric_c, role=role_c, flags=_lib.HULK_SEARCH_SELF if self_search else 0,
+                        max_distance=-1.0 if max_distance is None else float(max_distance), scratch_bytes=int(scratch_bytes))
+    kk = max(min(k, _lib.HULK_SEARCH_MAX_K), 1)
+    index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(m, dtype=np.uint32)
+    st = _lib.SearchStats()
+    L = _lib.load()
+    rc = L.hulk_search(device, qm.ctypes.data, qw.ctypes.data, m, None if dm is None else dm.ctypes.data, None if dw is None else dw.ctypes.data,
+                       0 if dm is None else dm.shape[0], qm.shape[1], ctypes.byref(o), index.ctypes.data, dist.ctypes.data, count.ctypes.data,
+                       ctypes.byref(st))
+    if rc != 0:
+        raise HulkError(rc, L.hulk_last_error(None).decode())
+    if stats is not None:
+        stats.update(_stats_dict(st))
+    return index, dist, count
+
+
+def search_files(query_files, db_files, k, ksize=21, algo="histosketch", metric="jaccard", role="row", max_distance=None,
+                 self_search=False, csv_path=None, threads=0, device=0, stats=None):
+    """The directory form (hulk_search_files): both lists of sketch files are loaded and MD5-verified by the native loader (a single
+    query file is fine), the search runs on the GPU and, csv_path given, the library writes "query,rank,hit,similarity" — one line
+    per hit, the similarity the string `smash` prints for that pair.  -> (query ordering, database ordering, index, distance, count);
+    the orderings are the sorted unique paths, index counts the database's."""
+    import ctypes
+    _search_consts(metric, role)
+    if algo not in AVAIL_ALGORITHMS:
+        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    q_order = sorted(set(query_files))
+    d_order = q_order if self_search else sorted(set(db_files))
+    k = int(k)
+    kk = max(min(k, _lib.HULK_SEARCH_MAX_K), 1)
+    m = len(q_order)
+    index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(max(m, 1), dtype=np.uint32)
+    qa, nq = _paths(query_files)
+    da, nd = (None, 0) if self_search else _paths(db_files)
+    st = _lib.SearchStats()
+    err = ctypes.create_string_buffer(4096)
+    L = _lib.load()
+    rc = L.hulk_search_files(device, qa, nq, da, nd, ksize, algo.encode(), metric.encode(), 1 if role == "column" else 0,
+                             k if 0 <= k < 2 ** 32 else 0, -1.0 if max_distance is None else float(max_distance),
+                             _lib.HULK_SEARCH_SELF if self_search else 0, threads, None if csv_path is None else os.fsencode(csv_path),
+                             index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st), err, len(err))
+    if rc != 0:
+        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    if stats is not None:
+        stats.update(_stats_dict(st))
+    return q_order, d_order, index, dist, count[:m]
 
 
 def go_format_f2(v: float) -> str:

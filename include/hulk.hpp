@@ -13,6 +13,7 @@
 //       pipeline/sketch.go:182-250                                          (RCCL inside libhulkhip.so)
 //   `--stream`: "prints the sketches ... after every interval"            hulk::Boss::EnableSnapshots / CollectSnapshots /
 //       cmd/sketch.go:56 (promised, read nowhere in src/pipeline)           OnSnapshot (recorded inside the batched flush)
+//   (none: the k nearest sketches of a database for every query sketch)   hulk::Search (HULKdata.GetDistance per pair)
 //
 // Header only; link with -lhulkhip.  A Boss is single-caller, like SeqMinimizer.Run's goroutine.
 #ifndef HULK_HPP
@@ -309,6 +310,46 @@ inline std::vector<double> Smash(const std::vector<HistoSketch> &sketches, const
     else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
     const int rc = hulk_smash(device, mins.data(), weights.data(), N, S, m, out.data());
     if (rc != HULK_OK) throw Error(rc, hulk_strerror(rc));
+    return out;
+}
+
+// For every query sketch the k closest sketches of a database, on the GPU (hulk_search): Smash's distance for the pair — queryIsSubject:
+// the query's row of that matrix, otherwise the database sketch's column — the pairs that are not NaN (and <= maxDistance, if it is in
+// [0, 1]) in (distance, database index) order, at most k per query.  An empty `database` searches the queries among themselves
+// (HULK_SEARCH_SELF): a sketch is not its own hit.  The database streams through the device: no queries x database array exists.
+struct Hit { uint32_t Index = 0; double Distance = 0; };
+inline std::vector<std::vector<Hit>> Search(const std::vector<HistoSketch> &queries, const std::vector<HistoSketch> &database, uint32_t k,
+                                            const std::string &metric, bool queryIsSubject = true, double maxDistance = -1.0,
+                                            uint64_t scratchBytes = 0, int device = 0, hulk_search_stats *stats = nullptr) {
+    const uint32_t M = (uint32_t)queries.size(), P = (uint32_t)database.size(), S = M ? queries[0].SketchSize : 0;
+    auto pack = [S](const std::vector<HistoSketch> &set, std::vector<uint64_t> &mins, std::vector<double> &weights, unsigned first) {
+        mins.resize(set.size() * (size_t)S); weights.resize(set.size() * (size_t)S);
+        for (size_t i = 0; i < set.size(); i++) {
+            if (set[i].Sketch.size() != S || set[i].SketchWeights.size() != S)
+                throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(first) + " vs " + std::to_string(set[i].Sketch.size()) + "\n");
+            std::copy(set[i].Sketch.begin(), set[i].Sketch.end(), mins.begin() + i * (size_t)S);
+            std::copy(set[i].SketchWeights.begin(), set[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
+        }
+    };
+    std::vector<uint64_t> qm, dm;
+    std::vector<double> qw, dw;
+    pack(queries, qm, qw, S);
+    pack(database, dm, dw, S);
+    hulk_search_opts o = hulk_search_opts();
+    o.k = k; o.role = queryIsSubject ? HULK_PANEL_ROW : HULK_PANEL_COLUMN; o.flags = P ? 0u : HULK_SEARCH_SELF;
+    o.max_distance = maxDistance; o.scratch_bytes = scratchBytes;
+    if (metric == "jaccard") o.metric = HULK_METRIC_JACCARD;
+    else if (metric == "weightedjaccard") o.metric = HULK_METRIC_WEIGHTED_JACCARD;
+    else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+    const size_t kk = k ? k : 1;
+    std::vector<uint32_t> index(M * kk + 1), count((size_t)M + 1);
+    std::vector<double> distance(M * kk + 1);
+    const int rc = hulk_search(device, qm.data(), qw.data(), M, P ? dm.data() : nullptr, P ? dw.data() : nullptr, P, S, &o, index.data(),
+                               distance.data(), count.data(), stats);
+    if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+    std::vector<std::vector<Hit>> out(M);
+    for (uint32_t i = 0; i < M; i++)
+        for (uint32_t j = 0; j < count[i]; j++) { Hit h; h.Index = index[i * kk + j]; h.Distance = distance[i * kk + j]; out[i].push_back(h); }
     return out;
 }
 

@@ -67,7 +67,7 @@ extern "C" {
  *    Additions since (no existing entry point changed): HULK_FLAG_KMV / HULK_FLAG_KHF with hulk_get_minhash / hulk_minhash_merge;
  *    sketch snapshots (hulk_set_snapshots, hulk_snapshot_count, hulk_get_snapshots, hulk_set_snapshot_callback, hulk_poll_snapshots);
  *    a panel the snapshots are scored against (hulk_set_panel, hulk_get_snapshot_distances, hulk_set_snapshot_panel_callback,
- *    hulk_panel_distances).
+ *    hulk_panel_distances); the nearest-neighbour search (hulk_search, hulk_search_files).
  * Bindings compare it with the value they were written for. */
 #define HULK_ABI_VERSION 4
 
@@ -568,6 +568,56 @@ typedef struct hulk_smash_stats {
 int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
                      uint32_t threads, const char *matrix_csv_path, const char *banner_csv_path, double *distances,
                      hulk_smash_stats *stats, char *errbuf, uint64_t errbuf_len);
+
+/* ---- nearest-neighbour search: for every query sketch the K closest sketches of a database ----------------------------------------
+ * distance(query i, database sketch p) = HULKdata.GetDistance exactly as hulk_smash computes it (mins compared as float64, jaccard =
+ * 1 - equal / sketch_size, weightedjaccard = GetWJD with both weight vectors the SUBJECT's, |w|, fp64 sums over the slots in ascending
+ * order): bit for bit the entry `smash` prints with both files in one directory.  role as for the panel: HULK_PANEL_ROW the query is
+ * the subject (its weights), HULK_PANEL_COLUMN the database sketch is; for jaccard the two are the same.
+ * The hit list of query i: the pairs whose distance is not NaN and, if max_distance is in [0, 1], is <= max_distance (a negative
+ * value or NaN: no limit), ordered by (distance ascending, database index ascending) — a total order: the result does not depend on
+ * scheduling, strip size or launch shape — cut to the first k.  hit_count[i] <= k is its length; hit_index / hit_distance [m][k] hold
+ * it, the entries behind hit_count[i] are 0xFFFFFFFF / NaN.  HULK_SEARCH_SELF: the database is the query set itself (db_mins and
+ * db_weights NULL, n_db ignored) and the pair (i, i) is left out: the k-nearest-neighbour graph of a collection.
+ * The prepared queries stay on the device; the database streams through it strip by strip (upload, prepare, distances of a block of
+ * queries x the strip into a scratch, selection into the running lists: k_search_dist, k_search_select in hulk_search.hip), so device
+ * memory is the queries plus scratch_bytes whatever n_db is, and no m x n_db array exists anywhere.  scratch_bytes (0 = default,
+ * 1 GiB) holds one strip (raw and prepared: 32 * sketch_size bytes per database sketch) and the distances of query block x strip.
+ * HULK_ERR_ARG before any HIP call, with a text in hulk_last_error(NULL): NULL arrays; k == 0 or k > HULK_SEARCH_MAX_K; m, n_db or
+ * sketch_size == 0; an unknown metric, role or flag; non-zero reserved; HULK_SEARCH_SELF together with db arrays, or no db arrays
+ * without it; a scratch_bytes too small for one tile (32 queries x 64 database sketches). */
+#define HULK_SEARCH_MAX_K 64u
+#define HULK_SEARCH_SELF 1u
+typedef struct hulk_search_opts {
+    uint32_t k;              /* hits per query, 1 .. HULK_SEARCH_MAX_K */
+    int metric;              /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD */
+    int role;                /* HULK_PANEL_ROW / HULK_PANEL_COLUMN */
+    uint32_t flags;          /* HULK_SEARCH_SELF */
+    double max_distance;     /* in [0, 1]: only hits with distance <= max_distance; negative or NaN: no limit */
+    uint64_t scratch_bytes;  /* 0 = default */
+    uint64_t reserved[4];    /* zero */
+} hulk_search_opts;
+typedef struct hulk_search_stats {
+    double seconds_total;    /* the whole call */
+    double kernel_ms_dist;   /* k_search_dist, summed over the strips and query blocks (HIP events) */
+    double kernel_ms_select; /* k_search_select, the same */
+    uint32_t strips, query_blocks;
+} hulk_search_stats;
+int hulk_search(int device, const uint64_t *q_mins, const double *q_weights, uint32_t m, const uint64_t *db_mins,
+                const double *db_weights, uint32_t n_db, uint32_t sketch_size, const hulk_search_opts *opts, uint32_t *hit_index,
+                double *hit_distance, uint32_t *hit_count, hulk_search_stats *stats);
+/* The directory form: both sets of sketch files go through hulk_load_sketches' loader (MD5, FindSketch, the reference's error texts;
+ * sorted path order within each set, a path given twice counts once) — but a set of ONE sketch is valid here: "needs at least 2" is
+ * smash's rule.  Different sketch lengths across the sets: "sketch length mismatch: %d vs %d\n" (the queries', the database's).
+ * HULK_SEARCH_SELF in flags: db_paths NULL, the queries are searched among themselves.  metric: "jaccard" | "weightedjaccard"; algo:
+ * "histosketch" | "kmv" | "khf".  csv_path != NULL: a file with the header "query,rank,hit,similarity" and one line per hit, in query
+ * order and then rank order from 1: the two paths as encoding/csv quotes them and strconv.FormatFloat(100 - 100 * distance, 'f', 2, 64),
+ * the string `smash` prints for that pair.  hit_index / hit_distance [unique query paths][k] and hit_count may be NULL; the indices
+ * count the database's sorted unique paths. */
+int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, const char *const *db_paths, uint32_t n_db,
+                      uint32_t ksize, const char *algo, const char *metric, int role, uint32_t k, double max_distance, uint32_t flags,
+                      uint32_t threads, const char *csv_path, uint32_t *hit_index, double *hit_distance, uint32_t *hit_count,
+                      hulk_search_stats *stats, char *errbuf, uint64_t errbuf_len);
 
 /* Device self-test: the jump hash replaces the fp64 division 2^31/r by a Newton reciprocal; this
  * checks RN(1/r) against IEEE division for EVERY r in [1, 2^31] and returns the mismatch count. */
