@@ -33,6 +33,7 @@ HULK_PANEL_ROW, HULK_PANEL_COLUMN = 0, 1    # hulk_set_panel: the snapshot is th
 HULK_PANEL_MAX = 65536
 HULK_SEARCH_MAX_K = 64          # hulk_search: hits per query
 HULK_SEARCH_SELF = 1            # ... the database is the query set itself, the pair (i, i) left out
+HULK_CLUSTER_MAX_N = 2097088     # hulk_cluster: sketches in one set
 HULK_MINHASH_MAX_SKETCH = 4096
 HULK_MAX_BINS = 1 << 20
 HULK_INJECT_NONE, HULK_INJECT_STALE_SEAL, HULK_INJECT_STALE_STAGE = 0, 1, 2
@@ -52,7 +53,7 @@ ABI_SYMBOLS = (
     "hulk_sketch_set_banner", "hulk_smash_files", "hulk_bgzf_inflate", "hulk_get_minhash", "hulk_minhash_merge",
     "hulk_set_snapshots", "hulk_snapshot_count", "hulk_get_snapshots", "hulk_set_snapshot_callback", "hulk_poll_snapshots",
     "hulk_set_panel", "hulk_get_snapshot_distances", "hulk_set_snapshot_panel_callback", "hulk_panel_distances",
-    "hulk_search", "hulk_search_files",
+    "hulk_search", "hulk_search_files", "hulk_cluster", "hulk_cluster_files",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -119,6 +120,17 @@ class SearchOpts(ctypes.Structure):
 class SearchStats(ctypes.Structure):
     _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_dist", ctypes.c_double), ("kernel_ms_select", ctypes.c_double),
                 ("strips", ctypes.c_uint32), ("query_blocks", ctypes.c_uint32)]
+
+
+class ClusterOpts(ctypes.Structure):
+    """hulk_cluster_opts (include/hulk_hip.h)."""
+    _fields_ = [("metric", ctypes.c_int), ("max_distance", ctypes.c_double), ("band_rows", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint64 * 4)]
+
+
+class ClusterStats(ctypes.Structure):
+    _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_link", ctypes.c_double), ("kernel_ms_flatten", ctypes.c_double),
+                ("links", ctypes.c_uint64), ("bands", ctypes.c_uint32), ("clusters", ctypes.c_uint32)]
 
 
 class HulkError(RuntimeError):
@@ -316,6 +328,11 @@ def load():
     L.hulk_search_files.restype = ctypes.c_int
     L.hulk_search_files.argtypes = [ctypes.c_int, cpp, u32, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, u32, dbl, u32, u32,
                                     ctypes.c_char_p, vp, vp, vp, ctypes.POINTER(SearchStats), ctypes.c_char_p, u64]
+    L.hulk_cluster.restype = ctypes.c_int
+    L.hulk_cluster.argtypes = [ctypes.c_int, vp, vp, u32, u32, ctypes.POINTER(ClusterOpts), vp, ctypes.POINTER(ClusterStats)]
+    L.hulk_cluster_files.restype = ctypes.c_int
+    L.hulk_cluster_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, dbl, u32, ctypes.c_char_p, vp,
+                                     ctypes.POINTER(ClusterStats), ctypes.c_char_p, u64]
     _lib = L
     return L
 

@@ -696,4 +696,50 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
     return HULK_OK;
 }
 
+int hulk_cluster_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
+                       double max_distance, uint32_t threads, const char *csv_path, uint32_t *label, hulk_cluster_stats *stats,
+                       char *errbuf, uint64_t errbuf_len) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    const std::string metric_s = metric, algo_s = algo;
+    if (metric_s != "jaccard" && metric_s != "weightedjaccard")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard]");
+    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (!(max_distance >= 0.0 && max_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_cluster: max_distance must be in [0, 1]");
+    hulk_sketch_set *set = nullptr;
+    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
+    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
+    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    const uint32_t n = (uint32_t)set->files.size();
+    std::vector<uint32_t> own;
+    if (!label) { own.resize(n); label = own.data(); }
+    hulk_cluster_opts o;
+    memset(&o, 0, sizeof o);
+    o.metric = metric_s == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD;
+    o.max_distance = max_distance;
+    {
+        const int rc = hulk_cluster(device, set->mins.data(), set->weights.data(), n, set->size, &o, label, stats);
+        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
+    }
+    if (csv_path) {
+        // a cluster's smallest member is its label: the ordinals count the labels in ascending order
+        std::vector<uint32_t> ordinal(n, 0), size(n, 0);
+        uint32_t next = 0;
+        for (uint32_t i = 0; i < n; i++) { if (label[i] == i) ordinal[i] = ++next; size[label[i]]++; }
+        std::vector<std::string> rows((size_t)n + 1);
+        rows[0] = "sketch,cluster,size,representative\n";
+        for (uint32_t i = 0; i < n; i++) {
+            std::string &r = rows[(size_t)i + 1];
+            const uint32_t l = label[i];
+            csv_field(r, set->files[i].path); r += ','; r += std::to_string(ordinal[l]); r += ','; r += std::to_string(size[l]); r += ',';
+            csv_field(r, set->files[l].path); r += '\n';
+        }
+        std::string err;
+        if (!write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    }
+    return HULK_OK;
+}
+
 }  // extern "C"

@@ -5,6 +5,8 @@ Reference: cmd/smash.go:60-226 (parameter checks, CollectJSONs, makeMatrix), HUL
 The N x N x S comparison runs in libhulkhip (hulk_smash); this module only loads, orders and writes.
 search / search_files: for every query sketch the k closest sketches of a database (hulk_search, hulk_search_files) — the same
 distance, selected on the GPU while the database streams through it.
+cluster / cluster_files: the connected components of "distance <= threshold" over a collection (hulk_cluster, hulk_cluster_files):
+single linkage, without the N x N matrix.
 """
 import fnmatch
 import glob
@@ -167,6 +169,65 @@ def search_files(query_files, db_files, k, ksize=21, algo="histosketch", metric=
     if stats is not None:
         stats.update(_stats_dict(st))
     return q_order, d_order, index, dist, count[:m]
+
+
+def _cluster_stats_dict(st):
+    return dict(seconds_total=st.seconds_total, kernel_ms_link=st.kernel_ms_link, kernel_ms_flatten=st.kernel_ms_flatten,
+                links=st.links, bands=st.bands, clusters=st.clusters)
+
+
+def cluster(mins, weights, max_distance, metric="jaccard", band_rows=0, device=0, stats=None):
+    """Single-linkage clusters of a sketch collection at a distance threshold, on the GPU (hulk_cluster): -> (labels uint32[N],
+    n_clusters).  With D = distance_matrix(mins, weights, metric), sketches i != j are linked when D[i, j] <= max_distance or
+    D[j, i] <= max_distance (a NaN never links, equality does); a cluster is a connected component and labels[i] its smallest
+    member.  max_distance must be in [0, 1]; band_rows (a multiple of 32, 0 = 2048): the subject rows one kernel launch takes —
+    it cannot change the result.  stats: a dict that receives seconds_total, kernel_ms_link, kernel_ms_flatten, links (the
+    ordered pairs i != j with D[i, j] <= max_distance), bands, clusters."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    m = np.ascontiguousarray(mins, dtype=np.uint64); w = np.ascontiguousarray(weights, dtype=np.float64)
+    if m.ndim != 2 or m.shape != w.shape:
+        raise ValueError("mins/weights must be [n][sketch_size]")
+    band_rows = int(band_rows)
+    if not 0 <= band_rows < 2 ** 32:
+        raise ValueError("band_rows must be a multiple of 32 (0 = default)")
+    o = _lib.ClusterOpts(metric=_lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+                         max_distance=float(max_distance), band_rows=band_rows)
+    labels = np.zeros(max(m.shape[0], 1), dtype=np.uint32)
+    st = _lib.ClusterStats()
+    L = _lib.load()
+    rc = L.hulk_cluster(device, m.ctypes.data, w.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), labels.ctypes.data, ctypes.byref(st))
+    if rc != 0:
+        raise HulkError(rc, L.hulk_last_error(None).decode())
+    if stats is not None:
+        stats.update(_cluster_stats_dict(st))
+    return labels[:m.shape[0]], int(st.clusters)
+
+
+def cluster_files(files, max_distance, ksize=21, algo="histosketch", metric="jaccard", csv_path=None, threads=0, device=0, stats=None):
+    """The directory form (hulk_cluster_files): the sketch files are loaded and MD5-verified by the native loader (one file is
+    fine), the clustering runs on the GPU and, csv_path given, the library writes "sketch,cluster,size,representative" — one line
+    per sketch in sorted path order: the 1-based ordinal of its cluster (ordered by smallest member), the cluster's size and the
+    path of its smallest member.  -> (ordering, labels, n_clusters); ordering = the sorted unique paths, labels index it."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if algo not in AVAIL_ALGORITHMS:
+        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    ordering = sorted(set(files))
+    labels = np.zeros(max(len(ordering), 1), dtype=np.uint32)
+    arr, n = _paths(files)
+    st = _lib.ClusterStats()
+    err = ctypes.create_string_buffer(4096)
+    L = _lib.load()
+    rc = L.hulk_cluster_files(device, arr, n, ksize, algo.encode(), metric.encode(), float(max_distance), threads,
+                              None if csv_path is None else os.fsencode(csv_path), labels.ctypes.data, ctypes.byref(st), err, len(err))
+    if rc != 0:
+        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    if stats is not None:
+        stats.update(_cluster_stats_dict(st))
+    return ordering, labels[:len(ordering)], int(st.clusters)
 
 
 def go_format_f2(v: float) -> str:

@@ -14,6 +14,7 @@
 //   `--stream`: "prints the sketches ... after every interval"            hulk::Boss::EnableSnapshots / CollectSnapshots /
 //       cmd/sketch.go:56 (promised, read nowhere in src/pipeline)           OnSnapshot (recorded inside the batched flush)
 //   (none: the k nearest sketches of a database for every query sketch)   hulk::Search (HULKdata.GetDistance per pair)
+//   (none: the sketches of a collection grouped at a distance threshold)  hulk::Cluster / hulk::ClusterFiles (single linkage)
 //
 // Header only; link with -lhulkhip.  A Boss is single-caller, like SeqMinimizer.Run's goroutine.
 #ifndef HULK_HPP
@@ -351,6 +352,51 @@ inline std::vector<std::vector<Hit>> Search(const std::vector<HistoSketch> &quer
     for (uint32_t i = 0; i < M; i++)
         for (uint32_t j = 0; j < count[i]; j++) { Hit h; h.Index = index[i * kk + j]; h.Distance = distance[i * kk + j]; out[i].push_back(h); }
     return out;
+}
+
+// Single-linkage clusters of a collection at a distance threshold, on the GPU (hulk_cluster): sketches i != j are linked when Smash's
+// entry [i][j] or [j][i] is <= maxDistance (in [0, 1]; a NaN never links, equality does); a cluster is a connected component, the
+// label of a sketch the smallest index in its cluster.  bandRows (a multiple of 32, 0 = default) cannot change the result.
+inline std::vector<uint32_t> Cluster(const std::vector<HistoSketch> &sketches, double maxDistance, const std::string &metric,
+                                     uint32_t bandRows = 0, int device = 0, hulk_cluster_stats *stats = nullptr) {
+    const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
+    std::vector<uint64_t> mins((size_t)N * S + 1);
+    std::vector<double> weights((size_t)N * S + 1);
+    for (uint32_t i = 0; i < N; i++) {
+        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
+            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
+        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
+        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
+    }
+    hulk_cluster_opts o = hulk_cluster_opts();
+    o.max_distance = maxDistance; o.band_rows = bandRows;
+    if (metric == "jaccard") o.metric = HULK_METRIC_JACCARD;
+    else if (metric == "weightedjaccard") o.metric = HULK_METRIC_WEIGHTED_JACCARD;
+    else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+    std::vector<uint32_t> label((size_t)N + 1);
+    const int rc = hulk_cluster(device, mins.data(), weights.data(), N, S, &o, label.data(), stats);
+    if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+    label.resize(N);
+    return label;
+}
+
+// The directory form (hulk_cluster_files): the files through the library's loader (sorted unique paths, the reference's error
+// texts), the labels in that order; clustersCSV, if not empty, receives "sketch,cluster,size,representative".
+inline std::vector<uint32_t> ClusterFiles(const std::vector<std::string> &jsonFiles, uint32_t kSize, const std::string &algo,
+                                          const std::string &metric, double maxDistance, const std::string &clustersCSV = std::string(),
+                                          hulk_cluster_stats *stats = nullptr, int device = 0, uint32_t threads = 0) {
+    std::vector<const char *> ptr;
+    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
+    std::vector<std::string> uniq(jsonFiles);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    std::vector<uint32_t> label(uniq.size() + 1);
+    char err[4096] = {0};
+    const int rc = hulk_cluster_files(device, ptr.data(), (uint32_t)ptr.size(), kSize, algo.c_str(), metric.c_str(), maxDistance, threads,
+                                      clustersCSV.empty() ? nullptr : clustersCSV.c_str(), label.data(), stats, err, sizeof err);
+    if (rc != HULK_OK) throw Error(rc, err);
+    label.resize(uniq.size());
+    return label;
 }
 
 // `hulk smash` as the reference runs it (cmd/smash.go:160-226): the sketch files of a directory in, <outFile>.hulk-matrix.csv out —

@@ -67,7 +67,8 @@ extern "C" {
  *    Additions since (no existing entry point changed): HULK_FLAG_KMV / HULK_FLAG_KHF with hulk_get_minhash / hulk_minhash_merge;
  *    sketch snapshots (hulk_set_snapshots, hulk_snapshot_count, hulk_get_snapshots, hulk_set_snapshot_callback, hulk_poll_snapshots);
  *    a panel the snapshots are scored against (hulk_set_panel, hulk_get_snapshot_distances, hulk_set_snapshot_panel_callback,
- *    hulk_panel_distances); the nearest-neighbour search (hulk_search, hulk_search_files).
+ *    hulk_panel_distances); the nearest-neighbour search (hulk_search, hulk_search_files); single-linkage clustering (hulk_cluster,
+ *    hulk_cluster_files).
  * Bindings compare it with the value they were written for. */
 #define HULK_ABI_VERSION 4
 
@@ -618,6 +619,44 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
                       uint32_t ksize, const char *algo, const char *metric, int role, uint32_t k, double max_distance, uint32_t flags,
                       uint32_t threads, const char *csv_path, uint32_t *hit_index, double *hit_distance, uint32_t *hit_count,
                       hulk_search_stats *stats, char *errbuf, uint64_t errbuf_len);
+
+/* ---- single-linkage clustering of a sketch collection at a distance threshold ---------------------------------------------------
+ * d(i, j) = entry [i][j] of the matrix hulk_smash gives (sketch i the subject), bit for bit.  Sketches i != j are LINKED when
+ * d(i, j) <= max_distance or d(j, i) <= max_distance: the compare is on the double itself, a NaN never links, a distance equal to the
+ * threshold does.  (jaccard: both directions are the same bits; weightedjaccard uses the subject's weights on both sides, so they are
+ * not, and one direction is enough.)  A cluster is a connected component of that graph; label[i] is the smallest index in i's
+ * component — a function of the inputs alone: bands, tiles, scheduling and timing cannot change it.  stats->links: the number of
+ * ordered pairs (i, j), i != j, with d(i, j) <= max_distance; stats->clusters: the number of i with label[i] == i.
+ * The whole set is prepared once and stays on the device (16 * sketch_size bytes a sketch; with the raw upload the peak is
+ * 32 * sketch_size * n bytes; that and HULK_CLUSTER_MAX_N limit n); no n x n array exists.  k_cluster_link (hulk_cluster.hip) is launched once per
+ * band of band_rows subject rows, a lock-free union-find keeps the components.
+ * HULK_ERR_ARG before any HIP call, with a text in hulk_last_error(NULL): NULL arrays or opts; n or sketch_size == 0; an unknown
+ * metric; max_distance outside [0, 1] (NaN included); band_rows not a multiple of 32; non-zero flags or reserved; n above
+ * HULK_CLUSTER_MAX_N (the set is prepared in one launch).  n == 1 is valid: one cluster, 0 links. */
+#define HULK_CLUSTER_MAX_N 2097088u
+typedef struct hulk_cluster_opts {
+    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD */
+    double max_distance;   /* tau in [0, 1]; anything else (NaN included): HULK_ERR_ARG */
+    uint32_t band_rows;    /* subject rows per launch; 0 = default (2048, search's block); a multiple of 32 (above 2^20: 2^20) */
+    uint32_t flags;        /* zero */
+    uint64_t reserved[4];  /* zero */
+} hulk_cluster_opts;
+typedef struct hulk_cluster_stats {
+    double seconds_total, kernel_ms_link, kernel_ms_flatten;   /* the whole call; k_cluster_link / k_cluster_flatten summed over the bands (HIP events) */
+    uint64_t links;
+    uint32_t bands, clusters;
+} hulk_cluster_stats;
+int hulk_cluster(int device, const uint64_t *mins, const double *weights, uint32_t n, uint32_t sketch_size,
+                 const hulk_cluster_opts *opts, uint32_t *label, hulk_cluster_stats *stats);
+/* The directory form: the files go through hulk_load_sketches' loader (MD5, FindSketch, the reference's error texts; sorted unique
+ * paths; a set of ONE sketch is valid).  metric: "jaccard" | "weightedjaccard" (histosketches only: hulk_smash_files' text); algo:
+ * "histosketch" | "kmv" | "khf".  label [unique paths] may be NULL.  csv_path != NULL: a file with the header
+ * "sketch,cluster,size,representative" and one line per sketch in sorted path order: its path, the 1-based ordinal of its cluster
+ * (clusters ordered by their smallest member), the cluster's member count, the path of its smallest member; paths as encoding/csv
+ * quotes them. */
+int hulk_cluster_files(int device, const char *const *paths, uint32_t n, uint32_t ksize, const char *algo, const char *metric,
+                       double max_distance, uint32_t threads, const char *csv_path, uint32_t *label,
+                       hulk_cluster_stats *stats, char *errbuf, uint64_t errbuf_len);
 
 /* Device self-test: the jump hash replaces the fp64 division 2^31/r by a Newton reciprocal; this
  * checks RN(1/r) against IEEE division for EVERY r in [1, 2^31] and returns the mismatch count. */
