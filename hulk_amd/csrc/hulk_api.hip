@@ -1,7 +1,7 @@
 // hulk_api.hip — the C ABI of libhulkhip.so (see include/hulk_hip.h for the reference seam each entry point replaces):
 // context creation, the AddSeq variants, Flush / finish, the getters, profiling, `hulk smash`.  Orchestration of a batch is
 // hulk_flush.hip, the tables hulk_tables.hip, the multi-GPU entry points hulk_comm.hip (hulk_ctx.h maps the pieces).
-#include "hulk_ctx.h"
+#include "hulk_oneshot.h"
 
 #include <mutex>
 
@@ -653,15 +653,12 @@ SmashBuffers g_smash;
 int hulk_smash_ex(int device, const uint64_t *mins, const double *weights, uint32_t n_sketches, uint32_t sketch_size,
                   int metric, double *distances, double *kernel_ms) {
     if (!mins || !weights || !distances) return fail(nullptr, HULK_ERR_ARG, "NULL");
-    if (metric != HULK_METRIC_JACCARD && metric != HULK_METRIC_WEIGHTED_JACCARD) return fail(nullptr, HULK_ERR_ARG, "metric");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, HULK_ERR_NO_DEVICE);
-    if (device < 0 || device >= ndev) return fail(nullptr, HULK_ERR_ARG, "device ordinal");
+    if (!metric_ok(metric)) return fail(nullptr, HULK_ERR_ARG, "metric");
+    if (const int rc = oneshot_device(device)) return rc;
     std::lock_guard<std::mutex> lock(g_smash.mu);
     SmashBuffers &B = g_smash;
 #define SM_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { B.drop(); return fail_hip(nullptr, e_, #call); } } while (0)
     const size_t NS = (size_t)n_sketches * sketch_size, NN = (size_t)n_sketches * n_sketches;
-    SM_CHK(hipSetDevice(device));
     if (B.device != device) { B.drop(); B.device = device; }
     if (NS > B.cap_ns || !B.d_m) {
         hipFree(B.d_m); hipFree(B.d_w); B.d_m = nullptr; B.d_w = nullptr; B.cap_ns = 0;

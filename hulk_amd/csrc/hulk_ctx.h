@@ -6,7 +6,7 @@
 //   hulk_snapshot.hip  sketch snapshots: planning them into a flush, the ring, delivery (hulk_set_snapshots ...)
 //   hulk_comm.hip    multi-GPU: RCCL binding, host / loopback transports, hulk_step_sharded / hulk_step_sliced, gather
 // Host code only: every numeric step of the path runs in the kernels of hulk_minimizer / hulk_spectrum / hulk_countmin /
-// hulk_cws .hip; there is no CPU fallback.
+// hulk_cws / hulk_pairwise .hip; there is no CPU fallback.
 #pragma once
 #include "../../include/hulk_hip.h"
 #include "hulk_internal.h"
@@ -191,6 +191,9 @@ int fail_hip(hulk_ctx *c, hipError_t e, const char *what);
 #define HIPCHK(c, call)                                             \
     do { hipError_t e_ = (call); if (e_ != hipSuccess) return hulk::fail_hip((c), e_, #call); } while (0)
 template <typename T> hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, n ? n * sizeof(T) : sizeof(T)); }
+// the two metrics and the two roles of the pairwise entry points (hulk_smash, the panel, hulk_search, hulk_cluster)
+inline bool metric_ok(int metric) { return metric == HULK_METRIC_JACCARD || metric == HULK_METRIC_WEIGHTED_JACCARD; }
+inline bool role_ok(int role) { return role == HULK_PANEL_ROW || role == HULK_PANEL_COLUMN; }
 
 // ---- hulk_tables.hip
 int build_chains(hulk_ctx *c);

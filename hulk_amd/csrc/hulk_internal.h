@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <chrono>
 
 // Experiment switches (HULK_JUMP_*, HULK_NIB_*, HULK_NO_FMIN, HULK_K1_DEBUG, HULK_POISON, the HULK_NO_* / HULK_BATCH overrides
 // of hulk_params fields ... docs/EXPERIMENTS.md) exist only in the profiling build, `make EXPERIMENTS=1` ->
@@ -213,6 +214,9 @@ hipError_t launch_add_hist(hipStream_t s, uint32_t *d_hist, const uint32_t *d_ad
 // (ProfScope, hulk_flush.hip) an event is recorded on the stream in front of it, and a kernel's duration is the time to the
 // next mark on the same stream ("-" closes a chain).  Meant for the one-stream mode (HULK_FLAG_NO_OVERLAP): every kernel alone.
 void prof_mark(hipStream_t s, const char *kernel);
+
+// seconds on the steady clock (the `seconds_*` of the stats structs)
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // context accessors for hulk_ingest_device.hip (defined in hulk_flush.hip; not part of the ABI)
 }  // namespace hulk

@@ -1,33 +1,31 @@
 // hulk_search.hip — nearest-neighbour search of sketches against a database (hulk_search): for every query the K closest database
-// sketches, HULKdata.GetDistance exactly as k_smash (hulk_cws.hip) computes it, without an M x P array anywhere.
+// sketches, HULKdata.GetDistance exactly as k_smash (hulk_pairwise.hip) computes it, without an M x P array anywhere.
 //   the queries     prepared once, slot-major doubles qmT / qwT [slot][QP] (k_smash_prep's layout: (double)min and |w|, zero rows
 //                   behind M; QP = M rounded up to 64), resident for the call
 //   the database    streams through the device in strips of Pb sketches: upload -> k_smash_prep -> per block of Mb queries
 //                   k_search_dist (distances of the block x the strip into the scratch [Mb][Pb]) -> k_search_select (the
 //                   running lists of the block's queries).  Device memory: the queries + scratch_bytes, whatever n_db is
-//   k_search_dist   k_smash's register tile over two different sets: a thread owns 4 subjects x 4 others, a workgroup of 128
-//                   threads 32 subjects x 64 others; chunks of 32 slots go through LDS as [slot][row] in two buffers, chunk n+1
-//                   is loaded into registers before chunk n is computed, one barrier per chunk, six ds_read_b128 per slot and
-//                   thread, 16 accumulators that add in slot order.  The SUBJECT side supplies mins, |w| and the union, the other
-//                   side mins only: ROLE row = the queries are the subjects, ROLE column = the strip's sketches are (for jaccard
-//                   the two are one kernel).  Tails in M, P and S are zero rows / columns as in k_smash; nothing outside
-//                   block x strip is written
+//   k_search_dist   the pair tile of hulk_pairtile.h (k_smash's loop: a workgroup of 128 threads owns 32 subjects x 64 others, 16
+//                   accumulators a thread that add in slot order; layout and contract are written there) over two different sets.
+//                   The SUBJECT side supplies mins, |w| and the union, the other side mins only: ROLE row = the queries are the
+//                   subjects, ROLE column = the strip's sketches are (for jaccard the two are one kernel).  Tails in M, P and S
+//                   are zero rows / columns as in k_smash; nothing outside block x strip is written
 //   k_search_select a wave owns a query: lane l < K holds entry l of its list, sorted by the 96-bit key (distance bits, database
 //                   index) — a non-negative, non-NaN double orders like its uint64 bits.  It reads the strip's row 64 values at
 //                   a time (coalesced, eight such loads in flight), rejects against the K-th key (after the first strip nearly everything fails this one
 //                   compare), takes the survivors of a ballot in lane order and inserts each: its rank in the list is a ballot's
 //                   population count, the tail moves up one lane.  The compare is the full key, so the list is a function of the
 //                   set of pairs alone: no atomics, no appends, no dependence on strips, blocks or scheduling
-#include "hulk_ctx.h"
+#include "hulk_oneshot.h"
+#include "hulk_pairtile.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 
 namespace hulk {
 namespace {
 
-constexpr int SEARCH_TS = 32, SEARCH_TQ = 64, SEARCH_CH = 32, SEARCH_PAD = 2, SELECT_AHEAD = 8;
+constexpr int SELECT_AHEAD = 8;
 
 // a: the subject side, slot-major [S][AP], columns a0 .. a0 + na of it; b: the other side [S][BP], columns b0 .. b0 + nb.
 // out[q][p], pitch doubles per query row: COLUMN 0 the subjects are the queries (q = a, p = b), COLUMN 1 the others are.
@@ -36,80 +34,18 @@ template <int METRIC, int COLUMN>
 __global__ __launch_bounds__(128) void k_search_dist(const double *__restrict__ aT, const double *__restrict__ awT, uint32_t AP, uint32_t a0,
                                                      uint32_t na, const double *__restrict__ bT, uint32_t BP, uint32_t b0, uint32_t nb,
                                                      uint32_t S, double *__restrict__ out, uint32_t pitch) {
-    __shared__ __align__(16) double ma[2][SEARCH_CH][SEARCH_TS + SEARCH_PAD], wa[METRIC == 1 ? 2 : 1][METRIC == 1 ? SEARCH_CH : 1][SEARCH_TS + SEARCH_PAD];
-    __shared__ __align__(16) double mb[2][SEARCH_CH][SEARCH_TQ + SEARCH_PAD];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;     // other quad, subject quad inside the tile
-    const uint32_t s0 = blockIdx.y * SEARCH_TS, q0 = blockIdx.x * SEARCH_TQ;    // tile origin, relative to a0 / b0
-    // staging: thread t moves slot (t / 4) of the chunk: 8 subject rows (mins, weights) and 16 other rows from (t % 4) on
-    const int lc = tid >> 2, lr = tid & 3;
+    const uint32_t s0 = blockIdx.y * PAIR_TS, q0 = blockIdx.x * PAIR_TQ;        // tile origin, relative to a0 / b0
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        uni[i] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) { acc[i][j] = 0.0; cnt[i][j] = 0; }
-    }
-    double2 ra[4], rw[4], rb[8];
-    auto fetch = [&](uint32_t c0) {
-        const uint32_t col = c0 + (uint32_t)lc;
-        const bool ok = col < S;
-        const double2 *pa = (const double2 *)(aT + (size_t)col * AP + a0 + s0 + 8 * lr);
-        const double2 *pw = (const double2 *)(awT + (size_t)col * AP + a0 + s0 + 8 * lr);
-        const double2 *pb = (const double2 *)(bT + (size_t)col * BP + b0 + q0 + 16 * lr);
-#pragma unroll
-        for (int x = 0; x < 4; x++) { ra[x] = ok ? pa[x] : make_double2(0.0, 0.0); if constexpr (METRIC == 1) rw[x] = ok ? pw[x] : make_double2(0.0, 0.0); }
-#pragma unroll
-        for (int x = 0; x < 8; x++) rb[x] = ok ? pb[x] : make_double2(0.0, 0.0);
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int x = 0; x < 4; x++) { *(double2 *)&ma[buf][lc][8 * lr + 2 * x] = ra[x]; if constexpr (METRIC == 1) *(double2 *)&wa[buf][lc][8 * lr + 2 * x] = rw[x]; }
-#pragma unroll
-        for (int x = 0; x < 8; x++) *(double2 *)&mb[buf][lc][16 * lr + 2 * x] = rb[x];
-    };
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    int buf = 0;
-    for (uint32_t c0 = 0; c0 < S; c0 += SEARCH_CH, buf ^= 1) {
-        const bool more = c0 + SEARCH_CH < S;
-        if (more) fetch(c0 + SEARCH_CH);                            // in flight under this chunk's arithmetic
-        const uint32_t lim = S - c0 < (uint32_t)SEARCH_CH ? S - c0 : (uint32_t)SEARCH_CH;
-#pragma unroll 2
-        for (uint32_t c = 0; c < lim; c++) {
-            const double2 a01 = *(const double2 *)&ma[buf][c][4 * ty], a23 = *(const double2 *)&ma[buf][c][4 * ty + 2];
-            const double2 b01 = *(const double2 *)&mb[buf][c][4 * tx], b23 = *(const double2 *)&mb[buf][c][4 * tx + 2];
-            const double a[4] = {a01.x, a01.y, a23.x, a23.y}, b[4] = {b01.x, b01.y, b23.x, b23.y};
-            if constexpr (METRIC == 1) {
-                const double2 w01 = *(const double2 *)&wa[buf][c][4 * ty], w23 = *(const double2 *)&wa[buf][c][4 * ty + 2];
-                const double w[4] = {w01.x, w01.y, w23.x, w23.y};
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    uni[i] += w[i];                                 // the subject's |w|, whatever the other sketch
-#pragma unroll
-                    for (int j = 0; j < 4; j++) acc[i][j] += (a[i] == b[j]) ? w[i] : 0.0;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++) cnt[i][j] += (a[i] == b[j]) ? 1u : 0u;      // a count of 1.0s is exact in fp64
-            }
-        }
-        if (more) stash(buf ^ 1);                                   // (the other buffer: nobody reads it during this chunk)
-        __syncthreads();
-    }
+    pair_tile<METRIC>(aT, awT, AP, a0 + s0, bT, BP, b0 + q0, S, acc, uni, cnt);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t s = s0 + 4 * ty + i;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t q = q0 + 4 * tx + j;
-            if (s < na && q < nb) {
-                const double d = METRIC == 1 ? 1 - (acc[i][j] / uni[i]) : 1.0 - ((double)cnt[i][j] / (double)S);
-                out[COLUMN ? (size_t)q * pitch + s : (size_t)s * pitch + q] = d;
-            }
+            if (s < na && q < nb) out[COLUMN ? (size_t)q * pitch + s : (size_t)s * pitch + q] = pair_distance<METRIC>(acc[i][j], uni[i], cnt[i][j], S);
         }
     }
 }
@@ -159,8 +95,6 @@ __global__ __launch_bounds__(256) void k_search_select(const double *__restrict_
     if (lane < K) { lkey[(size_t)q * K + lane] = kd; lidx[(size_t)q * K + lane] = ki; }
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 constexpr uint64_t SEARCH_DEFAULT_SCRATCH = 1ull << 30;
 constexpr uint32_t SEARCH_MAX_MB = 2048, SEARCH_MAX_PB = 1u << 20;   // (Pb / 32 and Mb / 32 are grid.y of k_search_dist)
 
@@ -183,10 +117,10 @@ template <int METRIC, int COLUMN>
 void search_dist(const double *qmT, const double *qwT, uint32_t QP, uint32_t qb, uint32_t mq, const double *dmT, const double *dwT,
                  uint32_t DP, uint32_t np, uint32_t S, double *d_dist, uint32_t pitch) {
     if (COLUMN)
-        hipLaunchKernelGGL((k_search_dist<METRIC, 1>), dim3((mq + SEARCH_TQ - 1) / SEARCH_TQ, (np + SEARCH_TS - 1) / SEARCH_TS), dim3(128), 0, nullptr,
+        hipLaunchKernelGGL((k_search_dist<METRIC, 1>), dim3((mq + PAIR_TQ - 1) / PAIR_TQ, (np + PAIR_TS - 1) / PAIR_TS), dim3(128), 0, nullptr,
                            dmT, dwT, DP, 0u, np, qmT, QP, qb, mq, S, d_dist, pitch);
     else
-        hipLaunchKernelGGL((k_search_dist<METRIC, 0>), dim3((np + SEARCH_TQ - 1) / SEARCH_TQ, (mq + SEARCH_TS - 1) / SEARCH_TS), dim3(128), 0, nullptr,
+        hipLaunchKernelGGL((k_search_dist<METRIC, 0>), dim3((np + PAIR_TQ - 1) / PAIR_TQ, (mq + PAIR_TS - 1) / PAIR_TS), dim3(128), 0, nullptr,
                            qmT, qwT, QP, qb, mq, dmT, DP, 0u, np, S, d_dist, pitch);
 }
 
@@ -202,8 +136,8 @@ extern "C" int hulk_search(int device, const uint64_t *q_mins, const double *q_w
     if (!q_mins || !q_weights || !opts || !hit_index || !hit_distance || !hit_count) return fail(nullptr, HULK_ERR_ARG, "hulk_search: NULL");
     const uint32_t K = opts->k;
     if (K == 0 || K > HULK_SEARCH_MAX_K) return fail(nullptr, HULK_ERR_ARG, "hulk_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
-    if (opts->metric != HULK_METRIC_JACCARD && opts->metric != HULK_METRIC_WEIGHTED_JACCARD) return fail(nullptr, HULK_ERR_ARG, "hulk_search: metric");
-    if (opts->role != HULK_PANEL_ROW && opts->role != HULK_PANEL_COLUMN) return fail(nullptr, HULK_ERR_ARG, "hulk_search: role");
+    if (!metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: metric");
+    if (!role_ok(opts->role)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: role");
     if (opts->flags & ~HULK_SEARCH_SELF) return fail(nullptr, HULK_ERR_ARG, "hulk_search: unknown flags");
     for (uint64_t x : opts->reserved) if (x) return fail(nullptr, HULK_ERR_ARG, "hulk_search: reserved fields must be zero");
     const bool self = (opts->flags & HULK_SEARCH_SELF) != 0;
@@ -217,69 +151,57 @@ extern "C" int hulk_search(int device, const uint64_t *q_mins, const double *q_w
         return fail(nullptr, HULK_ERR_ARG, "hulk_search: scratch_bytes " + std::to_string(opts->scratch_bytes) + " is too small for one tile (" +
                                                std::to_string(64ull * ((uint64_t)S * 32 + 32 * 8)) + " bytes at this sketch size)");
     const double t0 = now_s();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, HULK_ERR_NO_DEVICE);
-    if (device < 0 || device >= ndev) return fail(nullptr, HULK_ERR_ARG, "device ordinal");
+    if (const int rc = oneshot_device(device)) return rc;
     const double lim = (opts->max_distance >= 0.0 && opts->max_distance <= 1.0) ? opts->max_distance : INFINITY;
     const int metric = opts->metric, column = metric == HULK_METRIC_WEIGHTED_JACCARD && opts->role == HULK_PANEL_COLUMN;
     const uint32_t QP = smash_padded_n(m), DP = smash_padded_n(Pb);
     // (+ 64: with query blocks of 32 a 64-wide tile of ROLE column starts in the middle of the last 64 columns and reads up to 32
     // doubles past a slot's row — the next slot's, or these behind the last one; such columns are computed and never stored)
     const size_t QT = (size_t)QP * S + 64, DT = (size_t)DP * S, MS = (size_t)m * S, LK = (size_t)m * K;
+    OneShot own;
     unsigned long long *d_raw_m = nullptr, *d_lkey = nullptr; double *d_raw_w = nullptr, *d_qmT = nullptr, *d_qwT = nullptr, *d_dmT = nullptr, *d_dwT = nullptr, *d_dist = nullptr;
     uint32_t *d_lidx = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    auto done = [&](int rc) {
-        hipFree(d_raw_m); hipFree(d_raw_w); hipFree(d_qmT); hipFree(d_qwT); hipFree(d_dmT); hipFree(d_dwT); hipFree(d_dist); hipFree(d_lkey); hipFree(d_lidx);
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-        return rc;
-    };
-#define SR_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return done(fail_hip(nullptr, e_, #call)); } while (0)
-    SR_CHK(hipSetDevice(device));
-    for (hipEvent_t &e : ev) SR_CHK(hipEventCreate(&e));
+    for (hipEvent_t &e : ev) ONESHOT_CHK(own.event(&e));
     // the raw staging serves the queries first, then every strip
     const size_t RAW = std::max(MS, (size_t)Pb * S);
-    SR_CHK(hipMalloc((void **)&d_raw_m, RAW * 8)); SR_CHK(hipMalloc((void **)&d_raw_w, RAW * 8));
-    SR_CHK(hipMalloc((void **)&d_qmT, QT * 8)); SR_CHK(hipMalloc((void **)&d_qwT, QT * 8));
-    SR_CHK(hipMalloc((void **)&d_dmT, DT * 8)); SR_CHK(hipMalloc((void **)&d_dwT, DT * 8));
-    SR_CHK(hipMalloc((void **)&d_dist, (size_t)Mb * Pb * 8));
-    SR_CHK(hipMalloc((void **)&d_lkey, LK * 8)); SR_CHK(hipMalloc((void **)&d_lidx, LK * 4));
-    SR_CHK(hipMemset(d_lkey, 0xff, LK * 8)); SR_CHK(hipMemset(d_lidx, 0xff, LK * 4));
-    SR_CHK(hipMemset(d_qmT + (size_t)QP * S, 0, 64 * 8)); SR_CHK(hipMemset(d_qwT + (size_t)QP * S, 0, 64 * 8));
-    SR_CHK(hipMemcpy(d_raw_m, q_mins, MS * 8, hipMemcpyHostToDevice)); SR_CHK(hipMemcpy(d_raw_w, q_weights, MS * 8, hipMemcpyHostToDevice));
-    SR_CHK(launch_panel_prep(nullptr, d_raw_m, d_raw_w, m, S, d_qmT, d_qwT));
+    ONESHOT_CHK(own.alloc(&d_raw_m, RAW)); ONESHOT_CHK(own.alloc(&d_raw_w, RAW));
+    ONESHOT_CHK(own.alloc(&d_qmT, QT)); ONESHOT_CHK(own.alloc(&d_qwT, QT));
+    ONESHOT_CHK(own.alloc(&d_dmT, DT)); ONESHOT_CHK(own.alloc(&d_dwT, DT));
+    ONESHOT_CHK(own.alloc(&d_dist, (size_t)Mb * Pb));
+    ONESHOT_CHK(own.alloc(&d_lkey, LK)); ONESHOT_CHK(own.alloc(&d_lidx, LK));
+    ONESHOT_CHK(hipMemset(d_lkey, 0xff, LK * 8)); ONESHOT_CHK(hipMemset(d_lidx, 0xff, LK * 4));
+    ONESHOT_CHK(hipMemset(d_qmT + (size_t)QP * S, 0, 64 * 8)); ONESHOT_CHK(hipMemset(d_qwT + (size_t)QP * S, 0, 64 * 8));
+    ONESHOT_CHK(upload_prepared(nullptr, q_mins, q_weights, m, S, d_raw_m, d_raw_w, d_qmT, d_qwT));
     double ms_dist = 0.0, ms_select = 0.0;
     uint32_t strips = 0, blocks = 0;
     for (uint64_t p0 = 0; p0 < n_db; p0 += Pb, strips++) {
         const uint32_t np = (uint32_t)std::min<uint64_t>(Pb, n_db - p0);
         // (hipMemcpy on the null stream: behind the kernels that read the previous strip)
-        SR_CHK(hipMemcpy(d_raw_m, db_mins + (size_t)p0 * S, (size_t)np * S * 8, hipMemcpyHostToDevice));
-        SR_CHK(hipMemcpy(d_raw_w, db_weights + (size_t)p0 * S, (size_t)np * S * 8, hipMemcpyHostToDevice));
-        SR_CHK(launch_panel_prep(nullptr, d_raw_m, d_raw_w, np, S, d_dmT, d_dwT));
+        ONESHOT_CHK(upload_prepared(nullptr, db_mins + (size_t)p0 * S, db_weights + (size_t)p0 * S, np, S, d_raw_m, d_raw_w, d_dmT, d_dwT));
         const uint32_t NP = smash_padded_n(np);                     // the pitch k_smash_prep gave this strip
         blocks = 0;
         for (uint32_t qb = 0; qb < m; qb += Mb, blocks++) {
             const uint32_t mq = std::min(Mb, m - qb);
-            SR_CHK(hipEventRecord(ev[0], nullptr));
+            ONESHOT_CHK(hipEventRecord(ev[0], nullptr));
             if (metric != HULK_METRIC_WEIGHTED_JACCARD) search_dist<0, 0>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
             else if (column) search_dist<1, 1>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
             else search_dist<1, 0>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
-            SR_CHK(hipGetLastError());
-            SR_CHK(hipEventRecord(ev[1], nullptr));
+            ONESHOT_CHK(hipGetLastError());
+            ONESHOT_CHK(hipEventRecord(ev[1], nullptr));
             hipLaunchKernelGGL(k_search_select, dim3((mq + 3) / 4), dim3(256), 0, nullptr, d_dist, Pb, mq, np, qb, (uint32_t)p0, K, lim,
                                self ? 1u : 0u, d_lkey, d_lidx);
-            SR_CHK(hipGetLastError());
-            SR_CHK(hipEventRecord(ev[2], nullptr));
-            SR_CHK(hipEventSynchronize(ev[2]));
+            ONESHOT_CHK(hipGetLastError());
+            ONESHOT_CHK(hipEventRecord(ev[2], nullptr));
+            ONESHOT_CHK(hipEventSynchronize(ev[2]));
             float a = 0, b = 0;
-            SR_CHK(hipEventElapsedTime(&a, ev[0], ev[1])); SR_CHK(hipEventElapsedTime(&b, ev[1], ev[2]));
+            ONESHOT_CHK(hipEventElapsedTime(&a, ev[0], ev[1])); ONESHOT_CHK(hipEventElapsedTime(&b, ev[1], ev[2]));
             ms_dist += a; ms_select += b;
         }
     }
     std::vector<unsigned long long> keys(LK);
-    SR_CHK(hipMemcpy(keys.data(), d_lkey, LK * 8, hipMemcpyDeviceToHost));
-    SR_CHK(hipMemcpy(hit_index, d_lidx, LK * 4, hipMemcpyDeviceToHost));
-#undef SR_CHK
+    ONESHOT_CHK(hipMemcpy(keys.data(), d_lkey, LK * 8, hipMemcpyDeviceToHost));
+    ONESHOT_CHK(hipMemcpy(hit_index, d_lidx, LK * 4, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < m; i++) {
         uint32_t n = 0;
         for (uint32_t j = 0; j < K; j++) {
@@ -290,5 +212,5 @@ extern "C" int hulk_search(int device, const uint64_t *q_mins, const double *q_w
         hit_count[i] = n;
     }
     if (stats) { stats->seconds_total = now_s() - t0; stats->kernel_ms_dist = ms_dist; stats->kernel_ms_select = ms_select; stats->strips = strips; stats->query_blocks = blocks; }
-    return done(HULK_OK);
+    return HULK_OK;
 }

@@ -1,5 +1,5 @@
 // hulk_smashio.hip — the directory form of `hulk smash` in native code (host side; the N x N x S comparison itself is k_smash,
-// hulk_cws.hip): LoadHULKdata for every sketch file on a pool of threads (src/sketchio/sketchio.go:100-195: parse the JSON,
+// hulk_pairwise.hip): LoadHULKdata for every sketch file on a pool of threads (src/sketchio/sketchio.go:100-195: parse the JSON,
 // class / version checks, MD5 of the little-endian mins against the stored md5sum, src/helpers/helpers.go:156-166),
 // FindSketch per file (sketchio.go:198-257), the length check of GetDistance (sketchio.go:274-277), the matrix on the GPU and
 // the CSV encoding/csv would write (cmd/smash.go:183-226).  Error texts are the reference's.  Until round 6 this was a serial
@@ -12,7 +12,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <thread>
 
@@ -475,8 +474,6 @@ int put_err(char *errbuf, uint64_t errbuf_len, int code, const std::string &msg)
     return code;
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace
 }  // namespace hulk
 
@@ -646,7 +643,7 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
     if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
     if (k == 0 || k > HULK_SEARCH_MAX_K) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
-    if (role != HULK_PANEL_ROW && role != HULK_PANEL_COLUMN) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: role");
+    if (!role_ok(role)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: role");
     if (flags & ~HULK_SEARCH_SELF) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: unknown flags");
     const bool self = (flags & HULK_SEARCH_SELF) != 0;
     if (self && (db_paths || n_db)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: HULK_SEARCH_SELF takes no database");

@@ -9,9 +9,9 @@
 //                    flush stream copies their entries into a pinned mirror and records an event; the entry points of the step
 //                    path query the events of the queued flushes and hand what has arrived to the callback from the mirror
 //   the panel        hulk_set_panel: reference sketches held on the device slot-major; behind the kernels of a flush that recorded
-//                    snapshots k_snap_panel (hulk_cws.hip) scores them against it into a distance ring [cap][n_panel] that
+//                    snapshots k_snap_panel (hulk_pairwise.hip) scores them against it into a distance ring [cap][n_panel] that
 //                    shares the snapshot ring's indices, mirror and delivery
-#include "hulk_ctx.h"
+#include "hulk_oneshot.h"
 
 #include <algorithm>
 
@@ -213,31 +213,29 @@ int hulk_set_panel(hulk_ctx *c, const uint64_t *mins, const double *weights, uin
     if (c->seq_count || c->flush_index || c->finished) return fail(c, HULK_ERR_STATE, "the panel must be set before the first read");
     if (n_panel == 0) { panel_teardown(c); return HULK_OK; }
     if (!mins || !weights) return fail(c, HULK_ERR_ARG, "NULL");
-    if (metric != HULK_METRIC_JACCARD && metric != HULK_METRIC_WEIGHTED_JACCARD) return fail(c, HULK_ERR_ARG, "metric");
-    if (role != HULK_PANEL_ROW && role != HULK_PANEL_COLUMN) return fail(c, HULK_ERR_ARG, "panel role");
+    if (!metric_ok(metric)) return fail(c, HULK_ERR_ARG, "metric");
+    if (!role_ok(role)) return fail(c, HULK_ERR_ARG, "panel role");
     if (sketch_size != c->S) return fail(c, HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(c->S) + " vs " + std::to_string(sketch_size) + "\n");
     if (n_panel > HULK_PANEL_MAX) return fail(c, HULK_ERR_ARG, "panel of " + std::to_string(n_panel) + " sketches (at most " + std::to_string(HULK_PANEL_MAX) + ")");
     panel_teardown(c);
     hulk_ctx::Snapshots::Panel &P = c->snap.panel;
     const size_t NS = (size_t)n_panel * sketch_size, NT = (size_t)smash_padded_n(n_panel) * sketch_size, ND = (size_t)c->snap.cap * n_panel;
+    OneShot own;                                                    // the raw upload; the panel's arrays belong to the context
     unsigned long long *d_m = nullptr; double *d_w = nullptr;
     auto bail = [&](hipError_t e, const char *what) {
         const int rc = fail_hip(c, e, what); const std::string msg = c->last_error;
-        hipFree(d_m); hipFree(d_w); panel_teardown(c); c->last_error = msg; return rc;
+        panel_teardown(c); c->last_error = msg; return rc;
     };
     hipError_t e;
-    if ((e = hipMalloc((void **)&d_m, NS * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
-    if ((e = hipMalloc((void **)&d_w, NS * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
+    if ((e = own.alloc(&d_m, NS)) != hipSuccess) return bail(e, "hipMalloc(panel)");
+    if ((e = own.alloc(&d_w, NS)) != hipSuccess) return bail(e, "hipMalloc(panel)");
     if ((e = hipMalloc((void **)&P.d_mT, NT * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
     if ((e = hipMalloc((void **)&P.d_wT, NT * 8)) != hipSuccess) return bail(e, "hipMalloc(panel)");
     if ((e = hipMalloc((void **)&P.d_dist, ND * 8)) != hipSuccess) return bail(e, "hipMalloc(panel distances)");
     if ((e = hipHostMalloc((void **)&P.h_dist, ND * 8, hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc(panel distances)");
-    if ((e = hipMemcpy(d_m, mins, NS * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(panel)");
-    if ((e = hipMemcpy(d_w, weights, NS * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(panel)");
     if ((e = hipMemsetAsync(P.d_dist, 0, ND * 8, c->stream)) != hipSuccess) return bail(e, "hipMemsetAsync(panel distances)");
-    if ((e = launch_panel_prep(c->stream, d_m, d_w, n_panel, sketch_size, P.d_mT, P.d_wT)) != hipSuccess) return bail(e, "k_smash_prep(panel)");
+    if ((e = upload_prepared(c->stream, mins, weights, n_panel, sketch_size, d_m, d_w, P.d_mT, P.d_wT)) != hipSuccess) return bail(e, "upload_prepared(panel)");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize(panel)");
-    hipFree(d_m); hipFree(d_w);
     P.n = n_panel; P.metric = metric; P.role = role;
     return HULK_OK;
 }
@@ -265,33 +263,27 @@ int hulk_get_snapshot_distances(hulk_ctx *c, uint64_t first, uint32_t n, double 
 
 int hulk_panel_distances(int device, const uint64_t *snap_mins, const double *snap_weights, uint32_t m, const uint64_t *panel_mins,
                          const double *panel_weights, uint32_t n_panel, uint32_t sketch_size, int metric, int role, double *out) {
-    if (metric != HULK_METRIC_JACCARD && metric != HULK_METRIC_WEIGHTED_JACCARD) return fail(nullptr, HULK_ERR_ARG, "metric");
-    if (role != HULK_PANEL_ROW && role != HULK_PANEL_COLUMN) return fail(nullptr, HULK_ERR_ARG, "panel role");
+    if (!metric_ok(metric)) return fail(nullptr, HULK_ERR_ARG, "metric");
+    if (!role_ok(role)) return fail(nullptr, HULK_ERR_ARG, "panel role");
     if (n_panel > HULK_PANEL_MAX) return fail(nullptr, HULK_ERR_ARG, "panel of " + std::to_string(n_panel) + " sketches (at most " + std::to_string(HULK_PANEL_MAX) + ")");
     if (!sketch_size) return fail(nullptr, HULK_ERR_ARG, "sketch_size");
     if (!m || !n_panel) return HULK_OK;
     if (!snap_mins || !snap_weights || !panel_mins || !panel_weights || !out) return fail(nullptr, HULK_ERR_ARG, "NULL");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, HULK_ERR_NO_DEVICE);
-    if (device < 0 || device >= ndev) return fail(nullptr, HULK_ERR_ARG, "device ordinal");
+    if (const int rc = oneshot_device(device)) return rc;
     const size_t S = sketch_size, MS = (size_t)m * S, NS = (size_t)n_panel * S, NT = (size_t)smash_padded_n(n_panel) * S, MP = (size_t)m * n_panel;
+    OneShot own;
     unsigned long long *d_sm = nullptr, *d_pm = nullptr; double *d_sw = nullptr, *d_pw = nullptr, *d_mT = nullptr, *d_wT = nullptr, *d_out = nullptr;
-    auto done = [&](int rc) { hipFree(d_sm); hipFree(d_sw); hipFree(d_pm); hipFree(d_pw); hipFree(d_mT); hipFree(d_wT); hipFree(d_out); return rc; };
-#define PD_CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return done(fail_hip(nullptr, e_, #call)); } while (0)
-    PD_CHK(hipSetDevice(device));
-    PD_CHK(hipMalloc((void **)&d_sm, MS * 8)); PD_CHK(hipMalloc((void **)&d_sw, MS * 8));
-    PD_CHK(hipMalloc((void **)&d_pm, NS * 8)); PD_CHK(hipMalloc((void **)&d_pw, NS * 8));
-    PD_CHK(hipMalloc((void **)&d_mT, NT * 8)); PD_CHK(hipMalloc((void **)&d_wT, NT * 8));
-    PD_CHK(hipMalloc((void **)&d_out, MP * 8));
-    PD_CHK(hipMemcpy(d_sm, snap_mins, MS * 8, hipMemcpyHostToDevice)); PD_CHK(hipMemcpy(d_sw, snap_weights, MS * 8, hipMemcpyHostToDevice));
-    PD_CHK(hipMemcpy(d_pm, panel_mins, NS * 8, hipMemcpyHostToDevice)); PD_CHK(hipMemcpy(d_pw, panel_weights, NS * 8, hipMemcpyHostToDevice));
-    PD_CHK(launch_panel_prep(nullptr, d_pm, d_pw, n_panel, sketch_size, d_mT, d_wT));
+    ONESHOT_CHK(own.alloc(&d_sm, MS)); ONESHOT_CHK(own.alloc(&d_sw, MS));
+    ONESHOT_CHK(own.alloc(&d_pm, NS)); ONESHOT_CHK(own.alloc(&d_pw, NS));
+    ONESHOT_CHK(own.alloc(&d_mT, NT)); ONESHOT_CHK(own.alloc(&d_wT, NT));
+    ONESHOT_CHK(own.alloc(&d_out, MP));
+    ONESHOT_CHK(hipMemcpy(d_sm, snap_mins, MS * 8, hipMemcpyHostToDevice)); ONESHOT_CHK(hipMemcpy(d_sw, snap_weights, MS * 8, hipMemcpyHostToDevice));
+    ONESHOT_CHK(upload_prepared(nullptr, panel_mins, panel_weights, n_panel, sketch_size, d_pm, d_pw, d_mT, d_wT));
     for (uint32_t i = 0; i < m; i += SCAN_BATCH_MAX)              // a flush's worth of snapshots per launch; "ring" = this chunk, no wrap
-        PD_CHK(launch_snap_panel(nullptr, d_sm + (size_t)i * S, d_sw + (size_t)i * S, sketch_size, 0, 0xffffffffu,
-                                 std::min<uint32_t>(m - i, SCAN_BATCH_MAX), d_mT, d_wT, n_panel, metric, role, d_out + (size_t)i * n_panel));
-    PD_CHK(hipMemcpy(out, d_out, MP * 8, hipMemcpyDeviceToHost));
-#undef PD_CHK
-    return done(HULK_OK);
+        ONESHOT_CHK(launch_snap_panel(nullptr, d_sm + (size_t)i * S, d_sw + (size_t)i * S, sketch_size, 0, 0xffffffffu,
+                                      std::min<uint32_t>(m - i, SCAN_BATCH_MAX), d_mT, d_wT, n_panel, metric, role, d_out + (size_t)i * n_panel));
+    ONESHOT_CHK(hipMemcpy(out, d_out, MP * 8, hipMemcpyDeviceToHost));
+    return HULK_OK;
 }
 
 int hulk_snapshot_count(hulk_ctx *c, uint64_t *recorded, uint64_t *first_held) {
