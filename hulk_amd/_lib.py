@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     "hulk_set_snapshots", "hulk_snapshot_count", "hulk_get_snapshots", "hulk_set_snapshot_callback", "hulk_poll_snapshots",
     "hulk_set_panel", "hulk_get_snapshot_distances", "hulk_set_snapshot_panel_callback", "hulk_panel_distances",
     "hulk_search", "hulk_search_files", "hulk_cluster", "hulk_cluster_files",
+    "hulk_dendrogram", "hulk_dendrogram_files",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -131,6 +132,16 @@ class ClusterOpts(ctypes.Structure):
 class ClusterStats(ctypes.Structure):
     _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_link", ctypes.c_double), ("kernel_ms_flatten", ctypes.c_double),
                 ("links", ctypes.c_uint64), ("bands", ctypes.c_uint32), ("clusters", ctypes.c_uint32)]
+
+
+class DendrogramOpts(ctypes.Structure):
+    """hulk_dendrogram_opts (include/hulk_hip.h)."""
+    _fields_ = [("metric", ctypes.c_int), ("band_rows", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class DendrogramStats(ctypes.Structure):
+    _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_offer", ctypes.c_double), ("kernel_ms_fold", ctypes.c_double),
+                ("rounds", ctypes.c_uint32), ("bands", ctypes.c_uint32), ("edges", ctypes.c_uint32), ("components", ctypes.c_uint32)]
 
 
 class HulkError(RuntimeError):
@@ -333,6 +344,11 @@ def load():
     L.hulk_cluster_files.restype = ctypes.c_int
     L.hulk_cluster_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, dbl, u32, ctypes.c_char_p, vp,
                                      ctypes.POINTER(ClusterStats), ctypes.c_char_p, u64]
+    L.hulk_dendrogram.restype = ctypes.c_int
+    L.hulk_dendrogram.argtypes = [ctypes.c_int, vp, vp, u32, u32, ctypes.POINTER(DendrogramOpts), vp, vp, vp, vp, ctypes.POINTER(DendrogramStats)]
+    L.hulk_dendrogram_files.restype = ctypes.c_int
+    L.hulk_dendrogram_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, u32, ctypes.c_char_p, dbl, ctypes.c_char_p,
+                                        vp, vp, vp, vp, ctypes.POINTER(DendrogramStats), ctypes.c_char_p, u64]
     _lib = L
     return L
 

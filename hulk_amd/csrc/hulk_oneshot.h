@@ -1,5 +1,5 @@
 // hulk_oneshot.h — what the entry points that run without a context share (hulk_smash_ex, hulk_panel_distances, hulk_search,
-// hulk_cluster; hulk_set_panel for its temporaries): choosing the device, owning what the call allocates, and the way from host
+// hulk_cluster, hulk_dendrogram; hulk_set_panel for its temporaries): choosing the device, owning what the call allocates, and the way from host
 // sketches to the prepared slot-major arrays.  Helpers, not a framework: every caller keeps its own control flow.
 #pragma once
 #include "hulk_ctx.h"

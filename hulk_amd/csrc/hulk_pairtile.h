@@ -2,6 +2,7 @@
 // sketches against 64 other sketches, summed over the S slots in ascending order.  One text for
 //   k_search_dist   (hulk_search.hip)    a block of queries against a strip of the database, either side the subject
 //   k_cluster_link  (hulk_cluster.hip)   one set against itself in bands of subject rows; the distances go no further than a compare
+//   k_dendro_offer  (hulk_dendrogram.hip) the same bands; the distances go into per-sketch minima
 // each of which is its index arithmetic, one call of pair_tile and its own epilogue over pair_distance.
 // k_smash (hulk_pairwise.hip: one set against itself, the whole N x N matrix) KEEPS A LOOP OF ITS OWN, the same text with `if`
 // for `if constexpr`: through pair_tile its weighted form ran 1.1 % slower on the MI355X than with its own loop (N = 8,192,

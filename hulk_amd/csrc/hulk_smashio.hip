@@ -547,6 +547,24 @@ static int load_sketch_set(const char *const *paths, uint32_t n_paths, uint32_t 
     return HULK_OK;
 }
 
+// "sketch,cluster,size,representative" of hulk_cluster_files and of hulk_dendrogram_files' cut: one line per sketch in sorted path
+// order.  label[i]: the smallest member of i's cluster — the ordinals count the labels in ascending order
+static bool write_clusters_csv(const hulk_sketch_set &set, const uint32_t *label, const char *csv_path, std::string &err) {
+    const uint32_t n = (uint32_t)set.files.size();
+    std::vector<uint32_t> ordinal(n, 0), size(n, 0);
+    uint32_t next = 0;
+    for (uint32_t i = 0; i < n; i++) { if (label[i] == i) ordinal[i] = ++next; size[label[i]]++; }
+    std::vector<std::string> rows((size_t)n + 1);
+    rows[0] = "sketch,cluster,size,representative\n";
+    for (uint32_t i = 0; i < n; i++) {
+        std::string &r = rows[(size_t)i + 1];
+        const uint32_t l = label[i];
+        csv_field(r, set.files[i].path); r += ','; r += std::to_string(ordinal[l]); r += ','; r += std::to_string(size[l]); r += ',';
+        csv_field(r, set.files[l].path); r += '\n';
+    }
+    return write_all(csv_path, rows, err);
+}
+
 extern "C" {
 
 int hulk_load_sketches(const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, uint32_t threads,
@@ -721,21 +739,71 @@ int hulk_cluster_files(int device, const char *const *paths, uint32_t n_paths, u
         if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
     }
     if (csv_path) {
-        // a cluster's smallest member is its label: the ordinals count the labels in ascending order
-        std::vector<uint32_t> ordinal(n, 0), size(n, 0);
-        uint32_t next = 0;
-        for (uint32_t i = 0; i < n; i++) { if (label[i] == i) ordinal[i] = ++next; size[label[i]]++; }
-        std::vector<std::string> rows((size_t)n + 1);
-        rows[0] = "sketch,cluster,size,representative\n";
-        for (uint32_t i = 0; i < n; i++) {
-            std::string &r = rows[(size_t)i + 1];
-            const uint32_t l = label[i];
-            csv_field(r, set->files[i].path); r += ','; r += std::to_string(ordinal[l]); r += ','; r += std::to_string(size[l]); r += ',';
-            csv_field(r, set->files[l].path); r += '\n';
-        }
         std::string err;
-        if (!write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+        if (!write_clusters_csv(*set, label, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     }
+    return HULK_OK;
+}
+
+int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
+                          uint32_t threads, const char *csv_path, double cut_distance, const char *cut_csv_path,
+                          uint32_t *edge_a, uint32_t *edge_b, double *edge_distance, uint32_t *n_edges,
+                          hulk_dendrogram_stats *stats, char *errbuf, uint64_t errbuf_len) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_edges) *n_edges = 0;
+    if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    const std::string metric_s = metric, algo_s = algo;
+    if (metric_s != "jaccard" && metric_s != "weightedjaccard")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard]");
+    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    const bool cut = cut_distance == cut_distance;                  // NaN: no cut
+    if (cut && !(cut_distance >= 0.0 && cut_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_dendrogram: cut_distance must be in [0, 1] (or NaN: no cut)");
+    if (cut && !cut_csv_path) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_dendrogram: a cut_distance without a cut_csv_path");
+    hulk_sketch_set *set = nullptr;
+    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
+    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
+    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    const uint32_t n = (uint32_t)set->files.size();
+    std::vector<uint32_t> own_a, own_b; std::vector<double> own_d;
+    uint32_t m = 0;
+    if (!edge_a) { own_a.resize(n); edge_a = own_a.data(); }
+    if (!edge_b) { own_b.resize(n); edge_b = own_b.data(); }
+    if (!edge_distance) { own_d.resize(n); edge_distance = own_d.data(); }
+    hulk_dendrogram_opts o;
+    memset(&o, 0, sizeof o);
+    o.metric = metric_s == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD;
+    {
+        const int rc = hulk_dendrogram(device, set->mins.data(), set->weights.data(), n, set->size, &o, edge_a, edge_b, edge_distance, &m, stats);
+        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
+    }
+    if (n_edges) *n_edges = m;
+    // the edges ascend by distance: one sequential union-find (the smaller root stays) gives the size of every merge and, stopped
+    // behind the last edge <= cut_distance, the labels of the cut
+    std::vector<uint32_t> up(n), size(n, 1), label;
+    for (uint32_t i = 0; i < n; i++) up[i] = i;
+    auto find = [&](uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; };
+    auto labels_now = [&] { label.resize(n); for (uint32_t i = 0; i < n; i++) label[i] = find(i); };
+    std::vector<std::string> rows((size_t)m + 1);
+    rows[0] = "merge,sketch_a,sketch_b,distance,similarity,size\n";
+    bool cut_taken = false;
+    for (uint32_t e = 0; e < m; e++) {
+        if (cut && !cut_taken && !(edge_distance[e] <= cut_distance)) { labels_now(); cut_taken = true; }
+        const uint32_t a = find(edge_a[e]), b = find(edge_b[e]), lo = std::min(a, b), hi = std::max(a, b);
+        up[hi] = lo; size[lo] += size[hi];
+        std::string &r = rows[(size_t)e + 1];
+        char tmp[64];
+        r += std::to_string(e + 1); r += ',';
+        csv_field(r, set->files[edge_a[e]].path); r += ','; csv_field(r, set->files[edge_b[e]].path); r += ',';
+        snprintf(tmp, sizeof tmp, "%.17g", edge_distance[e]); r += tmp; r += ',';
+        format_f2(r, 100 - (edge_distance[e] * 100));               // cmd/smash.go:217
+        r += ','; r += std::to_string(size[lo]); r += '\n';
+    }
+    if (cut && !cut_taken) labels_now();
+    std::string err;
+    if (csv_path && !write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    if (cut && !write_clusters_csv(*set, label.data(), cut_csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     return HULK_OK;
 }
 

@@ -7,6 +7,8 @@ search / search_files: for every query sketch the k closest sketches of a databa
 distance, selected on the GPU while the database streams through it.
 cluster / cluster_files: the connected components of "distance <= threshold" over a collection (hulk_cluster, hulk_cluster_files):
 single linkage, without the N x N matrix.
+dendrogram / dendrogram_files: every threshold at once — the minimum spanning forest of the distance graph (hulk_dendrogram,
+hulk_dendrogram_files); cut_dendrogram and linkage_matrix read it on the host.
 """
 import fnmatch
 import glob
@@ -228,6 +230,130 @@ def cluster_files(files, max_distance, ksize=21, algo="histosketch", metric="jac
     if stats is not None:
         stats.update(_cluster_stats_dict(st))
     return ordering, labels[:len(ordering)], int(st.clusters)
+
+
+def _dendrogram_stats_dict(st):
+    return dict(seconds_total=st.seconds_total, kernel_ms_offer=st.kernel_ms_offer, kernel_ms_fold=st.kernel_ms_fold,
+                rounds=st.rounds, bands=st.bands, edges=st.edges, components=st.components)
+
+
+def dendrogram(mins, weights, metric="jaccard", band_rows=0, device=0, stats=None):
+    """The single-linkage dendrogram of a sketch collection, on the GPU (hulk_dendrogram): -> (a uint32[E], b uint32[E], d float64[E]),
+    a < b, the edges of the minimum spanning forest in merge order.  With D = distance_matrix(mins, weights, metric) the edge {i, j}
+    weighs fmin(D[i, j], D[j, i]) (no edge where both are NaN), edges are ordered by (weight, min(i, j), max(i, j)) and the result
+    is what Kruskal gives on that order: E = N - (components of the non-NaN graph), and cut_dendrogram(N, a, b, d, tau) is
+    cluster(mins, weights, tau, metric) for every tau.  band_rows (a multiple of 32, 0 = 2048) cannot change the result.  stats: a
+    dict that receives seconds_total, kernel_ms_offer, kernel_ms_fold, rounds, bands (per round), edges, components."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    m = np.ascontiguousarray(mins, dtype=np.uint64); w = np.ascontiguousarray(weights, dtype=np.float64)
+    if m.ndim != 2 or m.shape != w.shape:
+        raise ValueError("mins/weights must be [n][sketch_size]")
+    band_rows = int(band_rows)
+    if not 0 <= band_rows < 2 ** 32:
+        raise ValueError("band_rows must be a multiple of 32 (0 = default)")
+    o = _lib.DendrogramOpts(metric=_lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+                            band_rows=band_rows)
+    n = m.shape[0]
+    a = np.zeros(max(n, 1), dtype=np.uint32); b = np.zeros(max(n, 1), dtype=np.uint32); d = np.zeros(max(n, 1), dtype=np.float64)
+    ne = ctypes.c_uint32(0)
+    st = _lib.DendrogramStats()
+    L = _lib.load()
+    rc = L.hulk_dendrogram(device, m.ctypes.data, w.ctypes.data, n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data, d.ctypes.data,
+                           ctypes.byref(ne), ctypes.byref(st))
+    if rc != 0:
+        raise HulkError(rc, L.hulk_last_error(None).decode())
+    if stats is not None:
+        stats.update(_dendrogram_stats_dict(st))
+    return a[:ne.value], b[:ne.value], d[:ne.value]
+
+
+def dendrogram_files(files, ksize=21, algo="histosketch", metric="jaccard", csv_path=None, cut_distance=None, cut_csv_path=None,
+                     threads=0, device=0, stats=None):
+    """The directory form (hulk_dendrogram_files): the sketch files are loaded and MD5-verified by the native loader (one file is
+    fine), the dendrogram is computed on the GPU and, csv_path given, the library writes "merge,sketch_a,sketch_b,distance,
+    similarity,size" — one line per merge: its 1-based ordinal, the two paths, the distance as %.17g, the similarity as `smash`
+    prints it, the size of the cluster the merge creates.  cut_distance (in [0, 1]) with cut_csv_path: the file cluster_files
+    writes at that max_distance, byte for byte.  -> (ordering, a, b, d); ordering = the sorted unique paths, a and b index it."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if algo not in AVAIL_ALGORITHMS:
+        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    ordering = sorted(set(files))
+    n = max(len(ordering), 1)
+    a = np.zeros(n, dtype=np.uint32); b = np.zeros(n, dtype=np.uint32); d = np.zeros(n, dtype=np.float64)
+    ne = ctypes.c_uint32(0)
+    arr, n_paths = _paths(files)
+    st = _lib.DendrogramStats()
+    err = ctypes.create_string_buffer(4096)
+    L = _lib.load()
+    rc = L.hulk_dendrogram_files(device, arr, n_paths, ksize, algo.encode(), metric.encode(), threads,
+                                 None if csv_path is None else os.fsencode(csv_path),
+                                 float("nan") if cut_distance is None else float(cut_distance),
+                                 None if cut_csv_path is None else os.fsencode(cut_csv_path),
+                                 a.ctypes.data, b.ctypes.data, d.ctypes.data, ctypes.byref(ne), ctypes.byref(st), err, len(err))
+    if rc != 0:
+        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    if stats is not None:
+        stats.update(_dendrogram_stats_dict(st))
+    return ordering, a[:ne.value], b[:ne.value], d[:ne.value]
+
+
+def cut_dendrogram(n, a, b, d, max_distance):
+    """The clusters of a dendrogram at a threshold, on the host: -> (labels uint32[n], n_clusters) — the components of the edges
+    with d <= max_distance, labels[i] the smallest member of i's component: what cluster() gives at that max_distance."""
+    n = int(n)
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    for x, y, h in zip(np.asarray(a).tolist(), np.asarray(b).tolist(), np.asarray(d, dtype=np.float64).tolist()):
+        if not 0 <= x < n or not 0 <= y < n:
+            raise ValueError("an edge outside the set")
+        if h <= max_distance:
+            rx, ry = find(x), find(y)
+            if rx != ry:
+                parent[max(rx, ry)] = min(rx, ry)
+    labels = np.array([find(i) for i in range(n)], dtype=np.uint32)
+    return labels, int((labels == np.arange(n)).sum())
+
+
+def linkage_matrix(n, a, b, d):
+    """The dendrogram in the layout of scipy.cluster.hierarchy.linkage: an (n - 1) x 4 float64 array, row t = (id, id, distance,
+    size) of merge t, ids < n the sketches, id n + t the cluster merge t created (the smaller id first).  The edges are taken in
+    the order given, which is ascending for dendrogram()'s output.  ValueError when the forest is not one tree (n - 1 edges that
+    join n sketches).  SciPy is not needed."""
+    n = int(n)
+    a = np.asarray(a).tolist(); b = np.asarray(b).tolist(); d = np.asarray(d, dtype=np.float64).tolist()
+    if n < 1 or not len(a) == len(b) == len(d) == n - 1:
+        raise ValueError(f"not one tree: {len(a)} edges for {n} sketches (a forest has no linkage matrix)")
+    parent = list(range(n))
+    ident = list(range(n))                                          # root -> the id of its cluster
+    size = [1] * n
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    Z = np.zeros((n - 1, 4), dtype=np.float64)
+    for t, (x, y, h) in enumerate(zip(a, b, d)):
+        if not 0 <= x < n or not 0 <= y < n:
+            raise ValueError("an edge outside the set")
+        rx, ry = find(x), find(y)
+        if rx == ry:
+            raise ValueError("not one tree: an edge inside a cluster")
+        lo, hi = min(rx, ry), max(rx, ry)
+        Z[t] = (min(ident[rx], ident[ry]), max(ident[rx], ident[ry]), h, size[rx] + size[ry])
+        parent[hi] = lo
+        size[lo] = size[rx] + size[ry]
+        ident[lo] = n + t
+    return Z
 
 
 def go_format_f2(v: float) -> str:

@@ -15,6 +15,7 @@
 //       cmd/sketch.go:56 (promised, read nowhere in src/pipeline)           OnSnapshot (recorded inside the batched flush)
 //   (none: the k nearest sketches of a database for every query sketch)   hulk::Search (HULKdata.GetDistance per pair)
 //   (none: the sketches of a collection grouped at a distance threshold)  hulk::Cluster / hulk::ClusterFiles (single linkage)
+//   (none: every threshold at once, the single-linkage dendrogram)         hulk::Dendrogram / hulk::DendrogramFiles
 //
 // Header only; link with -lhulkhip.  A Boss is single-caller, like SeqMinimizer.Run's goroutine.
 #ifndef HULK_HPP
@@ -25,6 +26,7 @@
 #include <cstdint>
 #include <exception>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -397,6 +399,60 @@ inline std::vector<uint32_t> ClusterFiles(const std::vector<std::string> &jsonFi
     if (rc != HULK_OK) throw Error(rc, err);
     label.resize(uniq.size());
     return label;
+}
+
+// The single-linkage dendrogram of a collection, on the GPU (hulk_dendrogram): the minimum spanning forest of the graph whose edge
+// {i, j} weighs fmin(Smash's [i][j], [j][i]) (NaNs ignored; two NaNs: no edge), edges ordered by (weight, A, B): A < B, ascending —
+// the merge order.  Cut at any distance it is hulk::Cluster at that maxDistance.  bandRows cannot change the result.
+struct DendrogramEdge { uint32_t A = 0, B = 0; double Distance = 0; };
+inline std::vector<DendrogramEdge> Dendrogram(const std::vector<HistoSketch> &sketches, const std::string &metric, uint32_t bandRows = 0,
+                                              int device = 0, hulk_dendrogram_stats *stats = nullptr) {
+    const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
+    std::vector<uint64_t> mins((size_t)N * S + 1);
+    std::vector<double> weights((size_t)N * S + 1);
+    for (uint32_t i = 0; i < N; i++) {
+        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
+            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
+        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
+        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
+    }
+    hulk_dendrogram_opts o = hulk_dendrogram_opts();
+    o.band_rows = bandRows;
+    if (metric == "jaccard") o.metric = HULK_METRIC_JACCARD;
+    else if (metric == "weightedjaccard") o.metric = HULK_METRIC_WEIGHTED_JACCARD;
+    else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+    std::vector<uint32_t> a((size_t)N + 1), b((size_t)N + 1);
+    std::vector<double> d((size_t)N + 1);
+    uint32_t m = 0;
+    const int rc = hulk_dendrogram(device, mins.data(), weights.data(), N, S, &o, a.data(), b.data(), d.data(), &m, stats);
+    if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+    std::vector<DendrogramEdge> out(m);
+    for (uint32_t e = 0; e < m; e++) { out[e].A = a[e]; out[e].B = b[e]; out[e].Distance = d[e]; }
+    return out;
+}
+
+// The directory form (hulk_dendrogram_files): the files through the library's loader (sorted unique paths, which A and B count);
+// dendrogramCSV, if not empty, receives "merge,sketch_a,sketch_b,distance,similarity,size"; cutDistance in [0, 1] (NaN: no cut)
+// with clustersCSV: the file hulk::ClusterFiles writes at that maxDistance.
+inline std::vector<DendrogramEdge> DendrogramFiles(const std::vector<std::string> &jsonFiles, uint32_t kSize, const std::string &algo,
+                                                   const std::string &metric, const std::string &dendrogramCSV = std::string(),
+                                                   double cutDistance = std::numeric_limits<double>::quiet_NaN(),
+                                                   const std::string &clustersCSV = std::string(), hulk_dendrogram_stats *stats = nullptr,
+                                                   int device = 0, uint32_t threads = 0) {
+    std::vector<const char *> ptr;
+    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
+    const size_t n = jsonFiles.size() + 1;
+    std::vector<uint32_t> a(n), b(n);
+    std::vector<double> d(n);
+    uint32_t m = 0;
+    char err[4096] = {0};
+    const int rc = hulk_dendrogram_files(device, ptr.data(), (uint32_t)ptr.size(), kSize, algo.c_str(), metric.c_str(), threads,
+                                         dendrogramCSV.empty() ? nullptr : dendrogramCSV.c_str(), cutDistance,
+                                         clustersCSV.empty() ? nullptr : clustersCSV.c_str(), a.data(), b.data(), d.data(), &m, stats, err, sizeof err);
+    if (rc != HULK_OK) throw Error(rc, err);
+    std::vector<DendrogramEdge> out(m);
+    for (uint32_t e = 0; e < m; e++) { out[e].A = a[e]; out[e].B = b[e]; out[e].Distance = d[e]; }
+    return out;
 }
 
 // `hulk smash` as the reference runs it (cmd/smash.go:160-226): the sketch files of a directory in, <outFile>.hulk-matrix.csv out —

@@ -68,7 +68,7 @@ extern "C" {
  *    sketch snapshots (hulk_set_snapshots, hulk_snapshot_count, hulk_get_snapshots, hulk_set_snapshot_callback, hulk_poll_snapshots);
  *    a panel the snapshots are scored against (hulk_set_panel, hulk_get_snapshot_distances, hulk_set_snapshot_panel_callback,
  *    hulk_panel_distances); the nearest-neighbour search (hulk_search, hulk_search_files); single-linkage clustering (hulk_cluster,
- *    hulk_cluster_files).
+ *    hulk_cluster_files) and its dendrogram (hulk_dendrogram, hulk_dendrogram_files).
  * Bindings compare it with the value they were written for. */
 #define HULK_ABI_VERSION 4
 
@@ -657,6 +657,52 @@ int hulk_cluster(int device, const uint64_t *mins, const double *weights, uint32
 int hulk_cluster_files(int device, const char *const *paths, uint32_t n, uint32_t ksize, const char *algo, const char *metric,
                        double max_distance, uint32_t threads, const char *csv_path, uint32_t *label,
                        hulk_cluster_stats *stats, char *errbuf, uint64_t errbuf_len);
+
+/* ---- the single-linkage dendrogram of a sketch collection: every threshold of hulk_cluster at once ---------------------------------
+ * d(i, j) = entry [i][j] of the matrix hulk_smash gives (sketch i the subject), bit for bit.  The undirected edge {i, j}, i != j,
+ * weighs w(i, j) = fmin(d(i, j), d(j, i)) — a NaN direction is ignored, two NaN directions are no edge: hulk_cluster's "either
+ * direction links" for every threshold at once (jaccard: both directions are the same bits; weightedjaccard: they are not).  Edges
+ * are totally ordered by the key (w, lo, hi), lo = min(i, j), hi = max(i, j) (w >= 0: a double that orders like its bits), and the
+ * result is the minimum spanning forest under that order — what Kruskal gives on the edges sorted by the key; unique however many
+ * distances tie.  *n_edges = n - (connected components of the non-NaN graph); edge_a[e] < edge_b[e] and edge_distance[e], n - 1 entries
+ * each, receive the edges ascending by the key: the merge order of the dendrogram.  For any tau the components of
+ * {e: edge_distance[e] <= tau}, labelled by their smallest member, are hulk_cluster's labels at max_distance = tau.  A function of
+ * the inputs alone: bands, launch shape, the number of rounds and scheduling cannot change a bit.  n == 1: 0 edges; every pair NaN
+ * (every weight row zero under weightedjaccard): 0 edges, n components, HULK_OK.
+ * Boruvka's algorithm: the set is prepared once and stays on the device as in hulk_cluster (the same peak, or the set plus a scratch
+ * of 12 * (band_rows * ceil(n / 64) + 64 * ceil(n / 64) * band_rows / 32) bytes); a ROUND is one pass of k_dendro_offer
+ * (hulk_dendrogram.hip: hulk_cluster's tile, keeping per sketch the closest sketch of another component) in bands of band_rows
+ * subject rows, k_dendro_fold behind every band, and a contraction of the n offers on the host (hulk_boruvka.h).  At most
+ * ceil(log2 n) rounds deliver offers; one more, empty, closes a forest that NaNs separate: stats->rounds <= ceil(log2 n) + 1, 0 for
+ * n == 1.  No n x n array exists.
+ * HULK_ERR_ARG before any HIP call, with a text in hulk_last_error(NULL): NULL arrays, opts or n_edges; n or sketch_size == 0; an
+ * unknown metric; band_rows not a multiple of 32; non-zero flags or reserved; n above HULK_CLUSTER_MAX_N. */
+typedef struct hulk_dendrogram_opts {
+    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD */
+    uint32_t band_rows;    /* subject rows per launch; 0 = default (2048); a multiple of 32 (above 2^20: 2^20) */
+    uint32_t flags;        /* zero */
+    uint64_t reserved[4];  /* zero */
+} hulk_dendrogram_opts;
+typedef struct hulk_dendrogram_stats {
+    double seconds_total, kernel_ms_offer, kernel_ms_fold;   /* the whole call; k_dendro_offer / k_dendro_fold summed over rounds and bands (HIP events, read behind each round's one synchronisation) */
+    uint32_t rounds, bands /* per round */, edges, components;
+} hulk_dendrogram_stats;
+int hulk_dendrogram(int device, const uint64_t *mins, const double *weights, uint32_t n, uint32_t sketch_size,
+                    const hulk_dendrogram_opts *opts, uint32_t *edge_a, uint32_t *edge_b, double *edge_distance /* n - 1 each */,
+                    uint32_t *n_edges, hulk_dendrogram_stats *stats);
+/* The directory form: the files go through hulk_load_sketches' loader (MD5, FindSketch, the reference's error texts; sorted unique
+ * paths, which the indices count; a set of ONE sketch is valid).  metric: "jaccard" | "weightedjaccard" (histosketches only:
+ * hulk_smash_files' text); algo: "histosketch" | "kmv" | "khf".  edge_a / edge_b / edge_distance [unique paths - 1] and n_edges may be
+ * NULL.  csv_path != NULL: a file with the header "merge,sketch_a,sketch_b,distance,similarity,size" and one line per edge in merge
+ * order: the 1-based ordinal, the two paths as encoding/csv quotes them, the distance as %.17g (it reads back to the same double: a
+ * cut can be repeated exactly), strconv.FormatFloat(100 - 100 * distance, 'f', 2, 64) as `smash` prints it, and the size of the
+ * cluster the merge creates.  cut_distance in [0, 1] and cut_csv_path != NULL: the file hulk_cluster_files writes at max_distance =
+ * cut_distance, byte for byte ("sketch,cluster,size,representative"), from the edges with distance <= cut_distance; cut_distance NaN:
+ * no cut (cut_csv_path is ignored); any other cut_distance, or one in [0, 1] without a cut_csv_path, is HULK_ERR_ARG. */
+int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n, uint32_t ksize, const char *algo, const char *metric,
+                          uint32_t threads, const char *csv_path, double cut_distance /* NaN: no cut */, const char *cut_csv_path,
+                          uint32_t *edge_a, uint32_t *edge_b, double *edge_distance, uint32_t *n_edges,
+                          hulk_dendrogram_stats *stats, char *errbuf, uint64_t errbuf_len);
 
 /* Device self-test: the jump hash replaces the fp64 division 2^31/r by a Newton reciprocal; this
  * checks RN(1/r) against IEEE division for EVERY r in [1, 2^31] and returns the mismatch count. */
