@@ -2,6 +2,12 @@
 //   K2  k_count_used       the 1 % rule (kmerspectrum.go:53-55,84-96)
 //   K3  k_cms_segsum/k_cms_base/k_cms_freq   src/countmin/countmin.go:103-147
 //       k_elem_*/k_cmsd_*  the same with uniform scaling (0 < decay < 1)
+// The replay (k_*_freq) is a 2 x 2 over one skeleton, cms_replay<order>(arithmetic):
+//                         LDS order (default)       chain order (fallback)
+//   integer counters      k_cms_freq                k_cms_freq_chain
+//   fp64 with decay       k_cmsd_freq               k_cmsd_freq_chain
+// Three kernels rest on the LDS applying same-address lanes of one returning atomic in ascending lane order (k_lds_order_probe
+// checks it on the device): the two LDS-order forms, for their results, and k_cmsd_segsum, for the reproducible order of its sums.
 #include "hulk_device.h"
 
 #include <math.h>
@@ -33,19 +39,38 @@ __global__ __launch_bounds__(256) void k_count_used(const uint32_t *__restrict__
     }
 }
 
-
-
 // ------------------------------------------------------------------------------------------
-// K3 (no decay), bin-order form.  The chain-order kernels above gather 4-byte values along chains
-// whose bins are ~2000 apart: rocprofv3 showed 13x more HBM traffic than the algorithmic bytes.
-// Here every array is read in BIN order (coalesced) and the 7 x 2000 running counters live in LDS:
+// K3 (no decay), bin-order form.  (Kernels that followed each counter's chain of bins, ~2000 apart, came first and are gone:
+// they gathered 4-byte values along the chains, and rocprofv3 showed 13x more HBM traffic than the algorithmic bytes.)
+// Every array is read in BIN order (coalesced) and the 7 x 2000 running counters live in LDS:
 //   k_cms_segsum : per (spectrum, row, bin segment) sums per counter            (LDS atomics)
 //   k_cms_base   : counter value in front of every (spectrum, segment)          (tiny prefix kernel)
-//   k_cms_freq   : one workgroup per (segment, spectrum): waves 0..6 replay their row in bin order — one returning LDS
-//                  atomic add per (row, bin): the LDS itself applies same-counter lanes in bin order — and meet in an LDS
-//                  minimum per bin; wave 7 writes f / 1/f and wipes the spectrum.  No est arrays at all.
+//   k_cms_freq   : one workgroup per (segment, spectrum) replays the segment in bin order from there ("The replay" below)
 // ------------------------------------------------------------------------------------------
 constexpr int CMS_SEGS = 16;          // bin segments per spectrum
+inline int cms_seg_chunks(int32_t num_bins) { return ((num_bins + 63) / 64 + CMS_SEGS - 1) / CMS_SEGS; }   // chunks of 64 bins per segment
+
+// The row sums of one bin segment (k_cms_segsum, k_shard_local): the [depth][width] LDS counters start at zero and wave d < depth
+// adds the counts of the segment's bins, from b0 on, to row d.  The caller's barrier comes before the counters are read.
+__device__ __forceinline__ void cms_seg_row_sums(uint32_t *lctr, const uint32_t *__restrict__ hist, const uint16_t *__restrict__ pos16,
+                                                 size_t B, int64_t b0, int depth, int width, int seg_chunks) {
+    const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;
+    for (int i = tid; i < depth * width; i += blockDim.x) lctr[i] = 0;
+    __syncthreads();
+    if (d >= depth) return;
+    const uint16_t *pd = pos16 + (size_t)d * B;
+    for (int c0 = 0; c0 < seg_chunks; c0 += 8) {                  // 8 chunks of loads in flight
+        uint32_t h[8]; uint32_t p[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int64_t b = b0 + (int64_t)(c0 + u) * 64 + lane;
+            const bool ok = (c0 + u < seg_chunks) && b < (int64_t)B;
+            h[u] = ok ? hist[b] : 0u; p[u] = ok ? pd[b] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) if (h[u]) atomicAdd(&lctr[d * width + p[u]], h[u]);
+    }
+}
 
 __global__ __launch_bounds__(512) void k_cms_segsum(const uint32_t *__restrict__ hists,
                                                     const uint16_t *__restrict__ pos16,
@@ -53,29 +78,11 @@ __global__ __launch_bounds__(512) void k_cms_segsum(const uint32_t *__restrict__
                                                     int seg_chunks, const DevState *st, FlushBatch fb) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint32_t *lctr = (uint32_t *)smem;                           // [depth][width]
-    const int seg = blockIdx.x, t = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;  // wave d = row d (depth waves + 1 idle)
+    const int seg = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
     const uint32_t gomask = batch_gomask(st, fb);
     if (!((gomask >> t) & 1u)) return;
-    for (int i = tid; i < depth * width; i += blockDim.x) lctr[i] = 0;
-    __syncthreads();
     const size_t B = (size_t)fb.num_bins;
-    const uint32_t *hist = hists + (size_t)ring_slot(fb, t) * B;
-    if (d < depth) {
-        const uint16_t *pd = pos16 + (size_t)d * B;
-        const int64_t b0 = (int64_t)seg * seg_chunks * 64;
-        for (int c0 = 0; c0 < seg_chunks; c0 += 8) {              // 8 chunks of loads in flight
-            uint32_t h[8]; uint32_t p[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int64_t b = b0 + (int64_t)(c0 + u) * 64 + lane;
-                const bool ok = (c0 + u < seg_chunks) && b < (int64_t)B;
-                h[u] = ok ? hist[b] : 0u; p[u] = ok ? pd[b] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) if (h[u]) atomicAdd(&lctr[d * width + p[u]], h[u]);
-        }
-    }
+    cms_seg_row_sums(lctr, hists + (size_t)ring_slot(fb, t) * B, pos16, B, (int64_t)seg * seg_chunks * 64, depth, width, seg_chunks);
     __syncthreads();
     uint32_t *out = segsum + (((size_t)t * depth) * CMS_SEGS + 0) * width;
     for (int i = tid; i < depth * width; i += blockDim.x) {
@@ -104,212 +111,6 @@ __global__ __launch_bounds__(256) void k_cms_base(const uint32_t *__restrict__ s
         for (int seg = 0; seg < CMS_SEGS; seg++) { base[at0 + (size_t)seg * width] = run; run += sv[seg]; }
     }
     ctr[i] = run;
-}
-
-__global__ __launch_bounds__(512) void k_cms_freq(uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
-                                                  const unsigned long long *__restrict__ base,
-                                                  double *__restrict__ f64, float *__restrict__ rcp32,
-                                                  int depth, int width, int seg_chunks, size_t row_stride,
-                                                  DevState *st, FlushBatch fb) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int FG = 8, GB = FG * 64;                                          // chunks of 64 bins per barrier
-    unsigned long long *lctr = (unsigned long long *)smem;                       // [depth][width]
-    unsigned long long *smin = lctr + (size_t)depth * width;                     // [2][GB] minimum over the rows
-    const int seg = blockIdx.x, t = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;                  // waves 0..depth-1: rows; wave depth: combiner
-    const uint32_t gomask = batch_gomask(st, fb);
-    const bool go = (gomask >> t) & 1u;
-    const uint32_t slot = ring_slot(fb, t);
-    if (seg == 0 && tid == 0) {
-        const unsigned used = st->used[fb.parity][slot];
-        if (used != 0 && !go) set_error(st, -5);                                 // "not used yet" (kmerspectrum.go:94-96)
-        if (go) atomicAdd(&st->n_elements, (unsigned long long)used);
-    }
-    if (!go) return;
-    const size_t B = (size_t)fb.num_bins;
-    if (st->skip_exact[fb.parity]) {                                             // k_flush_decide: only Wipe is left to do
-        uint32_t *hw = hists + (size_t)slot * B;
-        const int64_t w0 = (int64_t)seg * seg_chunks * 64, w1 = w0 + (int64_t)seg_chunks * 64;
-        for (int64_t b = w0 + tid; b < w1 && b < (int64_t)B; b += blockDim.x) hw[b] = 0;
-        return;
-    }
-    {
-        const unsigned long long *bt = base + (((size_t)t * depth) * CMS_SEGS) * width;
-        for (int i = tid; i < depth * width; i += blockDim.x) {
-            const int dd = i / width, p = i - dd * width;
-            lctr[i] = bt[((size_t)dd * CMS_SEGS + seg) * width + p];
-        }
-        for (int i = tid; i < 2 * GB; i += blockDim.x) smin[i] = ~0ull;
-    }
-    __syncthreads();
-    uint32_t *hist = hists + (size_t)slot * B;
-    double *ft = f64 + (size_t)t * B;
-    float *rt = rcp32 + (size_t)t * row_stride;
-    const int64_t b0 = (int64_t)seg * seg_chunks * 64;
-    const int ngroups = (seg_chunks + FG - 1) / FG;
-    const uint16_t *pd = pos16 + (size_t)(d < depth ? d : 0) * B;
-    unsigned long long *rc = lctr + (size_t)(d < depth ? d : 0) * width;
-    // The LDS keeps the bin order by itself: ds_add_rtn_u64 returns the counter as it stood before this lane's add, same-
-    // address lanes of one instruction are applied in ascending lane order, a wave's instructions in program order
-    // (tools/ubench/lds_atomic_order.hip) — est = old + own count is the reference's counter after Add (countmin.go:122-127).
-    // The rows meet in one LDS minimum per bin; the combiner wave is one group behind.  (Until round 5: a static "previous
-    // lane on the same counter" table followed with register exchanges, per-row staging, 4 chunks per barrier: 117 us.)
-    uint32_t nh[FG], np_[FG];
-    auto fetch = [&](int g) {
-#pragma unroll
-        for (int c = 0; c < FG; c++) {
-            const int ch = g * FG + c;
-            const int64_t b = b0 + (int64_t)ch * 64 + lane;
-            nh[c] = 0; np_[c] = 0;
-            if (ch < seg_chunks && b < (int64_t)B) { nh[c] = hist[b]; if (d < depth) np_[c] = pd[b]; }
-        }
-    };
-    fetch(0);
-    uint32_t ph[FG];                                            // combiner: spectrum values of the group it finishes next
-#pragma unroll
-    for (int c = 0; c < FG; c++) ph[c] = 0;
-    for (int g = 0; g <= ngroups; g++) {
-        uint32_t hh[FG], pp[FG];
-#pragma unroll
-        for (int c = 0; c < FG; c++) { hh[c] = nh[c]; pp[c] = np_[c]; }
-        if (g + 1 < ngroups) fetch(g + 1);
-        if (d < depth && g < ngroups) {
-            unsigned long long *my = smin + (size_t)(g & 1) * GB;
-#pragma unroll
-            for (int c = 0; c < FG; c++) {
-                const uint32_t h = hh[c];
-                if (h) atomicMin(&my[c * 64 + lane], atomicAdd(&rc[pp[c]], (unsigned long long)h) + h);
-            }
-        }
-        if (d == depth && g > 0) {
-            unsigned long long *src = smin + (size_t)((g - 1) & 1) * GB;
-#pragma unroll
-            for (int c = 0; c < FG; c++) {
-                const int ch = (g - 1) * FG + c;
-                const int64_t b = b0 + (int64_t)ch * 64 + lane;
-                if (ch < seg_chunks && b < (int64_t)B) {
-                    if (ph[c]) {
-                        const unsigned long long mn = src[c * 64 + lane];
-                        src[c * 64 + lane] = ~0ull;
-                        const double f = (double)mn;
-                        ft[b] = f; rt[b] = (float)(1.0 / f);
-                        hist[b] = 0;                                 // Wipe (kmerspectrum.go:58-64)
-                    } else { ft[b] = 0.0; rt[b] = __builtin_nanf(""); }
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < FG; c++) ph[c] = hh[c];             // group g is finished by the combiner at g+1
-        __syncthreads();
-    }
-}
-
-// The fallback of k_cms_freq for a device whose LDS does NOT apply the same-address lanes of a returning atomic in ascending
-// lane order (lds_order_verified below; HULK_FLAG_CMS_CHAIN forces it): the bin order inside a 64-bin chunk comes from the static
-// table k_build_chains wrote — meta8 = {the nearest LOWER lane of the chunk on the same counter (64: none), bit 7: the last lane
-// on its counter} — followed with ballots and register exchanges; the LDS is only read by the first lane of a counter's run
-// and written by its last.  Same integers, same order of additions: bit-identical to k_cms_freq (tested), about twice its time.
-__global__ __launch_bounds__(512) void k_cms_freq_chain(uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
-                                                        const uint8_t *__restrict__ meta8,
-                                                        const unsigned long long *__restrict__ base,
-                                                        double *__restrict__ f64, float *__restrict__ rcp32,
-                                                        int depth, int width, int seg_chunks, size_t row_stride,
-                                                        DevState *st, FlushBatch fb) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int FG = 8, GB = FG * 64;
-    unsigned long long *lctr = (unsigned long long *)smem;                       // [depth][width]
-    unsigned long long *smin = lctr + (size_t)depth * width;                     // [2][GB] minimum over the rows
-    const int seg = blockIdx.x, t = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;
-    const uint32_t gomask = batch_gomask(st, fb);
-    const bool go = (gomask >> t) & 1u;
-    const uint32_t slot = ring_slot(fb, t);
-    if (seg == 0 && tid == 0) {
-        const unsigned used = st->used[fb.parity][slot];
-        if (used != 0 && !go) set_error(st, -5);                                 // "not used yet" (kmerspectrum.go:94-96)
-        if (go) atomicAdd(&st->n_elements, (unsigned long long)used);
-    }
-    if (!go) return;
-    const size_t B = (size_t)fb.num_bins;
-    if (st->skip_exact[fb.parity]) {
-        uint32_t *hw = hists + (size_t)slot * B;
-        const int64_t w0 = (int64_t)seg * seg_chunks * 64, w1 = w0 + (int64_t)seg_chunks * 64;
-        for (int64_t b = w0 + tid; b < w1 && b < (int64_t)B; b += blockDim.x) hw[b] = 0;
-        return;
-    }
-    {
-        const unsigned long long *bt = base + (((size_t)t * depth) * CMS_SEGS) * width;
-        for (int i = tid; i < depth * width; i += blockDim.x) {
-            const int dd = i / width, p = i - dd * width;
-            lctr[i] = bt[((size_t)dd * CMS_SEGS + seg) * width + p];
-        }
-        for (int i = tid; i < 2 * GB; i += blockDim.x) smin[i] = ~0ull;
-    }
-    __syncthreads();
-    uint32_t *hist = hists + (size_t)slot * B;
-    double *ft = f64 + (size_t)t * B;
-    float *rt = rcp32 + (size_t)t * row_stride;
-    const int64_t b0 = (int64_t)seg * seg_chunks * 64;
-    const int ngroups = (seg_chunks + FG - 1) / FG;
-    const uint16_t *pd = pos16 + (size_t)(d < depth ? d : 0) * B;
-    const uint8_t *md = meta8 + (size_t)(d < depth ? d : 0) * B;
-    unsigned long long *rc = lctr + (size_t)(d < depth ? d : 0) * width;
-    uint32_t ph[FG];
-#pragma unroll
-    for (int c = 0; c < FG; c++) ph[c] = 0;
-    for (int g = 0; g <= ngroups; g++) {
-        uint32_t hh[FG];
-#pragma unroll
-        for (int c = 0; c < FG; c++) {
-            const int ch = g * FG + c;
-            const int64_t b = b0 + (int64_t)ch * 64 + lane;
-            const bool valid = g < ngroups && ch < seg_chunks && b < (int64_t)B;
-            hh[c] = valid ? hist[b] : 0u;
-            if (d < depth && g < ngroups && ch < seg_chunks) {                   // (wave-uniform)
-                const uint32_t h = hh[c], p = valid ? pd[b] : 0u, m = valid ? md[b] : (64u | 0x80u);
-                const uint32_t prev = m & 0x7fu;
-                unsigned long long *my = smin + (size_t)(g & 1) * GB;
-                bool ready = false; unsigned long long Sn = 0;
-                if (prev >= 64u) {                                               // first lane of the chunk on this counter
-                    Sn = rc[p] + h;
-                    if (h) atomicMin(&my[c * 64 + lane], Sn);
-                    ready = true;
-                }
-                unsigned long long done = __ballot(ready);
-                while (done != ~0ull) {
-                    const unsigned long long ps = __shfl(Sn, (int)(prev & 63u));
-                    const bool pr = (done >> (prev & 63u)) & 1ull;
-                    if (!ready && pr) {
-                        Sn = ps + h;
-                        if (h) atomicMin(&my[c * 64 + lane], Sn);
-                        ready = true;
-                    }
-                    done = __ballot(ready);
-                }
-                if ((m & 0x80u) && valid) rc[p] = Sn;
-            }
-        }
-        if (d == depth && g > 0) {
-            unsigned long long *src = smin + (size_t)((g - 1) & 1) * GB;
-#pragma unroll
-            for (int c = 0; c < FG; c++) {
-                const int ch = (g - 1) * FG + c;
-                const int64_t b = b0 + (int64_t)ch * 64 + lane;
-                if (ch < seg_chunks && b < (int64_t)B) {
-                    if (ph[c]) {
-                        const unsigned long long mn = src[c * 64 + lane];
-                        src[c * 64 + lane] = ~0ull;
-                        const double f = (double)mn;
-                        ft[b] = f; rt[b] = (float)(1.0 / f);
-                        hist[b] = 0;                                 // Wipe (kmerspectrum.go:58-64)
-                    } else { ft[b] = 0.0; rt[b] = __builtin_nanf(""); }
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < FG; c++) ph[c] = hh[c];
-        __syncthreads();
-    }
 }
 
 // Wave priority of the issue arbiter (0..3).  The count-min replay kernels with decay are chains of dependent LDS round trips, one
@@ -423,285 +224,256 @@ __global__ __launch_bounds__(256) void k_cmsd_base(const double *__restrict__ se
     ctrd[i] = C;
 }
 
-// Replay with decay.  Workgroup (segment, spectrum): wave d < depth replays row d of the count-min sketch over the
-// segment's bins in order; the estimate of a bin is the minimum over the rows, which the row waves form with ONE 64-bit
-// LDS atomic minimum per (row, bin) on a small staging array (the estimates are non-negative doubles, whose bit patterns
-// order like unsigned integers; +inf = "bin not in the stream").  A barrier covers CMSD_FG = 8 chunks of 64 bins; the
-// combiner wave (d == depth) reads one value per bin, writes f (fp64), 1/f (fp32), wipes the spectrum and resets the
-// staging slot while the row waves are one group ahead.
+// ------------------------------------------------------------------------------------------
+// The replay: k_cms_freq, k_cms_freq_chain, k_cmsd_freq, k_cmsd_freq_chain are the four instances of cms_replay below.
+// Workgroup (segment, spectrum): wave d < depth replays row d of the count-min sketch over the segment's bins in order, the
+// [depth][width] counters in LDS.  The estimate of a bin is the minimum over the rows, which the row waves form with ONE 64-bit
+// LDS atomic minimum per (row, bin) on a small staging array (integers, or non-negative doubles, whose bit patterns order
+// like unsigned integers).  A barrier covers CMS_FG chunks of 64 bins; the combiner wave (d == depth) is one group behind:
+// it reads one value per bin, writes f (fp64) and 1/f (fp32), wipes the spectrum and resets the staging slot.  No est arrays.
+// The row waves are a chain of dependent LDS round trips, one workgroup per CU (112 KB of counters), so the number of round
+// trips per chunk IS the kernel's time; the per-bin inputs of the WHOLE next group are requested before the current group is
+// computed: nothing else hides their latency.
 //
-// The row waves are a chain of dependent LDS round trips, one workgroup per CU (112 KB of counters), so the number of
-// round trips per chunk IS the kernel's time.  A counter is kept ADDITIVELY normalised to a base element index,
-// S = sum over its elements i of v_i * w^-(i - base), so that its value right after element j is S * w^(j - base): an element
-// only ADDS g = v * w^-(j - base) to its counter.  Every CMSD_PERIOD elements the base moves on and the row's 2000
-// counters are rescaled by w^PERIOD (the period keeps w^-(j - base) far below the fp64 range for any decay < 1).
-//
-// k_cmsd_freq (below) lets the LDS keep the bin order: ds_add_rtn_f64 returns the counter as it stood before this lane's add.
-// k_cmsd_freq_chain (here) is its FALLBACK for a device whose LDS does not apply same-address lanes of one instruction in
-// ascending lane order (lds_order_verified; HULK_FLAG_CMS_CHAIN forces it): the order inside a 64-bin chunk comes from
-// k_build_chains' static table (meta8: nearest lower lane on the same counter, last-lane flag), followed with ballots and
-// register exchanges; the same additions in the same order — bit-identical to k_cmsd_freq where the LDS does keep the order
-// (tested) — at ~1.8x its time (517 -> 450 us was this form's round-3/4 history, docs/EXPERIMENTS.md).
-constexpr int CMSD_FG = 8;            // chunks per barrier group of k_cmsd_freq
+// Arithmetic (CmsInt / CmsDecay) owns the counter type, where the counters start, the bit pattern of "no value", the row
+// step of either order and the combiner's conversion.
+// Order: LDS — the LDS keeps the bin order by itself: a returning atomic add (ds_add_rtn_u64 / ds_add_rtn_f64) hands back the
+// counter as it stood before this lane's add, same-address lanes of one instruction are applied in ascending lane order, a
+// wave's instructions in program order (tools/ubench/lds_atomic_order.hip; lds_order_verified below).  Chain — the FALLBACK
+// for a device whose LDS does not (HULK_FLAG_CMS_CHAIN forces it): the order inside a 64-bin chunk comes from the static table
+// k_build_chains wrote — meta8 = {the nearest LOWER lane of the chunk on the same counter (64: none), bit 7: the last lane on
+// its counter} — followed with ballots and register exchanges (chain_resolve); the LDS is only read by the first lane of a
+// counter's run and written by its last.  The same additions in the same order: bit-identical to the LDS order (tested), at
+// 1.3x (integer) and 1.5x (decay) its time (profiles/cms_replay.txt; docs/EXPERIMENTS.md has both forms' history).
+// ------------------------------------------------------------------------------------------
+constexpr int CMS_FG = 8;             // chunks of 64 bins per barrier group
+constexpr int CMS_GB = CMS_FG * 64;
 constexpr int CMSD_WAVE_PRIO = 0;     // s_setprio of the replay kernels (set_wave_prio)
-__global__ __launch_bounds__(512) void k_cmsd_freq_chain(uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
-                                                   const uint8_t *__restrict__ meta8, const uint32_t *__restrict__ eidx,
-                                                   const uint32_t *__restrict__ sege0, const double *__restrict__ cstart,
-                                                   double *__restrict__ f64, float *__restrict__ rcp32, int depth,
-                                                   int width, int seg_chunks, size_t row_stride, double omega,
-                                                   DevState *st, FlushBatch fb) {
+
+// Chain order, one chunk of one row: a lane is computed once its predecessor on the same counter is (whether it is comes from
+// the wave's ballot of finished lanes).  add(before) returns the counter after this lane's bin, given the counter before it
+// — what the returning atomic hands back in the LDS order — and posts the lane's estimate.
+template <class T, class Add>
+__device__ __forceinline__ void chain_resolve(T *rc, uint32_t p, uint32_t m, bool live, Add add) {
+    const uint32_t prev = m & 0x7fu;
+    bool ready = false; T Sn = 0;
+    if (prev >= 64u) { Sn = add(rc[p]); ready = true; }              // first lane of the chunk on this counter: LDS state
+    unsigned long long done = __ballot(ready);
+    while (done != ~0ull) {
+        const T before = __shfl(Sn, (int)(prev & 63u));
+        const bool pr = (done >> (prev & 63u)) & 1ull;
+        if (!ready && pr) { Sn = add(before); ready = true; }
+        done = __ballot(ready);
+    }
+    if ((m & 0x80u) && live) rc[p] = Sn;
+}
+
+// Integer counters (decay_ratio == 1): est = counter before + own count is the reference's counter after Add (countmin.go:122-127).
+struct CmsInt {
+    using Ctr = unsigned long long;
+    static constexpr unsigned long long NONE = ~0ull;
+    static constexpr bool BY_SPECTRUM = true;    // "bin not in the stream" is a zero of the spectrum: the combiner needs its values and wipes only the others
+    static constexpr bool PRUNES = true;         // k_flush_decide's skip_exact leaves only the wipe to do
+    static constexpr bool REBASES = false;
+    const Ctr *__restrict__ start;               // k_cms_base: the counters in front of every (spectrum, segment)
+    __device__ void prepare(int, int, int, size_t) {}
+    __device__ uint32_t elem(int64_t) const { return 0u; }
+    __device__ void rebase(Ctr *, uint32_t, int, int) {}
+    __device__ void lds_step(Ctr *rc, unsigned long long *est, uint32_t h, uint32_t p, uint32_t) const {
+        if (h) atomicMin(est, atomicAdd(&rc[p], (Ctr)h) + h);
+    }
+    __device__ void chain_step(Ctr *rc, unsigned long long *est, uint32_t h, uint32_t p, uint32_t, uint32_t m, bool live) const {
+        chain_resolve(rc, p, m, live, [=](Ctr before) { const Ctr Sn = before + h; if (h) atomicMin(est, Sn); return Sn; });
+    }
+    static __device__ double value(unsigned long long bits) { return (double)bits; }
+};
+
+// fp64 counters with uniform scaling (0 < decay < 1).  A counter is kept ADDITIVELY normalised to a base element index,
+// S = sum over its elements i of v_i * w^-(i - base), so that its value right after element j is S * w^(j - base): an element
+// only ADDS g = v * w^-(j - base) to its counter.  Every `period` elements the base moves on and the row's counters are
+// rescaled by w^period (the period keeps w^-(j - base) far below the fp64 range for any decay < 1).  Zero bins are transparent;
+// +inf is "bin not in the stream".  (Rounding: C = (S + v*wi) * wf — a re-association of the reference's step-by-step
+// scaling, ~1e-13 relative; bit-reproducible from run to run.)
+__shared__ double cmsd_tabf_lo[64], cmsd_tabf_hi[66], cmsd_tabi_lo[64], cmsd_tabi_hi[66];   // w^x and w^-x for x = lo + 64 hi
+struct CmsDecay {
+    using Ctr = double;
+    static constexpr unsigned long long NONE = 0x7FF0000000000000ull;
+    static constexpr bool BY_SPECTRUM = false;   // the combiner sees +inf and wipes every bin
+    static constexpr bool PRUNES = false;
+    static constexpr bool REBASES = true;        // rebase() has work to do at a chunk whatever its bins hold
+    const double *__restrict__ start;            // k_cmsd_base's cstart: the value right after element e0 - 1, S at base = e0 - 1
+    const uint32_t *__restrict__ eidx, *__restrict__ sege0;
+    double omega;
+    const uint32_t *ei; long long base; int period; double wperiod;
+    __device__ void prepare(int t, int seg, int tid, size_t B) {
+        const double lnw = log(omega);                               // < 0
+        // elements per base: |ln w| * (period + 64) <= 600  =>  w^-(j - base) <= e^600 (counters stay below ~1e270)
+        period = 4032;
+        if (-lnw * (double)(period + 64) > 600.0) period = (int)(600.0 / -lnw) - 64;
+        period &= ~63;
+        if (period < 64) period = 64;
+        wperiod = exp((double)period * lnw);
+        if (tid < 64) { cmsd_tabf_lo[tid] = exp((double)tid * lnw); cmsd_tabi_lo[tid] = exp(-(double)tid * lnw); }
+        if (tid >= 64 && tid < 64 + 66) { const int x = tid - 64; cmsd_tabf_hi[x] = exp((double)(64 * x) * lnw); cmsd_tabi_hi[x] = exp(-(double)(64 * x) * lnw); }
+        ei = eidx + (size_t)t * B;
+        base = (long long)sege0[(size_t)t * CMS_SEGS + seg] - 1;
+    }
+    __device__ uint32_t elem(int64_t b) const { return ei[b]; }
+    // move the base on when the chunk's elements would leave the tables (wave-uniform: element indices ascend with the lane;
+    // lane 0 holds the chunk's first)
+    __device__ void rebase(Ctr *rv, uint32_t j, int lane, int width) {
+        const long long jfirst = (long long)__builtin_amdgcn_readfirstlane((int)j);
+        while (jfirst - base > (long long)period) {
+            for (int i = lane; i < width; i += 64) rv[i] *= wperiod;
+            base += period;
+        }
+    }
+    // ~15 VALU + 6 LDS instructions per (row, chunk), the eight atomics of a group in flight together
+    __device__ void lds_step(Ctr *rv, unsigned long long *est, uint32_t h, uint32_t p, uint32_t j) const {
+        if (h) {
+            const uint32_t x = (uint32_t)((long long)j - base);          // 1 .. period + 64
+            const double wi = cmsd_tabi_lo[x & 63u] * cmsd_tabi_hi[x >> 6], wf = cmsd_tabf_lo[x & 63u] * cmsd_tabf_hi[x >> 6];
+            const double gv = (double)h * wi;
+            const double before = atomicAdd(&rv[p], gv);                 // ds_add_rtn_f64: the counter in bin order
+            atomicMin(est, (unsigned long long)__double_as_longlong((before + gv) * wf));
+        }
+    }
+    __device__ void chain_step(Ctr *rv, unsigned long long *est, uint32_t h, uint32_t p, uint32_t j, uint32_t m, bool live) const {
+        const uint32_t x = h ? (uint32_t)((long long)j - base) : 0u;     // 1 .. period + 64 (unused for bins not in the stream)
+        const double wi = cmsd_tabi_lo[x & 63u] * cmsd_tabi_hi[x >> 6], wf = cmsd_tabf_lo[x & 63u] * cmsd_tabf_hi[x >> 6];
+        const double gv = (double)h * wi;
+        chain_resolve(rv, p, m, live, [=](double before) {
+            if (!h) return before;
+            const double Sn = before + gv;
+            atomicMin(est, (unsigned long long)__double_as_longlong(Sn * wf));
+            return Sn;
+        });
+    }
+    static __device__ double value(unsigned long long bits) { return __longlong_as_double((long long)bits); }
+};
+
+template <bool CHAIN, class A>
+__device__ __forceinline__ void cms_replay(A ar, uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
+                                           const uint8_t *__restrict__ meta8, double *__restrict__ f64, float *__restrict__ rcp32,
+                                           int depth, int width, int seg_chunks, size_t row_stride, DevState *st,
+                                           const FlushBatch &fb) {
+    using Ctr = typename A::Ctr;
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int GB = CMSD_FG * 64;
-    constexpr unsigned long long INF_BITS = 0x7FF0000000000000ull;
-    double *lval = (double *)smem;                                               // [depth][width] normalised counters
-    unsigned long long *smin = (unsigned long long *)(lval + (size_t)depth * width);   // [2][GB] min over the rows, as bits
-    __shared__ double tabf_lo[64], tabf_hi[66], tabi_lo[64], tabi_hi[66];          // w^x and w^-x for x = lo + 64 hi
+    Ctr *lctr = (Ctr *)smem;                                                     // [depth][width]
+    unsigned long long *smin = (unsigned long long *)(lctr + (size_t)depth * width);   // [2][CMS_GB] minimum over the rows, as bits
     const int seg = blockIdx.x, t = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;                  // waves 0..depth-1: rows; wave depth: combiner
     const uint32_t gomask = batch_gomask(st, fb);
     const bool go = (gomask >> t) & 1u;
     const uint32_t slot = ring_slot(fb, t);
     if (seg == 0 && tid == 0) {
         const unsigned used = st->used[fb.parity][slot];
-        if (used != 0 && !go) set_error(st, -5);
+        if (used != 0 && !go) set_error(st, -5);                                 // "not used yet" (kmerspectrum.go:94-96)
         if (go) atomicAdd(&st->n_elements, (unsigned long long)used);
     }
     if (!go) return;
     const size_t B = (size_t)fb.num_bins;
-    const double lnw = log(omega);                               // < 0
-    int period = 4032;
-    if (-lnw * (double)(period + 64) > 600.0) period = (int)(600.0 / -lnw) - 64;
-    period &= ~63;
-    if (period < 64) period = 64;
+    uint32_t *hist = hists + (size_t)slot * B;
+    const int64_t b0 = (int64_t)seg * seg_chunks * 64;
+    if (A::PRUNES && st->skip_exact[fb.parity]) {                                // k_flush_decide: only Wipe is left to do
+        const int64_t w1 = b0 + (int64_t)seg_chunks * 64;
+        for (int64_t b = b0 + tid; b < w1 && b < (int64_t)B; b += blockDim.x) hist[b] = 0;
+        return;
+    }
+    ar.prepare(t, seg, tid, B);
     {
-        const double *bt = cstart + (((size_t)t * depth) * CMS_SEGS) * width;
+        const Ctr *bt = ar.start + (((size_t)t * depth) * CMS_SEGS) * width;
         for (int i = tid; i < depth * width; i += blockDim.x) {
             const int dd = i / width, p = i - dd * width;
-            lval[i] = bt[((size_t)dd * CMS_SEGS + seg) * width + p];
+            lctr[i] = bt[((size_t)dd * CMS_SEGS + seg) * width + p];
         }
-        for (int i = tid; i < 2 * GB; i += blockDim.x) smin[i] = INF_BITS;
-        if (tid < 64) { tabf_lo[tid] = exp((double)tid * lnw); tabi_lo[tid] = exp(-(double)tid * lnw); }
-        if (tid >= 64 && tid < 64 + 66) { const int x = tid - 64; tabf_hi[x] = exp((double)(64 * x) * lnw); tabi_hi[x] = exp(-(double)(64 * x) * lnw); }
+        for (int i = tid; i < 2 * CMS_GB; i += blockDim.x) smin[i] = A::NONE;
     }
     __syncthreads();
-    uint32_t *hist = hists + (size_t)slot * B;
-    const uint32_t *ei = eidx + (size_t)t * B;
     double *ft = f64 + (size_t)t * B;
     float *rt = rcp32 + (size_t)t * row_stride;
-    const int64_t b0 = (int64_t)seg * seg_chunks * 64;
-    long long base = (long long)sege0[(size_t)t * CMS_SEGS + seg] - 1;
-    const double wperiod = exp((double)period * lnw);
-    const int ngroups = (seg_chunks + CMSD_FG - 1) / CMSD_FG;
+    const int ngroups = (seg_chunks + CMS_FG - 1) / CMS_FG;
     const uint16_t *pd = pos16 + (size_t)(d < depth ? d : 0) * B;
-    const uint8_t *md = meta8 + (size_t)(d < depth ? d : 0) * B;
-    double *rv = lval + (size_t)(d < depth ? d : 0) * width;
-    uint32_t nh[CMSD_FG], np_[CMSD_FG], nm[CMSD_FG], nj[CMSD_FG];
+    const uint8_t *md = CHAIN ? meta8 + (size_t)(d < depth ? d : 0) * B : nullptr;
+    Ctr *rc = lctr + (size_t)(d < depth ? d : 0) * width;
+    struct Group { uint32_t h[CMS_FG], p[CMS_FG], j[CMS_FG], m[CMS_FG]; } nx, cu;   // spectrum value, counter, element index, meta8
     auto fetch = [&](int g) {
 #pragma unroll
-        for (int c = 0; c < CMSD_FG; c++) {
-            const int ch = g * CMSD_FG + c;
+        for (int c = 0; c < CMS_FG; c++) {
+            const int ch = g * CMS_FG + c;
             const int64_t b = b0 + (int64_t)ch * 64 + lane;
-            nh[c] = 0; np_[c] = 0; nm[c] = 64u | 0x80u; nj[c] = 0;
-            if (d < depth && ch < seg_chunks && b < (int64_t)B) { nh[c] = hist[b]; np_[c] = pd[b]; nm[c] = md[b]; nj[c] = ei[b]; }
+            nx.h[c] = 0; nx.p[c] = 0; nx.j[c] = 0; nx.m[c] = 64u | 0x80u;
+            if ((d < depth || A::BY_SPECTRUM) && ch < seg_chunks && b < (int64_t)B) {
+                nx.h[c] = hist[b];
+                if (d < depth) { nx.p[c] = pd[b]; nx.j[c] = ar.elem(b); if (CHAIN) nx.m[c] = md[b]; }
+            }
         }
     };
     fetch(0);
-    uint32_t chh[CMSD_FG], cp[CMSD_FG], cm[CMSD_FG], cj[CMSD_FG];
-    for (int g = 0; g <= ngroups; g++) {
+    uint32_t ph[CMS_FG];                                        // combiner: spectrum values of the group it finishes next
 #pragma unroll
-        for (int c = 0; c < CMSD_FG; c++) { chh[c] = nh[c]; cp[c] = np_[c]; cm[c] = nm[c]; cj[c] = nj[c]; }
+    for (int c = 0; c < CMS_FG; c++) ph[c] = 0;
+    for (int g = 0; g <= ngroups; g++) {
+        cu = nx;
         if (g + 1 < ngroups) fetch(g + 1);
         if (d < depth && g < ngroups) {
-            unsigned long long *my = smin + (size_t)(g & 1) * GB;
+            unsigned long long *my = smin + (size_t)(g & 1) * CMS_GB + lane;
 #pragma unroll
-            for (int c = 0; c < CMSD_FG; c++) {
-                const int ch = g * CMSD_FG + c;
-                if (ch >= seg_chunks) break;
-                const int64_t b = b0 + (int64_t)ch * 64 + lane;
-                const uint32_t h = chh[c], p = cp[c], m = cm[c]; const long long j = (long long)cj[c];
-                {
-                    const long long jfirst = (long long)__builtin_amdgcn_readfirstlane((int)cj[c]);
-                    while (jfirst - base > (long long)period) {
-                        for (int i = lane; i < width; i += 64) rv[i] *= wperiod;
-                        base += period;
-                    }
-                }
-                const uint32_t x = h ? (uint32_t)(j - base) : 0u;                // 1 .. period + 64 (unused for bins not in the stream)
-                const double wi = tabi_lo[x & 63u] * tabi_hi[x >> 6], wf = tabf_lo[x & 63u] * tabf_hi[x >> 6];
-                const double gv = (double)h * wi;
-                // resolve the lanes in same-counter order: a lane is computed once its predecessor is (whether it is comes
-                // from the wave's ballot of finished lanes).  `before` is what ds_add_rtn_f64 returns in k_cmsd_freq.
-                const uint32_t prev = m & 0x7fu;
-                bool ready = false; double Sn = 0.0;
-                if (prev >= 64u) {                                  // first lane of the chunk on this counter: LDS state
-                    const double before = rv[p];
-                    if (h) { Sn = before + gv; atomicMin(&my[c * 64 + lane], (unsigned long long)__double_as_longlong(Sn * wf)); }
-                    else Sn = before;
-                    ready = true;
-                }
-                unsigned long long done = __ballot(ready);
-                while (done != ~0ull) {
-                    const double before = __shfl(Sn, (int)(prev & 63u));
-                    const bool pr = (done >> (prev & 63u)) & 1ull;
-                    if (!ready && pr) {
-                        if (h) { Sn = before + gv; atomicMin(&my[c * 64 + lane], (unsigned long long)__double_as_longlong(Sn * wf)); }
-                        else Sn = before;
-                        ready = true;
-                    }
-                    done = __ballot(ready);
-                }
-                if ((m & 0x80u) && b < (int64_t)B) rv[p] = Sn;
+            for (int c = 0; c < CMS_FG; c++) {
+                const int ch = g * CMS_FG + c;
+                // a chunk beyond the segment's end holds no bin.  k_cms_freq is left without this test: its step does nothing
+                // where h == 0, and with the test (eight more scalar compares and exec masks per group) it took 57.61 us
+                // against the parent's 57.29, spread 0.09; without it 55.70 against 56.92 (profiles/cms_replay.txt)
+                if ((CHAIN || A::REBASES) && ch >= seg_chunks) continue;
+                ar.rebase(rc, cu.j[c], lane, width);
+                if (CHAIN) ar.chain_step(rc, &my[c * 64], cu.h[c], cu.p[c], cu.j[c], cu.m[c], b0 + (int64_t)ch * 64 + lane < (int64_t)B);
+                else ar.lds_step(rc, &my[c * 64], cu.h[c], cu.p[c], cu.j[c]);
             }
         }
         if (d == depth && g > 0) {
-            unsigned long long *src = smin + (size_t)((g - 1) & 1) * GB;
+            unsigned long long *src = smin + (size_t)((g - 1) & 1) * CMS_GB + lane;
 #pragma unroll
-            for (int c = 0; c < CMSD_FG; c++) {
-                const int ch = (g - 1) * CMSD_FG + c;
+            for (int c = 0; c < CMS_FG; c++) {
+                const int ch = (g - 1) * CMS_FG + c;
                 const int64_t b = b0 + (int64_t)ch * 64 + lane;
                 if (ch < seg_chunks && b < (int64_t)B) {
-                    const unsigned long long bits = src[c * 64 + lane];
-                    src[c * 64 + lane] = INF_BITS;
-                    if (bits != INF_BITS) {
-                        const double mn = __longlong_as_double((long long)bits);
-                        ft[b] = mn; rt[b] = (float)(1.0 / mn);
+                    const bool look = !A::BY_SPECTRUM || ph[c] != 0;
+                    unsigned long long bits = A::NONE;
+                    if (look) { bits = src[c * 64]; src[c * 64] = A::NONE; }
+                    if (A::BY_SPECTRUM ? look : bits != A::NONE) {
+                        const double f = A::value(bits);
+                        ft[b] = f; rt[b] = (float)(1.0 / f);
                     } else { ft[b] = 0.0; rt[b] = __builtin_nanf(""); }
-                    hist[b] = 0;
+                    if (look) hist[b] = 0;                           // Wipe (kmerspectrum.go:58-64)
                 }
             }
         }
+#pragma unroll
+        for (int c = 0; c < CMS_FG; c++) ph[c] = cu.h[c];       // group g is finished by the combiner at g+1
         __syncthreads();
     }
 }
 
-
-// The same replay with the counter kept ADDITIVELY normalised, S = sum over its elements i of v_i * w^-(i - base), so that its
-// value right after element j is S * w^(j - base): an element then only ADDS g = v * w^-(j - base) to its counter, and the
-// LDS does the bin-order bookkeeping by itself — ds_add_rtn_f64 returns the counter as it stood before this lane's add,
-// same-address lanes of one instruction are applied in ascending lane order and the instructions of a wave in program order
-// (tools/ubench/lds_atomic_order.hip checks both on the chip).  No "previous lane on the same counter" table, no ballots,
-// no register exchanges, no read-then-write hazard between consecutive chunks: the eight atomics of a group are in flight
-// together.  ~15 VALU + 6 LDS instructions per (row, chunk) where the chain form has ~90 VALU: 450 -> see
-// profiles/r05_c3_kernel_stats_serial.md.  (Rounding: C = (S + v*wi) * wf against the chain form's S*wf + v — both are
-// re-associations of the reference's step-by-step scaling, ~1e-13 relative; bit-reproducible from run to run.)
-template <int FG>
-__global__ __launch_bounds__(512) void k_cmsd_freq(uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
-                                                   const uint32_t *__restrict__ eidx, const uint32_t *__restrict__ sege0,
-                                                   const double *__restrict__ cstart, double *__restrict__ f64,
-                                                   float *__restrict__ rcp32, int depth, int width, int seg_chunks,
-                                                   size_t row_stride, double omega, DevState *st, FlushBatch fb) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int GB = FG * 64;
-    constexpr unsigned long long INF_BITS = 0x7FF0000000000000ull;
-    double *lval = (double *)smem;                                               // [depth][width] normalised counters
-    unsigned long long *smin = (unsigned long long *)(lval + (size_t)depth * width);   // [2][GB] min over the rows, as bits
-    __shared__ double tabf_lo[64], tabf_hi[66], tabi_lo[64], tabi_hi[66];          // w^x and w^-x for x = lo + 64 hi
+#define CMS_REPLAY_IO uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16, double *__restrict__ f64, \
+                      float *__restrict__ rcp32, int depth, int width, int seg_chunks, size_t row_stride, DevState *st, FlushBatch fb
+__global__ __launch_bounds__(512) void k_cms_freq(const unsigned long long *__restrict__ base, CMS_REPLAY_IO) {
+    cms_replay<false>(CmsInt{base}, hists, pos16, nullptr, f64, rcp32, depth, width, seg_chunks, row_stride, st, fb);
+}
+__global__ __launch_bounds__(512) void k_cms_freq_chain(const unsigned long long *__restrict__ base, const uint8_t *__restrict__ meta8,
+                                                        CMS_REPLAY_IO) {
+    cms_replay<true>(CmsInt{base}, hists, pos16, meta8, f64, rcp32, depth, width, seg_chunks, row_stride, st, fb);
+}
+__global__ __launch_bounds__(512) void k_cmsd_freq(const double *__restrict__ cstart, const uint32_t *__restrict__ eidx,
+                                                   const uint32_t *__restrict__ sege0, double omega, CMS_REPLAY_IO) {
     set_wave_prio(fb.prio);
-    const int seg = blockIdx.x, t = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;
-    const uint32_t gomask = batch_gomask(st, fb);
-    const bool go = (gomask >> t) & 1u;
-    const uint32_t slot = ring_slot(fb, t);
-    if (seg == 0 && tid == 0) {
-        const unsigned used = st->used[fb.parity][slot];
-        if (used != 0 && !go) set_error(st, -5);
-        if (go) atomicAdd(&st->n_elements, (unsigned long long)used);
-    }
-    if (!go) return;
-    const size_t B = (size_t)fb.num_bins;
-    const double lnw = log(omega);                               // < 0
-    // elements per base: |ln w| * (period + 64) <= 600  =>  w^-(j - base) <= e^600 (counters stay below ~1e270)
-    int period = 4032;
-    if (-lnw * (double)(period + 64) > 600.0) period = (int)(600.0 / -lnw) - 64;
-    period &= ~63;
-    if (period < 64) period = 64;
-    {
-        const double *bt = cstart + (((size_t)t * depth) * CMS_SEGS) * width;
-        for (int i = tid; i < depth * width; i += blockDim.x) {
-            const int dd = i / width, p = i - dd * width;
-            lval[i] = bt[((size_t)dd * CMS_SEGS + seg) * width + p];       // value as of element e0 - 1: see `base` below
-        }
-        for (int i = tid; i < 2 * GB; i += blockDim.x) smin[i] = INF_BITS;
-        if (tid < 64) { tabf_lo[tid] = exp((double)tid * lnw); tabi_lo[tid] = exp(-(double)tid * lnw); }
-        if (tid >= 64 && tid < 64 + 66) { const int x = tid - 64; tabf_hi[x] = exp((double)(64 * x) * lnw); tabi_hi[x] = exp(-(double)(64 * x) * lnw); }
-    }
-    __syncthreads();
-    uint32_t *hist = hists + (size_t)slot * B;
-    const uint32_t *ei = eidx + (size_t)t * B;
-    double *ft = f64 + (size_t)t * B;
-    float *rt = rcp32 + (size_t)t * row_stride;
-    const int64_t b0 = (int64_t)seg * seg_chunks * 64;
-    // a counter holding S stands for the value S * w^(j - base) right after element j has been added (cstart = the value right
-    // after element e0 - 1: S = cstart at base = e0 - 1)
-    long long base = (long long)sege0[(size_t)t * CMS_SEGS + seg] - 1;
-    const double wperiod = exp((double)period * lnw);
-    const int ngroups = (seg_chunks + FG - 1) / FG;
-    const uint16_t *pd = pos16 + (size_t)(d < depth ? d : 0) * B;
-    double *rv = lval + (size_t)(d < depth ? d : 0) * width;
-    // row waves: the three per-bin inputs of the WHOLE next group (8 chunks = 24 loads per lane) are requested before the
-    // current group is computed: with one workgroup per CU nothing else hides their latency
-    uint32_t nh[FG], np_[FG], nj[FG];
-    auto fetch = [&](int g) {
-#pragma unroll
-        for (int c = 0; c < FG; c++) {
-            const int ch = g * FG + c;
-            const int64_t b = b0 + (int64_t)ch * 64 + lane;
-            nh[c] = 0; np_[c] = 0; nj[c] = 0;
-            if (d < depth && ch < seg_chunks && b < (int64_t)B) { nh[c] = hist[b]; np_[c] = pd[b]; nj[c] = ei[b]; }
-        }
-    };
-    fetch(0);
-    uint32_t chh[FG], cp[FG], cj[FG];
-    for (int g = 0; g <= ngroups; g++) {
-#pragma unroll
-        for (int c = 0; c < FG; c++) { chh[c] = nh[c]; cp[c] = np_[c]; cj[c] = nj[c]; }
-        if (g + 1 < ngroups) fetch(g + 1);
-        if (d < depth && g < ngroups) {
-            unsigned long long *my = smin + (size_t)(g & 1) * GB;
-#pragma unroll
-            for (int c = 0; c < FG; c++) {
-                const int ch = g * FG + c;
-                if (ch >= seg_chunks) continue;
-                const uint32_t h = chh[c], p = cp[c]; const long long j = (long long)cj[c];
-                // move the base on when the chunk's elements would leave the tables (wave-uniform: element indices
-                // ascend with the lane; lane 0 holds the chunk's first)
-                {
-                    const long long jfirst = (long long)__builtin_amdgcn_readfirstlane((int)cj[c]);
-                    while (jfirst - base > (long long)period) {
-                        for (int i = lane; i < width; i += 64) rv[i] *= wperiod;
-                        base += period;
-                    }
-                }
-                if (h) {
-                    const uint32_t x = (uint32_t)(j - base);                     // 1 .. period + 64
-                    const double wi = tabi_lo[x & 63u] * tabi_hi[x >> 6], wf = tabf_lo[x & 63u] * tabf_hi[x >> 6];
-                    const double gv = (double)h * wi;
-                    const double before = atomicAdd(&rv[p], gv);                 // ds_add_rtn_f64: the counter in bin order
-                    const double C = (before + gv) * wf;
-                    atomicMin(&my[c * 64 + lane], (unsigned long long)__double_as_longlong(C));
-                }
-            }
-        }
-        if (d == depth && g > 0) {
-            unsigned long long *src = smin + (size_t)((g - 1) & 1) * GB;
-#pragma unroll
-            for (int c = 0; c < FG; c++) {
-                const int ch = (g - 1) * FG + c;
-                const int64_t b = b0 + (int64_t)ch * 64 + lane;
-                if (ch < seg_chunks && b < (int64_t)B) {
-                    const unsigned long long bits = src[c * 64 + lane];
-                    src[c * 64 + lane] = INF_BITS;
-                    if (bits != INF_BITS) {
-                        const double mn = __longlong_as_double((long long)bits);
-                        ft[b] = mn; rt[b] = (float)(1.0 / mn);
-                    } else { ft[b] = 0.0; rt[b] = __builtin_nanf(""); }
-                    hist[b] = 0;
-                }
-            }
-        }
-        __syncthreads();
-    }
+    cms_replay<false>(CmsDecay{cstart, eidx, sege0, omega}, hists, pos16, nullptr, f64, rcp32, depth, width, seg_chunks, row_stride, st, fb);
 }
+__global__ __launch_bounds__(512) void k_cmsd_freq_chain(const double *__restrict__ cstart, const uint32_t *__restrict__ eidx,
+                                                         const uint32_t *__restrict__ sege0, double omega,
+                                                         const uint8_t *__restrict__ meta8, CMS_REPLAY_IO) {
+    cms_replay<true>(CmsDecay{cstart, eidx, sege0, omega}, hists, pos16, meta8, f64, rcp32, depth, width, seg_chunks, row_stride, st, fb);
+}
+#undef CMS_REPLAY_IO
 
 // ==========================================================================================
 // Concept drift (decay_ratio != 1): reference src/countmin/countmin.go:49-56,103-110,141-147 and
@@ -785,10 +557,9 @@ hipError_t launch_cms_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t 
                                unsigned long long *d_ctr, uint32_t *d_segsum, unsigned long long *d_base,
                                double *d_f64, float *d_rcp32, int depth, int width, size_t row_stride,
                                DevState *st, const FlushBatch &fb, bool chain) {
-    const int chunks = (fb.num_bins + 63) / 64;
-    const int seg_chunks = (chunks + CMS_SEGS - 1) / CMS_SEGS;
+    const int seg_chunks = cms_seg_chunks(fb.num_bins);
     const size_t lds1 = (size_t)depth * width * 4;
-    const size_t lds3 = (size_t)depth * width * 8 + (size_t)2 * 8 * 64 * 8;
+    const size_t lds3 = (size_t)depth * width * 8 + (size_t)2 * CMS_GB * 8;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void *)k_cms_freq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
@@ -803,12 +574,12 @@ hipError_t launch_cms_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t 
     hipLaunchKernelGGL(k_cms_base, dim3((depth * width + 255) / 256), dim3(256), 0, s, d_segsum, d_ctr, d_base, depth, width, st, fb);
     if (chain) {
         prof_mark(s, "k_cms_freq_chain");
-        hipLaunchKernelGGL(k_cms_freq_chain, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_hists, d_pos16, d_meta8, d_base, d_f64,
+        hipLaunchKernelGGL(k_cms_freq_chain, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_base, d_meta8, d_hists, d_pos16, d_f64,
                            d_rcp32, depth, width, seg_chunks, row_stride, st, fb);
     }
     else {
         prof_mark(s, "k_cms_freq");
-        hipLaunchKernelGGL(k_cms_freq, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_hists, d_pos16, d_base, d_f64,
+        hipLaunchKernelGGL(k_cms_freq, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_base, d_hists, d_pos16, d_f64,
                            d_rcp32, depth, width, seg_chunks, row_stride, st, fb);
     }
     return hipGetLastError();
@@ -822,17 +593,15 @@ hipError_t launch_cmsd_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t
                                 int depth, int width, size_t row_stride, double omega, DevState *st, const FlushBatch &fb_in,
                                 hipEvent_t freq_begin, hipEvent_t freq_end, bool chain_form) {
     FlushBatch fb = fb_in;
-    const int chunks = (fb.num_bins + 63) / 64;
-    const int seg_chunks = (chunks + CMS_SEGS - 1) / CMS_SEGS;
+    const int seg_chunks = cms_seg_chunks(fb.num_bins);
     if (depth > 8) return hipErrorInvalidValue;                     // k_cmsd_segsum: one wave per row, 8 waves
     { static const char *e = HULK_EXP_ENV("HULK_CMSD_PRIO"); fb.prio = e ? atoi(e) : CMSD_WAVE_PRIO; }
     const size_t lds1 = (size_t)depth * width * 8 + (size_t)2 * 512 * 8;
-    const size_t lds3 = (size_t)depth * width * 8 + (size_t)2 * CMSD_FG * 64 * 8;
+    const size_t lds3 = (size_t)depth * width * 8 + (size_t)2 * CMS_GB * 8;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void *)k_cmsd_segsum, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_cmsd_freq<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_cmsd_freq<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds3 + (size_t)2 * 8 * 64 * 8));
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_cmsd_freq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_cmsd_freq_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
         if (e != hipSuccess) return e;
         attr_set = true;
@@ -845,21 +614,15 @@ hipError_t launch_cmsd_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t
                        depth, width, st, fb);
     if (freq_begin) { const hipError_t e = hipEventRecord(freq_begin, s); if (e != hipSuccess) return e; }   // bench.py: k_cmsd_freq alone
     const bool chain = chain_form || HULK_EXP_ENV("HULK_CMSD_CHAIN") != nullptr;   // the fallback (lds_order_verified / HULK_FLAG_CMS_CHAIN)
-    static const bool fg16 = HULK_EXP_ENV("HULK_CMSD_FG16") != nullptr;        // 16 chunks per barrier group (A/B)
     if (chain) {
         prof_mark(s, "k_cmsd_freq_chain");
-        hipLaunchKernelGGL(k_cmsd_freq_chain, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_hists, d_pos16, d_meta8, d_eidx, d_sege0,
-                           d_cstart, d_f64, d_rcp32, depth, width, seg_chunks, row_stride, omega, st, fb);
-    }
-    else if (fg16) {
-        prof_mark(s, "k_cmsd_freq");
-        hipLaunchKernelGGL(k_cmsd_freq<16>, dim3(CMS_SEGS, fb.count), dim3(512), lds3 + (size_t)2 * 8 * 64 * 8, s, d_hists, d_pos16, d_eidx, d_sege0,
-                           d_cstart, d_f64, d_rcp32, depth, width, seg_chunks, row_stride, omega, st, fb);
+        hipLaunchKernelGGL(k_cmsd_freq_chain, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_cstart, d_eidx, d_sege0, omega, d_meta8,
+                           d_hists, d_pos16, d_f64, d_rcp32, depth, width, seg_chunks, row_stride, st, fb);
     }
     else {
         prof_mark(s, "k_cmsd_freq");
-        hipLaunchKernelGGL(k_cmsd_freq<8>, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_hists, d_pos16, d_eidx, d_sege0,
-                           d_cstart, d_f64, d_rcp32, depth, width, seg_chunks, row_stride, omega, st, fb);
+        hipLaunchKernelGGL(k_cmsd_freq, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_cstart, d_eidx, d_sege0, omega, d_hists,
+                           d_pos16, d_f64, d_rcp32, depth, width, seg_chunks, row_stride, st, fb);
     }
     if (freq_end) { const hipError_t e = hipEventRecord(freq_end, s); if (e != hipSuccess) return e; }
     return hipGetLastError();
@@ -1007,25 +770,11 @@ __global__ __launch_bounds__(512) void k_shard_local(uint32_t *__restrict__ hist
     uint32_t *lctr = (uint32_t *)smem;                           // [depth][width]
     const int seg = blockIdx.x, t = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, d = tid >> 6;  // waves 0..depth-1: rows; wave depth: used bins
-    for (int i = tid; i < depth * width; i += blockDim.x) lctr[i] = 0;
-    __syncthreads();
     const size_t B = (size_t)fb.num_bins;
     uint32_t *hist = hists + (size_t)ring_slot(fb, t) * B;
     const int64_t b0 = (int64_t)seg * seg_chunks * 64;
-    if (d < depth) {
-        const uint16_t *pd = pos16 + (size_t)d * B;
-        for (int c0 = 0; c0 < seg_chunks; c0 += 8) {              // 8 chunks of loads in flight
-            uint32_t h[8]; uint32_t p[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int64_t b = b0 + (int64_t)(c0 + u) * 64 + lane;
-                const bool ok = (c0 + u < seg_chunks) && b < (int64_t)B;
-                h[u] = ok ? hist[b] : 0u; p[u] = ok ? pd[b] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) if (h[u]) atomicAdd(&lctr[d * width + p[u]], h[u]);
-        }
-    } else if (d == depth) {
+    cms_seg_row_sums(lctr, hist, pos16, B, b0, depth, width, seg_chunks);
+    if (d == depth) {
         unsigned cnt = 0;
         for (int c0 = 0; c0 < seg_chunks; c0++) {
             const int64_t b = b0 + (int64_t)c0 * 64 + lane;
@@ -1107,8 +856,7 @@ hipError_t launch_shard_check(hipStream_t s, const uint32_t *d_hdr_all, uint32_t
 hipError_t launch_shard_local(hipStream_t s, uint32_t *d_hists, const uint16_t *d_pos16, uint32_t *d_hdr, uint32_t *d_delta,
                               int depth, int width, const FlushBatch &fb) {
     if (fb.count == 0) return hipSuccess;
-    const int chunks = (fb.num_bins + 63) / 64;
-    const int seg_chunks = (chunks + CMS_SEGS - 1) / CMS_SEGS;
+    const int seg_chunks = cms_seg_chunks(fb.num_bins);
     prof_mark(s, "k_shard_local");
     hipLaunchKernelGGL(k_shard_local, dim3(CMS_SEGS, fb.count), dim3(512), (size_t)depth * width * 4, s, d_hists, d_pos16, d_hdr,
                        d_delta, depth, width, seg_chunks, fb);

@@ -82,6 +82,39 @@ def test_forced_chain_fallback_is_bit_identical_and_matches_the_oracle(k, S, int
     o.close()
 
 
+@pytest.mark.parametrize("decay", [1.0, 0.02])
+@pytest.mark.parametrize("whole_batch_bound", [True, False])
+def test_segments_without_bins_in_all_four_forms(decay, whole_batch_bound):
+    """k = 7: 2,401 bins are 38 chunks of 64, so a segment is 3 chunks, segments 13-15 start beyond the last bin and segment 12 is
+    ragged (its last chunk has 33 live lanes).  Dense spectra (values 1-40: nearly every chunk has lanes that share a counter)
+    through the histogram hook, integer and decayed arithmetic, LDS and chain order; without the whole-batch bound every flush
+    runs the replay, with it the later ones may take the wipe-only exit."""
+    from hulk_amd import _lib
+    from oracle import pyorc
+    import hulk_amd
+    k, S = 7, 24
+    B = k ** 4
+    rng = np.random.default_rng(7)
+    hists = [((rng.random(B) < dens) * rng.integers(1, 41, size=B)).astype(np.uint32) for dens in (1.0, 0.9, 1.0, 0.6)]
+    prune = 0 if whole_batch_bound else _lib.HULK_FLAG_NO_SKIP
+    out = []
+    for s in (pyorc.Sketcher(k, 3, S, 0, decay, 0),
+              hulk_amd.GpuSketcher(k, 3, S, decay_ratio=decay, flags=prune),
+              hulk_amd.GpuSketcher(k, 3, S, decay_ratio=decay, flags=prune | _lib.HULK_FLAG_CMS_CHAIN)):
+        for h in hists:
+            s.add_histogram(h); s.flush()
+        out.append(s.sketch() + (s.cms(),))
+        s.close()
+    (om, ow, oc), a, b = out
+    assert np.array_equal(a[0], b[0])
+    assert np.array_equal(a[1].view(np.uint64), b[1].view(np.uint64))
+    assert np.array_equal(a[2].view(np.uint64), b[2].view(np.uint64))
+    for m, w, c in (a, b):
+        assert np.array_equal(om, m)
+        assert np.allclose(w, ow, rtol=1e-7 if decay != 1.0 else 1e-9, atol=0)
+        assert np.allclose(c, oc, rtol=1e-9, atol=1e-300)
+
+
 def test_a_probe_that_reports_a_violation_selects_the_fallback():
     """The checker itself: in the profiling build HULK_LDS_PROBE_SABOTAGE makes one lane's expectation wrong, which is what a
     device with another lane order would look like to it — the context must then run the chain-form kernels, say so on stderr
