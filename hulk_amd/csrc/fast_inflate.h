@@ -11,6 +11,7 @@
 // Only what the gzip reader of the reference accepts is accepted (compress/gzip + compress/flate, Go 1.12):
 // stored, fixed and dynamic blocks, distances up to 32 KiB, over-subscribed or incomplete code sets are errors
 // (a distance code set with a single code is allowed, as in zlib and Go).
+// Tested against streams of other encoders' shapes too, not only zlib's (tests/deflate_craft.py, tests/test_deflate_crafted_cpu.py).
 #pragma once
 #include <stdint.h>
 #include <string.h>

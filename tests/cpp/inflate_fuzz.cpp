@@ -3,6 +3,7 @@
 // block kinds: independently compressed chunks joined at Z_FULL_FLUSH points), fed in random input
 // pieces (down to 1 byte) with random output pieces, so that every resume point of the decoder is exercised.
 // usage: inflate_fuzz [cases] [seed]      exit code 0 = all equal
+//        inflate_fuzz --corpus FILE      the crafted streams of tests/deflate_craft.py (see corpus_main)
 #include "../../hulk_amd/csrc/fast_inflate.h"
 #include "../../hulk_amd/csrc/par_inflate.h"
 #include "../../hulk_amd/csrc/crc32_clmul.h"
@@ -149,7 +150,7 @@ static bool spec_check(const std::vector<uint8_t> &src, const std::vector<uint8_
     if (b.stop != SPEC_LINK || at + b.out_len != src.size()) { printf("spec: from boundary %zu: stop %d, %zu + %zu of %zu\n", pick, (int)b.stop, at, b.out_len, src.size()); return false; }
     std::vector<uint8_t> res(b.out_len);
     spec_resolve(b.base, b.out_len, lut.data(), res.data());
-    if (memcmp(res.data(), src.data() + at, b.out_len) != 0) { printf("spec: resolved text differs from boundary %zu on\n", pick); return false; }
+    if (b.out_len && memcmp(res.data(), src.data() + at, b.out_len) != 0) { printf("spec: resolved text differs from boundary %zu on\n", pick); return false; }
     return true;
 }
 
@@ -165,7 +166,43 @@ static bool crc_check() {
     return true;
 }
 
+// --corpus FILE: streams made by tests/deflate_craft.py (shapes zlib's encoder never writes).  Records of
+// [u8 kind][u32 n][name][u32 n][deflate stream][u32 n][text], little endian; kind 0 = valid: Decoder gives the text at every
+// pairing of input pieces 1 / 7 / 300 / 2^20 with output pieces 1 / 600 / 2^22, and spec_check holds; kind 1 = zlib refuses the
+// stream: ERROR at every pairing; kind 2 = zlib inflates it to the text (bytes may follow the final block): DONE with the text.
+static int corpus_main(const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { printf("cannot open %s\n", path); return 2; }
+    auto u32 = [&](uint32_t &v) { uint8_t b[4]; if (fread(b, 1, 4, f) != 4) return false; v = b[0] | b[1] << 8 | b[2] << 16 | (uint32_t)b[3] << 24; return true; };
+    auto blob = [&](std::vector<uint8_t> &v) { uint32_t n; if (!u32(n)) return false; v.resize(n); return n == 0 || fread(v.data(), 1, n, f) == n; };
+    static const size_t pieces[4] = {1, 7, 300, (size_t)1 << 20}, opieces[3] = {1, 600, (size_t)1 << 22};
+    Decoder *d = new Decoder;
+    int n_streams = 0, bad = 0, kinds[3] = {0, 0, 0};
+    for (int kind; (kind = fgetc(f)) != EOF; n_streams++) {
+        std::vector<uint8_t> name, comp, text;
+        if (kind > 2 || !blob(name) || !blob(comp) || !blob(text)) { printf("corpus file damaged at record %d\n", n_streams); return 2; }
+        const std::string nm(name.begin(), name.end());
+        kinds[kind]++;
+        for (size_t piece : pieces)
+            for (size_t opiece : opieces) {
+                std::vector<uint8_t> res; std::string err;
+                const bool ok = decode(*d, comp, piece, opiece, kind == 1 ? 70000 : text.size(), res, err);
+                const bool state_error = d->state == Decoder::ERROR;
+                if (kind == 1 ? (ok || !state_error) : (!ok || res != text)) {
+                    bad++;
+                    printf("FAIL %s: piece=%zu opiece=%zu ok=%d err=%s got=%zu of %zu\n", nm.c_str(), piece, opiece, (int)ok, err.c_str(), res.size(), text.size());
+                }
+            }
+        if (kind == 0 && !spec_check(text, comp)) { bad++; printf("FAIL spec %s\n", nm.c_str()); }
+    }
+    fclose(f);
+    delete d;
+    printf("corpus: %d streams (%d valid, %d refused, %d accepted with a flaw around them), %d bad\n", n_streams, kinds[0], kinds[1], kinds[2], bad);
+    return bad != 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 2 && std::string(argv[1]) == "--corpus") { srand(1); return corpus_main(argv[2]); }
     const int cases = argc > 1 ? atoi(argv[1]) : 400;
     srand(argc > 2 ? atoi(argv[2]) : 1);
     Decoder *d = new Decoder;

@@ -2,8 +2,10 @@
 """Device BGZF inflate (HULK_INGEST_DEVICE_INFLATE) against the host readers: random FASTQ / FASTA texts cut into members of
 random sizes, each deflated with a random zlib level / strategy / flush points; ordinary gzip members mixed in; corruption of a
 payload bit, a CRC, an ISIZE, a BSIZE; truncation and trailing bytes.  Every case is sketched with and without the flag (same
-process, same parameters): stats, sketch, counters or error message must agree.
-usage: fuzz_bgzf_device.py [--cases N] [--seed S] [--dir D]   (last stdout line: a JSON summary)"""
+process, same parameters): stats, sketch, counters or error message must agree.  --crafted: the members are written by
+tests/deflate_craft.py instead of zlib — FASTQ built from tokens, small blocks with random code shapes (codes of up to 15 bits,
+lone and absent distance codes, 7-bit code-length codes), the shapes of other encoders; the corruptions stay the same.
+usage: fuzz_bgzf_device.py [--cases N] [--seed S] [--dir D] [--crafted]   (last stdout line: a JSON summary)"""
 import argparse, gzip, json, os, re, sys, tempfile, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -47,10 +49,21 @@ def text_of(rng):
     return t, t.startswith(b">")
 
 
-def container(rng, text):
-    out, at = [], 0
+def crafted(rng):
+    """(members, text) from the test encoder: a FASTQ of 1 KB - 400 KB in members of random sizes"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import deflate_craft
+    hi = int(rng.choice([2000, 20000, 65280]))
+    members, _, _ = deflate_craft.fastq_bgzf_members(int(rng.integers(0, 2 ** 31)), int(rng.choice([1000, 30000, 150000, 400000])), lo=300, hi=hi)
+    if rng.random() >= 0.8:
+        members.pop()                                                                        # (no end-of-file member)
+    return members
+
+
+def container(rng, text, members=None):
+    out, at = members or [], 0
     big = rng.random() < 0.5
-    while at < len(text):
+    while members is None and at < len(text):
         n = 65280 if big and rng.random() < 0.7 else int(rng.integers(1, 65281))
         piece = text[at:at + n]; at += n
         if rng.random() < 0.05:
@@ -60,7 +73,7 @@ def container(rng, text):
             if 12 + 6 + len(body) + 8 > 65536:                                                # (incompressible: stored)
                 c = zlib.compressobj(0, zlib.DEFLATED, -15); body = c.compress(piece) + c.flush()
             out.append(member(piece, body))
-    if rng.random() < 0.8:
+    if members is None and rng.random() < 0.8:
         out.append(member(b"", deflate(rng, b"")))
     data = bytearray(b"".join(out))
     kind = "clean"
@@ -100,14 +113,19 @@ def main():
     ap.add_argument("--cases", type=int, default=200)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dir", default=None)
+    ap.add_argument("--crafted", action="store_true")
     a = ap.parse_args()
     d = tempfile.mkdtemp(dir=a.dir)
     log = os.path.join(d, "trace.txt")
     rng = np.random.default_rng(a.seed)
     mismatches, members, kinds = 0, 0, {}
     for case in range(a.cases):
-        text, fasta = text_of(rng)
-        data, kind = container(rng, text)
+        if a.crafted:
+            fasta = False
+            data, kind = container(rng, None, crafted(rng))
+        else:
+            text, fasta = text_of(rng)
+            data, kind = container(rng, text)
         kinds[kind] = kinds.get(kind, 0) + 1
         p = os.path.join(d, "c%d.%s.gz" % (case, "fa" if fasta else "fq"))
         open(p, "wb").write(data)
@@ -126,7 +144,7 @@ def main():
             mismatches += 1
             print("MISMATCH case %d (%s, fasta=%s): host %r | device %r" % (case, kind, fasta, host[:5], dev[:5]), flush=True)
         os.remove(p)
-    print(json.dumps({"cases": a.cases, "mismatches": mismatches, "device_members": members, "kinds": kinds, "seed": a.seed}))
+    print(json.dumps({"cases": a.cases, "mismatches": mismatches, "device_members": members, "kinds": kinds, "seed": a.seed, "crafted": a.crafted}))
     return 1 if mismatches else 0
 
 
