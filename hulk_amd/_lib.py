@@ -37,7 +37,7 @@ HULK_CLUSTER_MAX_N = 2097088     # hulk_cluster: sketches in one set
 HULK_MINHASH_MAX_SKETCH = 4096
 HULK_MAX_BINS = 1 << 20
 HULK_INJECT_NONE, HULK_INJECT_STALE_SEAL, HULK_INJECT_STALE_STAGE = 0, 1, 2
-HULK_DEBUG_TILEMIN, HULK_DEBUG_SCANMAP = 1, 2
+HULK_DEBUG_TILEMIN, HULK_DEBUG_SCANMAP, HULK_DEBUG_NIBBLE = 1, 2, 3
 
 # every symbol include/hulk_hip.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = (

@@ -720,12 +720,22 @@ int hulk_debug_read(hulk_ctx *c, uint32_t what, void *out, uint64_t *bytes_io) {
     { int rcs = sync_all(c); if (rcs != HULK_OK) return rcs; }
     const size_t groups = (c->slots + SCAN_ROWS - 1) / SCAN_ROWS, wtiles = (size_t)c->ntiles * 4;
     const void *src = nullptr; size_t need = 0;
-    if (what == HULK_DEBUG_TILEMIN) { src = c->d_tilemin; need = groups * wtiles * SCAN_ROWS * sizeof(float); }
+    const hulk_ctx::BinLane *nib_lane = nullptr;                // HULK_DEBUG_NIBBLE: the lane of the latest short-read binning launch
+    if (what == HULK_DEBUG_NIBBLE) {                            // its geometry (host), then its flags (device)
+        if (c->last_fast_lane < 0 || !c->lane[c->last_fast_lane].ml.nib_over) return fail(c, HULK_ERR_STATE, "hulk_debug_read: no short-read binning launch yet");
+        nib_lane = &c->lane[c->last_fast_lane];
+        src = nib_lane->ml.nib_over; need = (size_t)(SPECTRUM_GEOM_WORDS + RING_MAX) * 4;
+    }
+    else if (what == HULK_DEBUG_TILEMIN) { src = c->d_tilemin; need = groups * wtiles * SCAN_ROWS * sizeof(float); }
     else if (what == HULK_DEBUG_SCANMAP) { src = c->d_scanmap; need = groups * ((wtiles + 63) / 64) * 8; }
     else return fail(c, HULK_ERR_ARG, "hulk_debug_read: what");
     const uint64_t cap = *bytes_io;
     *bytes_io = need;
     if (cap < need) return fail(c, HULK_ERR_ARG, "hulk_debug_read: buffer too small");
+    if (nib_lane) {
+        memcpy(out, nib_lane->geom, SPECTRUM_GEOM_WORDS * 4);
+        out = (uint32_t *)out + SPECTRUM_GEOM_WORDS; need = RING_MAX * 4;
+    }
     HIPCHK(c, hipMemcpyAsync(out, src, need, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HULK_OK;

@@ -119,7 +119,13 @@ struct hulk_ctx {
         hipStream_t stream = nullptr;                   // lane 1 only (lane 0 runs on the context's stream)
         hulk::MinimizerList ml{}; uint64_t ml_regions = 0;
         uint32_t *d_slow_list = nullptr, *d_slow_count = nullptr; uint64_t d_slow_cap = 0;
+#ifdef HULK_EXPERIMENTS
+        uint32_t geom[hulk::SPECTRUM_GEOM_WORDS] = {0, 0, 0, 0, 0};   // launch_minimizer_post's record of the lane's latest spectrum launch (all 0: it binned no reads)
+#endif
     } lane[2];
+#ifdef HULK_EXPERIMENTS
+    int last_fast_lane = -1;                            // the lane of the latest short-read binning launch (bin_fast)
+#endif
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;    // context stream -> lane 1 in front of a batch, and back (lanes_join)
     hipStream_t last_bin_stream = nullptr;              // the stream the latest binning launches went to
     hipEvent_t ev_heavy[2] = {nullptr, nullptr}; int heavy_idx = 0; bool heavy_set[2] = {false, false};   // experiment HULK_C3_GATE (profiling build)

@@ -281,7 +281,13 @@ static int bin_fast(hulk_ctx *c, hulk_ctx::BinLane &ln, hipStream_t s, const uin
     if ((c->profiling & 4)) {
         HIPCHK(c, hipEventCreateWithFlags(&pj.a, PROFILE_EVENT_FLAGS)); HIPCHK(c, hipEventCreateWithFlags(&pj.b, PROFILE_EVENT_FLAGS));
     }
-    HIPCHK(c, launch_minimizer_post(s, n, P, ln.ml, hist, ln.d_slow_list, ln.d_slow_count, pj.a, pj.b, spectra_gate));
+    uint32_t *geom = nullptr;                                   // (the shipping build records nothing: the argument stays null)
+#ifdef HULK_EXPERIMENTS
+    geom = ln.geom;
+    for (int i = 0; i < SPECTRUM_GEOM_WORDS; i++) geom[i] = 0;  // a launch without reads reports no geometry, not the previous one
+    c->last_fast_lane = (int)(&ln - c->lane);
+#endif
+    HIPCHK(c, launch_minimizer_post(s, n, P, ln.ml, hist, ln.d_slow_list, ln.d_slow_count, pj.a, pj.b, spectra_gate, geom));
     if ((c->profiling & 4)) c->prof.push_back(pj);
     int threads = 256;
     pick_config(c->p.k, max_len, P, threads);      // (the fast path implies max_len <= 512: always fits)

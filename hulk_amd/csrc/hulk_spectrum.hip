@@ -506,7 +506,7 @@ __global__ void k_add_hist(uint32_t *hist, const uint32_t *add, int32_t n) {
 // K1b: jump hash of the list (dense key array); K1c: spectrum ranges in LDS, merged without atomics
 hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParams P, const MinimizerList &ml,
                                  uint32_t *d_hists, uint32_t *d_slow_list, uint32_t *d_slow_count, hipEvent_t jump_begin,
-                                 hipEvent_t jump_end, hipEvent_t wait_before_spectra) {
+                                 hipEvent_t jump_end, hipEvent_t wait_before_spectra, uint32_t *geom) {
     if (n_reads == 0) return hipSuccess;
     hipError_t e = hipSuccess;
     const uint32_t n_regions = (uint32_t)((n_reads + FAST_READS_PER_WAVE - 1) / FAST_READS_PER_WAVE);
@@ -591,6 +591,9 @@ hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParam
             nib_attr = true;
         }
         const unsigned pg = (n_spectra * np + 7) / 8;
+#ifdef HULK_EXPERIMENTS
+        if (geom) { geom[0] = n_spectra; geom[1] = np; geom[2] = (uint32_t)nr; geom[3] = (uint32_t)rlog; geom[4] = (uint32_t)nib_block; }
+#endif
         prof_mark(s, "k_nibble_hist");
         hipLaunchKernelGGL(k_nibble_hist, dim3(8u * (unsigned)nr * pg), dim3(nib_block), (size_t)words * 4, s, ml, n_regions, P,
                            n_spectra, np, n_reads, nr, rlog);
@@ -607,6 +610,9 @@ hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParam
         return hipGetLastError();
     }
     const unsigned pair_groups = (n_spectra * n_parts + 7) / 8;
+#ifdef HULK_EXPERIMENTS
+    if (geom) { geom[0] = n_spectra; geom[1] = n_parts; geom[2] = (uint32_t)nranges; geom[3] = 15u /* log2 HIST_RANGE */; geom[4] = 1024u; }
+#endif
     prof_mark(s, "k_range_hist");
     hipLaunchKernelGGL(k_range_hist, dim3(8u * (unsigned)nranges * pair_groups), dim3(1024), HIST_RANGE * 4, s, ml, n_regions,
                        ml.partial, P, n_spectra, n_parts, n_reads, nranges, nullptr, nullptr);

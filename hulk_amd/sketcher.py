@@ -335,14 +335,15 @@ class GpuSketcher:
             raise RuntimeError("test hook of the profiling build: run with HULK_LIB=exp (make -C hulk_amd/csrc EXPERIMENTS=1)")
 
     def debug_read(self, what: int):
-        """Test hook (hulk_debug_read): HULK_DEBUG_TILEMIN -> float32 array, HULK_DEBUG_SCANMAP -> uint64 array."""
+        """Test hook (hulk_debug_read): HULK_DEBUG_TILEMIN -> float32 array, HULK_DEBUG_SCANMAP -> uint64 array,
+        HULK_DEBUG_NIBBLE -> uint32 array (n_spectra, parts, ranges, log2 range bins, block threads, then the 17 overflow flags)."""
         self._need_experiments()
         n = ctypes.c_uint64(0)
         buf = np.zeros(1, dtype=np.uint8)
         self._L.hulk_debug_read(self._ctx, what, buf.ctypes.data, ctypes.byref(n))       # (too small: reports the size)
         buf = np.zeros(n.value, dtype=np.uint8)
         self._chk(self._L.hulk_debug_read(self._ctx, what, buf.ctypes.data, ctypes.byref(n)))
-        return buf.view(np.float32 if what == _lib.HULK_DEBUG_TILEMIN else np.uint64)
+        return buf.view({_lib.HULK_DEBUG_TILEMIN: np.float32, _lib.HULK_DEBUG_NIBBLE: np.uint32}.get(what, np.uint64))
 
     def debug_inject(self, what: int, step: int):
         """Test hook (hulk_debug_inject): make this rank's header block of `step` void / its host staging late."""

@@ -382,9 +382,14 @@ int hulk_debug_inject(hulk_ctx *ctx, uint32_t what, uint64_t step);
 /* Test hook: internal buffers of the CWS scan as the latest flush left them (after a synchronisation).
  *   HULK_DEBUG_TILEMIN  float[slot groups][wave tiles][8]: the fp32 tile minima of the batch (no concept drift: plane 0)
  *   HULK_DEBUG_SCANMAP  uint64[slot groups][(wave tiles + 63) / 64]: which tiles the scan read
+ *   HULK_DEBUG_NIBBLE   uint32[5 + 17]: the latest short-read binning launch as its work lane holds it (HULK_ERR_STATE before the
+ *                       first one; five zeros if that launch binned no reads): spectra of the launch,
+ *                       parts per spectrum, bin ranges, log2 of a range's bins, threads of a histogram workgroup (the 4-bit
+ *                       kernels, or the exact ones when those ran), then nib_over[17]: which spectra's 4-bit counters overflowed
  * *bytes_io: capacity of `out` in, bytes written out (HULK_ERR_ARG if too small; the size needed is returned in it). */
 #define HULK_DEBUG_TILEMIN 1u
 #define HULK_DEBUG_SCANMAP 2u
+#define HULK_DEBUG_NIBBLE 3u
 int hulk_debug_read(hulk_ctx *ctx, uint32_t what, void *out, uint64_t *bytes_io);
 #endif /* HULK_EXPERIMENTS */
 
