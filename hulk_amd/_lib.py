@@ -29,6 +29,7 @@ HULK_FLAG_GAMMA_CPYTHON, HULK_FLAG_NO_PRUNE, HULK_FLAG_NO_SKIP, HULK_FLAG_SHARD_
 HULK_FLAG_KMV, HULK_FLAG_KHF = 128, 256     # feed the bottom-k / k-hash-functions MinHash sketches (hulk_get_minhash)
 HULK_MINHASH_KMV, HULK_MINHASH_KHF = 0, 1
 HULK_METRIC_JACCARD, HULK_METRIC_WEIGHTED_JACCARD = 0, 1
+HULK_METRIC_BOTTOMK = 3         # KMV sketches: the multiset intersection of KMVsketch.GetSimilarity (2 is no metric)
 HULK_PANEL_ROW, HULK_PANEL_COLUMN = 0, 1    # hulk_set_panel: the snapshot is the subject (its row of the smash matrix) / the panel sketch is
 HULK_PANEL_MAX = 65536
 HULK_SEARCH_MAX_K = 64          # hulk_search: hits per query

@@ -652,8 +652,10 @@ SmashBuffers g_smash;
 
 int hulk_smash_ex(int device, const uint64_t *mins, const double *weights, uint32_t n_sketches, uint32_t sketch_size,
                   int metric, double *distances, double *kernel_ms) {
-    if (!mins || !weights || !distances) return fail(nullptr, HULK_ERR_ARG, "NULL");
-    if (!metric_ok(metric)) return fail(nullptr, HULK_ERR_ARG, "metric");
+    const bool bottomk = metric == HULK_METRIC_BOTTOMK;             // (reads no weights: they may be NULL)
+    if (!mins || (!weights && !bottomk) || !distances) return fail(nullptr, HULK_ERR_ARG, "NULL");
+    if (!pair_metric_ok(metric)) return fail(nullptr, HULK_ERR_ARG, "metric");
+    if (!bottomk_size_ok(metric, sketch_size)) return fail(nullptr, HULK_ERR_ARG, "hulk_smash: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
     if (const int rc = oneshot_device(device)) return rc;
     std::lock_guard<std::mutex> lock(g_smash.mu);
     SmashBuffers &B = g_smash;
@@ -680,9 +682,11 @@ int hulk_smash_ex(int device, const uint64_t *mins, const double *weights, uint3
     }
     if (!B.ea) { SM_CHK(hipEventCreate(&B.ea)); SM_CHK(hipEventCreate(&B.eb)); }
     SM_CHK(hipMemcpy(B.d_m, mins, NS * 8, hipMemcpyHostToDevice));
-    SM_CHK(hipMemcpy(B.d_w, weights, NS * 8, hipMemcpyHostToDevice));
+    if (!bottomk) SM_CHK(hipMemcpy(B.d_w, weights, NS * 8, hipMemcpyHostToDevice));
     if (kernel_ms) SM_CHK(hipEventRecord(B.ea, nullptr));
-    SM_CHK(launch_smash(nullptr, B.d_m, B.d_w, n_sketches, sketch_size, metric, B.d_o, B.d_mT, B.d_wT));
+    // (bottomk: d_mT / d_wT hold the sorted run-length form, hulk_bottomk_tile.h; kernel_ms covers its preparation as it does k_smash_prep)
+    if (bottomk) SM_CHK(launch_bottomk_smash(nullptr, B.d_m, n_sketches, sketch_size, B.d_o, B.d_mT, B.d_wT));
+    else SM_CHK(launch_smash(nullptr, B.d_m, B.d_w, n_sketches, sketch_size, metric, B.d_o, B.d_mT, B.d_wT));
     if (kernel_ms) SM_CHK(hipEventRecord(B.eb, nullptr));
     SM_CHK(hipMemcpy(distances, B.d_o, NN * 8, hipMemcpyDeviceToHost));
     if (kernel_ms) { float ms = 0; SM_CHK(hipEventElapsedTime(&ms, B.ea, B.eb)); *kernel_ms = ms; }

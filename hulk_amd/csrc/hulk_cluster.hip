@@ -26,6 +26,7 @@
 // What the labels need to be exact is the kernel boundary between the last k_cluster_link and the last k_cluster_flatten.
 #include "hulk_oneshot.h"
 #include "hulk_pairtile.h"
+#include "hulk_bottomk_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -46,10 +47,10 @@ static_assert(CLUSTER_MAX_N % 64 == 0 && CLUSTER_MAX_N / 32 <= 65535, "k_smash_p
 // mT / wT: the prepared set [S][NP].  Subjects b0 + 32 * blockIdx.y .. (below N), others 64 * (qt0 + blockIdx.x) .. (below N).
 // filter: skip a pair whose two parents are equal already (plain loads; it pays where links are dense: DESIGN 4e).
 // links: the ordered pairs s != q with d(s, q) <= tau
-template <int METRIC>
-__global__ __launch_bounds__(128) void k_cluster_link(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t N,
-                                                      uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t filter,
-                                                      uint32_t *parent, unsigned long long *links, uint32_t *err) {
+// cluster_link_tile is the kernel's text around the tile: tile(s0, q0, acc, uni, cnt) fills the sums of the tile at rows s0, columns q0
+template <int METRIC, class TILE>
+__device__ __forceinline__ void cluster_link_tile(uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t filter,
+                                                  uint32_t *parent, unsigned long long *links, uint32_t *err, TILE tile) {
     const uint32_t s0 = b0 + blockIdx.y * PAIR_TS, q0 = (qt0 + blockIdx.x) * PAIR_TQ;
     if (METRIC == 0 && s0 >= q0 + PAIR_TQ - 1) return;              // jaccard: every pair of the tile has s >= q (the whole workgroup leaves)
     __shared__ uint32_t wg_links;
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(128) void k_cluster_link(const double *__restrict__
     if (tid == 0) wg_links = 0;                                     // (ordered before its use by the tile's barriers)
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
+    tile(s0, q0, acc, uni, cnt);
     // the epilogue.  First the 16 compares into one word — the accumulators are dead behind it, the unions run on a handful of registers
     uint32_t mask = 0;
 #pragma unroll
@@ -86,6 +87,25 @@ __global__ __launch_bounds__(128) void k_cluster_link(const double *__restrict__
     if (tid == 0 && wg_links) atomicAdd(links, (unsigned long long)wg_links);
 }
 
+template <int METRIC>
+__global__ __launch_bounds__(128) void k_cluster_link(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t N,
+                                                      uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t filter,
+                                                      uint32_t *parent, unsigned long long *links, uint32_t *err) {
+    cluster_link_tile<METRIC>(N, b0, qt0, S, tau, filter, parent, links, err,
+                              [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
+        pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
+    });
+}
+
+// HULK_METRIC_BOTTOMK: the same text over bottomk_tile's count (hulk_bottomk_tile.h), symmetric as jaccard is — the triangle, a link counts twice
+__global__ __launch_bounds__(128) void k_cluster_link_bottomk(const BottomkSet set, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau,
+                                                              uint32_t filter, uint32_t *parent, unsigned long long *links, uint32_t *err) {
+    cluster_link_tile<0>(N, b0, qt0, S, tau, filter, parent, links, err,
+                         [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
+        bottomk_tile(set, s0, set, q0, S, cnt);
+    });
+}
+
 // parent[i] = root(i).  No hook runs beside this kernel, so the roots stand still and every store writes the value the node ends with
 __global__ __launch_bounds__(256) void k_cluster_flatten(uint32_t *parent, uint32_t N, uint32_t *err) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -108,10 +128,13 @@ using namespace hulk;
 extern "C" int hulk_cluster(int device, const uint64_t *mins, const double *weights, uint32_t n, uint32_t sketch_size,
                             const hulk_cluster_opts *opts, uint32_t *label, hulk_cluster_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
-    if (!mins || !weights || !opts || !label) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: NULL");
+    // (HULK_METRIC_BOTTOMK reads no weights: they may be NULL)
+    const bool bottomk = opts && opts->metric == HULK_METRIC_BOTTOMK;
+    if (!mins || (!weights && !bottomk) || !opts || !label) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: NULL");
     if (n == 0 || sketch_size == 0) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: n and sketch_size must be positive");
     if (n > CLUSTER_MAX_N) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: n must be at most " + std::to_string(CLUSTER_MAX_N));
-    if (!metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: metric");
+    if (!pair_metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: metric");
+    if (!bottomk_size_ok(opts->metric, sketch_size)) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
     if (!(opts->max_distance >= 0.0 && opts->max_distance <= 1.0)) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: max_distance must be in [0, 1]");
     if (opts->band_rows % 32) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: band_rows must be a multiple of 32");
     if (opts->flags) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: unknown flags");
@@ -131,7 +154,9 @@ extern "C" int hulk_cluster(int device, const uint64_t *mins, const double *weig
     ONESHOT_CHK(own.alloc(&d_mT, NT)); ONESHOT_CHK(own.alloc(&d_wT, NT));
     ONESHOT_CHK(own.alloc(&d_raw_m, NS)); ONESHOT_CHK(own.alloc(&d_raw_w, NS));
     ONESHOT_CHK(own.alloc(&d_parent, N)); ONESHOT_CHK(own.alloc(&d_links, 1)); ONESHOT_CHK(own.alloc(&d_err, 1));
-    ONESHOT_CHK(upload_prepared(nullptr, mins, weights, N, S, d_raw_m, d_raw_w, d_mT, d_wT));
+    // bottomk: the same buffers hold the sorted run-length form (bottomk_view)
+    if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, mins, N, S, d_raw_m, d_mT, d_wT));
+    else ONESHOT_CHK(upload_prepared(nullptr, mins, weights, N, S, d_raw_m, d_raw_w, d_mT, d_wT));
     ONESHOT_CHK(hipDeviceSynchronize());
     ONESHOT_CHK(own.release(d_raw_m));                              // (the peak of device memory: the header comment)
     ONESHOT_CHK(own.release(d_raw_w));
@@ -158,7 +183,9 @@ extern "C" int hulk_cluster(int device, const uint64_t *mins, const double *weig
         const dim3 g(NP / PAIR_TQ - qt0, (rows + PAIR_TS - 1) / PAIR_TS);
         const bool last = b0 + band >= N;
         ONESHOT_CHK(mark());
-        if (metric == HULK_METRIC_WEIGHTED_JACCARD)
+        if (bottomk)
+            hipLaunchKernelGGL(k_cluster_link_bottomk, g, dim3(128), 0, nullptr, bottomk_view(d_mT, d_wT, NP, S), N, (uint32_t)b0, qt0, S, tau, filter, d_parent, d_links, d_err);
+        else if (metric == HULK_METRIC_WEIGHTED_JACCARD)
             hipLaunchKernelGGL(k_cluster_link<1>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, filter, d_parent, d_links, d_err);
         else
             hipLaunchKernelGGL(k_cluster_link<0>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, filter, d_parent, d_links, d_err);

@@ -199,6 +199,9 @@ int fail_hip(hulk_ctx *c, hipError_t e, const char *what);
 template <typename T> hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, n ? n * sizeof(T) : sizeof(T)); }
 // the two metrics and the two roles of the pairwise entry points (hulk_smash, the panel, hulk_search, hulk_cluster)
 inline bool metric_ok(int metric) { return metric == HULK_METRIC_JACCARD || metric == HULK_METRIC_WEIGHTED_JACCARD; }
+// ... and what the pairwise entry points take (hulk_smash, hulk_search, hulk_cluster, hulk_dendrogram; the panels score histosketches)
+inline bool pair_metric_ok(int metric) { return metric_ok(metric) || metric == HULK_METRIC_BOTTOMK; }
+inline bool bottomk_size_ok(int metric, uint32_t sketch_size) { return metric != HULK_METRIC_BOTTOMK || sketch_size <= HULK_MINHASH_MAX_SKETCH; }
 inline bool role_ok(int role) { return role == HULK_PANEL_ROW || role == HULK_PANEL_COLUMN; }
 
 // ---- hulk_tables.hip

@@ -27,6 +27,7 @@
 // The output does not depend on bands, launch shape or the number of rounds: every minimum is over a total order.
 #include "hulk_oneshot.h"
 #include "hulk_pairtile.h"
+#include "hulk_bottomk_tile.h"
 #include "hulk_boruvka.h"
 
 #include <algorithm>
@@ -49,11 +50,11 @@ __device__ __forceinline__ void offer_min(uint64_t &d, uint32_t &p, uint64_t od,
 
 // mT / wT: the prepared set [S][NP].  Subjects b0 + 32 * blockIdx.y .., others 64 * (qt0 + blockIdx.x) ..; CT = NP / 64, RT = the
 // pitch of the column scratch (the band's planned row tiles).  Every launched workgroup writes its 32 row and 64 column entries
-template <int METRIC>
-__global__ __launch_bounds__(128) void k_dendro_offer(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t N,
-                                                      uint32_t b0, uint32_t qt0, uint32_t S, const uint32_t *__restrict__ comp, uint32_t RT,
-                                                      uint64_t *__restrict__ row_d, uint32_t *__restrict__ row_p,
-                                                      uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p) {
+// dendro_offer_tile is the kernel's text around the tile: tile(s0, q0, acc, uni, cnt) fills the sums of the tile at rows s0, columns q0
+template <int METRIC, class TILE>
+__device__ __forceinline__ void dendro_offer_tile(uint32_t NP, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, const uint32_t *__restrict__ comp,
+                                                  uint32_t RT, uint64_t *__restrict__ row_d, uint32_t *__restrict__ row_p,
+                                                  uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p, TILE tile) {
     const uint32_t ct = qt0 + blockIdx.x, CT = NP / PAIR_TQ;
     const uint32_t s0 = b0 + blockIdx.y * PAIR_TS, q0 = ct * PAIR_TQ;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;     // other quad, subject quad inside the tile
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(128) void k_dendro_offer(const double *__restrict__
     __shared__ uint32_t x_p[PAIR_TQ];
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
+    tile(s0, q0, acc, uni, cnt);
     // the epilogue: the accumulators die pair by pair into 4 row and 4 column minima
     uint32_t cs[4], cq[4];
 #pragma unroll
@@ -139,6 +140,27 @@ __global__ __launch_bounds__(128) void k_dendro_offer(const double *__restrict__
     }
 }
 
+template <int METRIC>
+__global__ __launch_bounds__(128) void k_dendro_offer(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t N,
+                                                      uint32_t b0, uint32_t qt0, uint32_t S, const uint32_t *__restrict__ comp, uint32_t RT,
+                                                      uint64_t *__restrict__ row_d, uint32_t *__restrict__ row_p,
+                                                      uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p) {
+    dendro_offer_tile<METRIC>(NP, N, b0, qt0, S, comp, RT, row_d, row_p, col_d, col_p,
+                              [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
+        pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
+    });
+}
+
+// HULK_METRIC_BOTTOMK: the same text over bottomk_tile's count (hulk_bottomk_tile.h), symmetric as jaccard is — the tiles on and above the diagonal
+__global__ __launch_bounds__(128) void k_dendro_offer_bottomk(const BottomkSet set, uint32_t NP, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S,
+                                                              const uint32_t *__restrict__ comp, uint32_t RT, uint64_t *__restrict__ row_d,
+                                                              uint32_t *__restrict__ row_p, uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p) {
+    dendro_offer_tile<0>(NP, N, b0, qt0, S, comp, RT, row_d, row_p, col_d, col_p,
+                         [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
+        bottomk_tile(set, s0, set, q0, S, cnt);
+    });
+}
+
 // one wave a sketch: best[i] = min(best[i] (fresh: no offer), the band's row partials of i (if the band holds row i: the column tiles
 // from qt0 on), its column partials (if i's column tile was launched: the rt row tiles of this band))
 __global__ __launch_bounds__(256) void k_dendro_fold(uint32_t N, uint32_t NP, uint32_t b0, uint32_t rows, uint32_t qt0, uint32_t RT, uint32_t rt,
@@ -171,10 +193,13 @@ extern "C" int hulk_dendrogram(int device, const uint64_t *mins, const double *w
                                uint32_t *n_edges, hulk_dendrogram_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_edges) *n_edges = 0;
-    if (!mins || !weights || !opts || !edge_a || !edge_b || !edge_distance || !n_edges) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: NULL");
+    // (HULK_METRIC_BOTTOMK reads no weights: they may be NULL)
+    const bool bottomk = opts && opts->metric == HULK_METRIC_BOTTOMK;
+    if (!mins || (!weights && !bottomk) || !opts || !edge_a || !edge_b || !edge_distance || !n_edges) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: NULL");
     if (n == 0 || sketch_size == 0) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: n and sketch_size must be positive");
     if (n > DENDRO_MAX_N) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: n must be at most " + std::to_string(DENDRO_MAX_N));
-    if (!metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: metric");
+    if (!pair_metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: metric");
+    if (!bottomk_size_ok(opts->metric, sketch_size)) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
     if (opts->band_rows % 32) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: band_rows must be a multiple of 32");
     if (opts->flags) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: unknown flags");
     for (uint64_t x : opts->reserved) if (x) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: reserved fields must be zero");
@@ -199,7 +224,9 @@ extern "C" int hulk_dendrogram(int device, const uint64_t *mins, const double *w
         uint64_t *d_row_d = nullptr, *d_col_d = nullptr, *d_best_d = nullptr;
         ONESHOT_CHK(own.alloc(&d_mT, NT)); ONESHOT_CHK(own.alloc(&d_wT, NT));
         ONESHOT_CHK(own.alloc(&d_raw_m, NS)); ONESHOT_CHK(own.alloc(&d_raw_w, NS));
-        ONESHOT_CHK(upload_prepared(nullptr, mins, weights, N, S, d_raw_m, d_raw_w, d_mT, d_wT));
+        // bottomk: the same buffers hold the sorted run-length form (bottomk_view)
+        if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, mins, N, S, d_raw_m, d_mT, d_wT));
+        else ONESHOT_CHK(upload_prepared(nullptr, mins, weights, N, S, d_raw_m, d_raw_w, d_mT, d_wT));
         ONESHOT_CHK(hipDeviceSynchronize());
         ONESHOT_CHK(own.release(d_raw_m));                          // (the peak of device memory: the header comment)
         ONESHOT_CHK(own.release(d_raw_w));
@@ -223,7 +250,9 @@ extern "C" int hulk_dendrogram(int device, const uint64_t *mins, const double *w
                 const uint32_t qt0 = metric == HULK_METRIC_WEIGHTED_JACCARD ? 0u : (uint32_t)b0 / PAIR_TQ;
                 const dim3 g(CT - qt0, rt);
                 ONESHOT_CHK(hipEventRecord(ev[3 * b], nullptr));
-                if (metric == HULK_METRIC_WEIGHTED_JACCARD)
+                if (bottomk)
+                    hipLaunchKernelGGL(k_dendro_offer_bottomk, g, dim3(128), 0, nullptr, bottomk_view(d_mT, d_wT, NP, S), NP, N, (uint32_t)b0, qt0, S, d_comp, RT, d_row_d, d_row_p, d_col_d, d_col_p);
+                else if (metric == HULK_METRIC_WEIGHTED_JACCARD)
                     hipLaunchKernelGGL(k_dendro_offer<1>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, d_comp, RT, d_row_d, d_row_p, d_col_d, d_col_p);
                 else
                     hipLaunchKernelGGL(k_dendro_offer<0>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, d_comp, RT, d_row_d, d_row_p, d_col_d, d_col_p);

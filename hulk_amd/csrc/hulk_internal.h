@@ -198,6 +198,11 @@ hipError_t launch_cws_beta(hipStream_t s, const uint64_t *d_uraw, uint64_t first
 hipError_t launch_smash(hipStream_t s, const unsigned long long *d_mins, const double *d_weights, uint32_t N, uint32_t S,
                         int metric, double *d_out, double *d_mT, double *d_wT);     // d_mT, d_wT: scratch [S][smash_padded_n(N)]
 uint32_t smash_padded_n(uint32_t N);
+// HULK_METRIC_BOTTOMK (hulk_bottomk.hip): d_mins [N][S], S <= HULK_MINHASH_MAX_SKETCH, sorted and run-length coded on the device into
+// the two buffers of smash_padded_n(N) * S doubles the other metrics keep their slot-major arrays in (bottomk_view, hulk_bottomk_tile.h)
+hipError_t launch_bottomk_prep(hipStream_t s, const unsigned long long *d_mins, uint32_t N, uint32_t S, double *d_mT, double *d_wT);
+hipError_t launch_bottomk_smash(hipStream_t s, const unsigned long long *d_mins, uint32_t N, uint32_t S, double *d_out, double *d_mT,
+                                double *d_wT);
 // hulk_set_panel / hulk_panel_distances (k_snap_panel): the panel slot-major as k_smash_prep lays it out, d_pmT / d_pwT
 // [S][smash_padded_n(P)]; the snapshots in entries (base + m) % cap, m < M <= SCAN_BATCH_MAX, of the ring [cap][S] -> the same
 // entries of d_out [cap][P].  role 0: the snapshot is the subject, 1: the panel sketch is

@@ -46,4 +46,13 @@ inline hipError_t upload_prepared(hipStream_t s, const uint64_t *mins, const dou
     return e;
 }
 
+// the same for HULK_METRIC_BOTTOMK: n host sketches [n][S] -> d_raw_m -> k_bottomk_prep -> the sorted run-length form in d_mT / d_wT
+// (bottomk_view, hulk_bottomk_tile.h, over smash_padded_n(n) rows).  No weights
+inline hipError_t upload_bottomk(hipStream_t s, const uint64_t *mins, uint32_t n, uint32_t S, unsigned long long *d_raw_m, double *d_mT,
+                                 double *d_wT) {
+    hipError_t e = hipMemcpy(d_raw_m, mins, (size_t)n * S * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_bottomk_prep(s, d_raw_m, n, S, d_mT, d_wT);
+    return e;
+}
+
 }  // namespace hulk

@@ -18,6 +18,7 @@
 //                   set of pairs alone: no atomics, no appends, no dependence on strips, blocks or scheduling
 #include "hulk_oneshot.h"
 #include "hulk_pairtile.h"
+#include "hulk_bottomk_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,15 +31,14 @@ constexpr int SELECT_AHEAD = 8;
 // a: the subject side, slot-major [S][AP], columns a0 .. a0 + na of it; b: the other side [S][BP], columns b0 .. b0 + nb.
 // out[q][p], pitch doubles per query row: COLUMN 0 the subjects are the queries (q = a, p = b), COLUMN 1 the others are.
 // Columns behind na / nb inside a tile are read (the arrays are padded: see hulk_search) and never written.
-template <int METRIC, int COLUMN>
-__global__ __launch_bounds__(128) void k_search_dist(const double *__restrict__ aT, const double *__restrict__ awT, uint32_t AP, uint32_t a0,
-                                                     uint32_t na, const double *__restrict__ bT, uint32_t BP, uint32_t b0, uint32_t nb,
-                                                     uint32_t S, double *__restrict__ out, uint32_t pitch) {
+// search_dist_tile is the kernel's text around the tile: tile(s0, q0, acc, uni, cnt) fills the sums of the workgroup's tile at (s0, q0)
+template <int METRIC, int COLUMN, class TILE>
+__device__ __forceinline__ void search_dist_tile(uint32_t na, uint32_t nb, uint32_t S, double *__restrict__ out, uint32_t pitch, TILE tile) {
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;     // other quad, subject quad inside the tile
     const uint32_t s0 = blockIdx.y * PAIR_TS, q0 = blockIdx.x * PAIR_TQ;        // tile origin, relative to a0 / b0
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    pair_tile<METRIC>(aT, awT, AP, a0 + s0, bT, BP, b0 + q0, S, acc, uni, cnt);
+    tile(s0, q0, acc, uni, cnt);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t s = s0 + 4 * ty + i;
@@ -48,6 +48,24 @@ __global__ __launch_bounds__(128) void k_search_dist(const double *__restrict__ 
             if (s < na && q < nb) out[COLUMN ? (size_t)q * pitch + s : (size_t)s * pitch + q] = pair_distance<METRIC>(acc[i][j], uni[i], cnt[i][j], S);
         }
     }
+}
+
+template <int METRIC, int COLUMN>
+__global__ __launch_bounds__(128) void k_search_dist(const double *__restrict__ aT, const double *__restrict__ awT, uint32_t AP, uint32_t a0,
+                                                     uint32_t na, const double *__restrict__ bT, uint32_t BP, uint32_t b0, uint32_t nb,
+                                                     uint32_t S, double *__restrict__ out, uint32_t pitch) {
+    search_dist_tile<METRIC, COLUMN>(na, nb, S, out, pitch, [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
+        pair_tile<METRIC>(aT, awT, AP, a0 + s0, bT, BP, b0 + q0, S, acc, uni, cnt);
+    });
+}
+
+// HULK_METRIC_BOTTOMK: the same text over bottomk_tile's count (hulk_bottomk_tile.h) — rows a0 .. a0 + na of the prepared queries
+// against rows b0 .. b0 + nb of the prepared strip; symmetric, so the queries are always the rows of `out`
+__global__ __launch_bounds__(128) void k_search_dist_bottomk(const BottomkSet a, uint32_t a0, uint32_t na, const BottomkSet b, uint32_t b0,
+                                                             uint32_t nb, uint32_t S, double *__restrict__ out, uint32_t pitch) {
+    search_dist_tile<0, 0>(na, nb, S, out, pitch, [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
+        bottomk_tile(a, a0 + s0, b, b0 + q0, S, cnt);
+    });
 }
 
 // dist [mq][pitch]: row r = query qbase + r against database sketches pbase .. pbase + np.  lkey / lidx [M][K]: the running lists,
@@ -133,19 +151,22 @@ extern "C" int hulk_search(int device, const uint64_t *q_mins, const double *q_w
                            const double *db_weights, uint32_t n_db, uint32_t sketch_size, const hulk_search_opts *opts,
                            uint32_t *hit_index, double *hit_distance, uint32_t *hit_count, hulk_search_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
-    if (!q_mins || !q_weights || !opts || !hit_index || !hit_distance || !hit_count) return fail(nullptr, HULK_ERR_ARG, "hulk_search: NULL");
+    // (HULK_METRIC_BOTTOMK reads no weights: they may be NULL)
+    const bool bottomk = opts && opts->metric == HULK_METRIC_BOTTOMK;
+    if (!q_mins || (!q_weights && !bottomk) || !opts || !hit_index || !hit_distance || !hit_count) return fail(nullptr, HULK_ERR_ARG, "hulk_search: NULL");
     const uint32_t K = opts->k;
     if (K == 0 || K > HULK_SEARCH_MAX_K) return fail(nullptr, HULK_ERR_ARG, "hulk_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
-    if (!metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: metric");
+    if (!pair_metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: metric");
     if (!role_ok(opts->role)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: role");
     if (opts->flags & ~HULK_SEARCH_SELF) return fail(nullptr, HULK_ERR_ARG, "hulk_search: unknown flags");
     for (uint64_t x : opts->reserved) if (x) return fail(nullptr, HULK_ERR_ARG, "hulk_search: reserved fields must be zero");
     const bool self = (opts->flags & HULK_SEARCH_SELF) != 0;
     if (self && (db_mins || db_weights)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: HULK_SEARCH_SELF takes no database");
-    if (!self && (!db_mins || !db_weights)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: no database (and no HULK_SEARCH_SELF)");
+    if (!self && (!db_mins || (!db_weights && !bottomk))) return fail(nullptr, HULK_ERR_ARG, "hulk_search: no database (and no HULK_SEARCH_SELF)");
     if (self) { db_mins = q_mins; db_weights = q_weights; n_db = m; }
     if (m == 0 || n_db == 0 || sketch_size == 0) return fail(nullptr, HULK_ERR_ARG, "hulk_search: m, n_db and sketch_size must be positive");
     const uint32_t S = sketch_size;
+    if (!bottomk_size_ok(opts->metric, S)) return fail(nullptr, HULK_ERR_ARG, "hulk_search: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
     uint32_t Mb = 0, Pb = 0;
     if (!search_plan(m, n_db, S, opts->scratch_bytes, &Mb, &Pb))
         return fail(nullptr, HULK_ERR_ARG, "hulk_search: scratch_bytes " + std::to_string(opts->scratch_bytes) + " is too small for one tile (" +
@@ -172,19 +193,25 @@ extern "C" int hulk_search(int device, const uint64_t *q_mins, const double *q_w
     ONESHOT_CHK(own.alloc(&d_lkey, LK)); ONESHOT_CHK(own.alloc(&d_lidx, LK));
     ONESHOT_CHK(hipMemset(d_lkey, 0xff, LK * 8)); ONESHOT_CHK(hipMemset(d_lidx, 0xff, LK * 4));
     ONESHOT_CHK(hipMemset(d_qmT + (size_t)QP * S, 0, 64 * 8)); ONESHOT_CHK(hipMemset(d_qwT + (size_t)QP * S, 0, 64 * 8));
-    ONESHOT_CHK(upload_prepared(nullptr, q_mins, q_weights, m, S, d_raw_m, d_raw_w, d_qmT, d_qwT));
+    // bottomk: the same buffers hold the sorted run-length form (bottomk_view), the strips' too
+    if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, q_mins, m, S, d_raw_m, d_qmT, d_qwT));
+    else ONESHOT_CHK(upload_prepared(nullptr, q_mins, q_weights, m, S, d_raw_m, d_raw_w, d_qmT, d_qwT));
     double ms_dist = 0.0, ms_select = 0.0;
     uint32_t strips = 0, blocks = 0;
     for (uint64_t p0 = 0; p0 < n_db; p0 += Pb, strips++) {
         const uint32_t np = (uint32_t)std::min<uint64_t>(Pb, n_db - p0);
         // (hipMemcpy on the null stream: behind the kernels that read the previous strip)
-        ONESHOT_CHK(upload_prepared(nullptr, db_mins + (size_t)p0 * S, db_weights + (size_t)p0 * S, np, S, d_raw_m, d_raw_w, d_dmT, d_dwT));
+        if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, db_mins + (size_t)p0 * S, np, S, d_raw_m, d_dmT, d_dwT));
+        else ONESHOT_CHK(upload_prepared(nullptr, db_mins + (size_t)p0 * S, db_weights + (size_t)p0 * S, np, S, d_raw_m, d_raw_w, d_dmT, d_dwT));
         const uint32_t NP = smash_padded_n(np);                     // the pitch k_smash_prep gave this strip
         blocks = 0;
         for (uint32_t qb = 0; qb < m; qb += Mb, blocks++) {
             const uint32_t mq = std::min(Mb, m - qb);
             ONESHOT_CHK(hipEventRecord(ev[0], nullptr));
-            if (metric != HULK_METRIC_WEIGHTED_JACCARD) search_dist<0, 0>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
+            if (bottomk)
+                hipLaunchKernelGGL(k_search_dist_bottomk, dim3((np + PAIR_TQ - 1) / PAIR_TQ, (mq + PAIR_TS - 1) / PAIR_TS), dim3(128), 0, nullptr,
+                                   bottomk_view(d_qmT, d_qwT, QP, S), qb, mq, bottomk_view(d_dmT, d_dwT, NP, S), 0u, np, S, d_dist, Pb);
+            else if (metric != HULK_METRIC_WEIGHTED_JACCARD) search_dist<0, 0>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
             else if (column) search_dist<1, 1>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
             else search_dist<1, 0>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
             ONESHOT_CHK(hipGetLastError());

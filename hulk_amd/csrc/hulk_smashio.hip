@@ -586,6 +586,10 @@ const double *hulk_sketch_set_weights(const hulk_sketch_set *set) { return set ?
 const char *hulk_sketch_set_path(const hulk_sketch_set *set, uint32_t i) { return (set && i < set->files.size()) ? set->files[i].path.c_str() : nullptr; }
 const char *hulk_sketch_set_banner(const hulk_sketch_set *set, uint32_t i) { return (set && i < set->files.size()) ? set->files[i].banner.c_str() : nullptr; }
 
+// the metrics of the *_files entry points (cmd/smash.go:30 and this library's bottomk) and their HULK_METRIC_ values
+static bool metric_name_ok(const std::string &m) { return m == "jaccard" || m == "weightedjaccard" || m == "bottomk"; }
+static int metric_code(const std::string &m) { return m == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : m == "bottomk" ? HULK_METRIC_BOTTOMK : HULK_METRIC_JACCARD; }
+
 int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
                      uint32_t threads, const char *matrix_csv_path, const char *banner_csv_path, double *distances,
                      hulk_smash_stats *stats, char *errbuf, uint64_t errbuf_len) {
@@ -593,8 +597,8 @@ int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uin
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
     const std::string metric_s = metric, algo_s = algo;
     // cmd/smash.go:60-82
-    if (metric_s != "jaccard" && metric_s != "weightedjaccard")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard]");
+    if (!metric_name_ok(metric_s))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
     if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
     const double t0 = now_s();
@@ -604,13 +608,15 @@ int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uin
     const uint32_t n = (uint32_t)set->files.size(), S = set->size;
     if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
     const double t1 = now_s();
     std::vector<double> own;
     double *dist = distances;
     if (!dist) { own.resize((size_t)n * n); dist = own.data(); }
     double kernel_ms = 0.0;
     {
-        const int rc = hulk_smash_ex(device, set->mins.data(), set->weights.data(), n, S, metric_s == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD,
+        const int rc = hulk_smash_ex(device, set->mins.data(), set->weights.data(), n, S, metric_code(metric_s),
                                      dist, &kernel_ms);
         if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
     }
@@ -656,8 +662,8 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
     if (stats) memset(stats, 0, sizeof *stats);
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
     const std::string metric_s = metric, algo_s = algo;
-    if (metric_s != "jaccard" && metric_s != "weightedjaccard")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard]");
+    if (!metric_name_ok(metric_s))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
     if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
     if (k == 0 || k > HULK_SEARCH_MAX_K) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
@@ -678,6 +684,8 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
     }
     if (metric_s == "weightedjaccard" && !qs->histosketch)          // sketchio.go:287-293
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
     const hulk_sketch_set *db = self ? qs : ds;
     const uint32_t m = (uint32_t)qs->files.size();
     std::vector<uint32_t> own_i, own_c; std::vector<double> own_d;
@@ -686,7 +694,7 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
     if (!hit_count) { own_c.resize(m); hit_count = own_c.data(); }
     hulk_search_opts o;
     memset(&o, 0, sizeof o);
-    o.k = k; o.metric = metric_s == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD; o.role = role; o.flags = flags;
+    o.k = k; o.metric = metric_code(metric_s); o.role = role; o.flags = flags;
     o.max_distance = max_distance;
     {
         const int rc = hulk_search(device, qs->mins.data(), qs->weights.data(), m, self ? nullptr : ds->mins.data(), self ? nullptr : ds->weights.data(),
@@ -717,8 +725,8 @@ int hulk_cluster_files(int device, const char *const *paths, uint32_t n_paths, u
     if (stats) memset(stats, 0, sizeof *stats);
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
     const std::string metric_s = metric, algo_s = algo;
-    if (metric_s != "jaccard" && metric_s != "weightedjaccard")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard]");
+    if (!metric_name_ok(metric_s))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
     if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
     if (!(max_distance >= 0.0 && max_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_cluster: max_distance must be in [0, 1]");
@@ -727,12 +735,14 @@ int hulk_cluster_files(int device, const char *const *paths, uint32_t n_paths, u
     struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
     if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
     const uint32_t n = (uint32_t)set->files.size();
     std::vector<uint32_t> own;
     if (!label) { own.resize(n); label = own.data(); }
     hulk_cluster_opts o;
     memset(&o, 0, sizeof o);
-    o.metric = metric_s == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD;
+    o.metric = metric_code(metric_s);
     o.max_distance = max_distance;
     {
         const int rc = hulk_cluster(device, set->mins.data(), set->weights.data(), n, set->size, &o, label, stats);
@@ -753,8 +763,8 @@ int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n_paths
     if (n_edges) *n_edges = 0;
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
     const std::string metric_s = metric, algo_s = algo;
-    if (metric_s != "jaccard" && metric_s != "weightedjaccard")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard]");
+    if (!metric_name_ok(metric_s))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
     if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
     const bool cut = cut_distance == cut_distance;                  // NaN: no cut
@@ -765,6 +775,8 @@ int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n_paths
     struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
     if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
         return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
     const uint32_t n = (uint32_t)set->files.size();
     std::vector<uint32_t> own_a, own_b; std::vector<double> own_d;
     uint32_t m = 0;
@@ -773,7 +785,7 @@ int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n_paths
     if (!edge_distance) { own_d.resize(n); edge_distance = own_d.data(); }
     hulk_dendrogram_opts o;
     memset(&o, 0, sizeof o);
-    o.metric = metric_s == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : HULK_METRIC_JACCARD;
+    o.metric = metric_code(metric_s);
     {
         const int rc = hulk_dendrogram(device, set->mins.data(), set->weights.data(), n, set->size, &o, edge_a, edge_b, edge_distance, &m, stats);
         if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));

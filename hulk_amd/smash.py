@@ -20,7 +20,11 @@ from . import _lib
 from ._lib import HulkError
 from .sketchio import load_hulk_data
 
-AVAIL_METRICS = ["jaccard", "weightedjaccard"]          # cmd/smash.go:30 (the others are unreachable from the CLI)
+# cmd/smash.go:30 (the others are unreachable from the CLI), and "bottomk": the set similarity of two KMV sketches
+# (KMVsketch.GetSimilarity, kmv.go:119-159, which the reference never reaches from its command line) — kmv sketches only
+AVAIL_METRICS = ["jaccard", "weightedjaccard", "bottomk"]
+PANEL_METRICS = ["jaccard", "weightedjaccard"]          # panels score histosketch snapshots
+_METRIC_CODE = {"jaccard": _lib.HULK_METRIC_JACCARD, "weightedjaccard": _lib.HULK_METRIC_WEIGHTED_JACCARD, "bottomk": _lib.HULK_METRIC_BOTTOMK}
 AVAIL_ALGORITHMS = ["histosketch", "kmv", "khf"]        # sketchio.go:17
 
 
@@ -41,18 +45,20 @@ def collect_jsons(sketch_dir, recursive=False):
 
 def distance_matrix(mins, weights, metric="jaccard", device=0, timing=None):
     """distances[s, q] = GetDistance(subject s, query q) for all pairs, computed on the GPU.
-    timing: a dict that receives "kernel_ms" (k_smash alone, HIP events; hulk_smash_ex)."""
+    timing: a dict that receives "kernel_ms" (k_smash alone, HIP events; hulk_smash_ex).
+    metric "bottomk": 1 - (multiset intersection of the two rows of mins, as uint64) / sketch_size, whatever the order of a row's
+    values; weights is not read and may be None."""
     mins = np.ascontiguousarray(mins, dtype=np.uint64)
-    weights = np.ascontiguousarray(weights, dtype=np.float64)
-    if mins.shape != weights.shape or mins.ndim != 2:
+    weights = _weights_for(metric, mins, weights)
+    if (weights is not None and mins.shape != weights.shape) or mins.ndim != 2:
         raise ValueError("mins/weights must be [n_sketches][sketch_size]")
     n, s = mins.shape
     out = np.zeros((n, n), dtype=np.float64)
     L = _lib.load()
     import ctypes
     kms = ctypes.c_double(0.0)
-    rc = L.hulk_smash_ex(device, mins.ctypes.data, weights.ctypes.data, n, s,
-                         1 if metric == "weightedjaccard" else 0, out.ctypes.data,
+    rc = L.hulk_smash_ex(device, mins.ctypes.data, None if weights is None else weights.ctypes.data, n, s,
+                         _METRIC_CODE.get(metric, _lib.HULK_METRIC_JACCARD), out.ctypes.data,
                          ctypes.byref(kms) if timing is not None else None)
     if timing is not None:
         timing["kernel_ms"] = kms.value
@@ -61,13 +67,20 @@ def distance_matrix(mins, weights, metric="jaccard", device=0, timing=None):
     return out
 
 
+def _weights_for(metric, mins, weights):
+    """weights as a contiguous float64 array; None stays None for bottomk, which reads none"""
+    if weights is None and metric == "bottomk":
+        return None
+    return np.ascontiguousarray(weights, dtype=np.float64)
+
+
 def panel_distances(snap_mins, snap_weights, panel_mins, panel_weights, metric="jaccard", role="row", device=0):
     """distances[i, p] between sketch i of snap_* [m][S] and sketch p of panel_* [n_panel][S], on the GPU with the kernel that
     scores sketch snapshots against a panel (hulk_panel_distances): role "row" = sketch i is the subject (the block
     distance_matrix([snap; panel])[:m, m:]), "column" = panel sketch p is (the block [m:, :m] transposed).  One against many."""
     import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if metric not in PANEL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {PANEL_METRICS}")
     if role not in ("row", "column"):
         raise ValueError("role must be 'row' or 'column'")
     sm = np.ascontiguousarray(snap_mins, dtype=np.uint64); sw = np.ascontiguousarray(snap_weights, dtype=np.float64)
@@ -91,7 +104,7 @@ def _search_consts(metric, role):
         raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
     if role not in ("row", "column"):
         raise ValueError("role must be 'row' or 'column'")
-    return (_lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+    return (_METRIC_CODE[metric],
             _lib.HULK_PANEL_COLUMN if role == "column" else _lib.HULK_PANEL_ROW)
 
 
@@ -111,16 +124,16 @@ def search(q_mins, q_weights, db_mins, db_weights, k, metric="jaccard", role="ro
     seconds_total, kernel_ms_dist, kernel_ms_select, strips, query_blocks."""
     import ctypes
     metric_c, role_c = _search_consts(metric, role)
-    qm = np.ascontiguousarray(q_mins, dtype=np.uint64); qw = np.ascontiguousarray(q_weights, dtype=np.float64)
-    if qm.ndim != 2 or qm.shape != qw.shape:
+    qm = np.ascontiguousarray(q_mins, dtype=np.uint64); qw = _weights_for(metric, qm, q_weights)
+    if qm.ndim != 2 or (qw is not None and qm.shape != qw.shape):
         raise ValueError("mins/weights must be [n][sketch_size]")
     if self_search:
         if db_mins is not None or db_weights is not None:
             raise ValueError("self_search takes no database")
         dm = dw = None
     else:
-        dm = np.ascontiguousarray(db_mins, dtype=np.uint64); dw = np.ascontiguousarray(db_weights, dtype=np.float64)
-        if dm.ndim != 2 or dm.shape != dw.shape:
+        dm = np.ascontiguousarray(db_mins, dtype=np.uint64); dw = _weights_for(metric, dm, db_weights)
+        if dm.ndim != 2 or (dw is not None and dm.shape != dw.shape):
             raise ValueError("mins/weights must be [n][sketch_size]")
         if qm.shape[1] != dm.shape[1]:
             raise HulkError(-30, f"sketch length mismatch: {qm.shape[1]} vs {dm.shape[1]}\n")
@@ -131,7 +144,7 @@ def search(q_mins, q_weights, db_mins, db_weights, k, metric="jaccard", role="ro
     index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(m, dtype=np.uint32)
     st = _lib.SearchStats()
     L = _lib.load()
-    rc = L.hulk_search(device, qm.ctypes.data, qw.ctypes.data, m, None if dm is None else dm.ctypes.data, None if dw is None else dw.ctypes.data,
+    rc = L.hulk_search(device, qm.ctypes.data, None if qw is None else qw.ctypes.data, m, None if dm is None else dm.ctypes.data, None if dw is None else dw.ctypes.data,
                        0 if dm is None else dm.shape[0], qm.shape[1], ctypes.byref(o), index.ctypes.data, dist.ctypes.data, count.ctypes.data,
                        ctypes.byref(st))
     if rc != 0:
@@ -188,18 +201,18 @@ def cluster(mins, weights, max_distance, metric="jaccard", band_rows=0, device=0
     import ctypes
     if metric not in AVAIL_METRICS:
         raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    m = np.ascontiguousarray(mins, dtype=np.uint64); w = np.ascontiguousarray(weights, dtype=np.float64)
-    if m.ndim != 2 or m.shape != w.shape:
+    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
+    if m.ndim != 2 or (w is not None and m.shape != w.shape):
         raise ValueError("mins/weights must be [n][sketch_size]")
     band_rows = int(band_rows)
     if not 0 <= band_rows < 2 ** 32:
         raise ValueError("band_rows must be a multiple of 32 (0 = default)")
-    o = _lib.ClusterOpts(metric=_lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+    o = _lib.ClusterOpts(metric=_METRIC_CODE[metric],
                          max_distance=float(max_distance), band_rows=band_rows)
     labels = np.zeros(max(m.shape[0], 1), dtype=np.uint32)
     st = _lib.ClusterStats()
     L = _lib.load()
-    rc = L.hulk_cluster(device, m.ctypes.data, w.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), labels.ctypes.data, ctypes.byref(st))
+    rc = L.hulk_cluster(device, m.ctypes.data, None if w is None else w.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), labels.ctypes.data, ctypes.byref(st))
     if rc != 0:
         raise HulkError(rc, L.hulk_last_error(None).decode())
     if stats is not None:
@@ -247,20 +260,20 @@ def dendrogram(mins, weights, metric="jaccard", band_rows=0, device=0, stats=Non
     import ctypes
     if metric not in AVAIL_METRICS:
         raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    m = np.ascontiguousarray(mins, dtype=np.uint64); w = np.ascontiguousarray(weights, dtype=np.float64)
-    if m.ndim != 2 or m.shape != w.shape:
+    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
+    if m.ndim != 2 or (w is not None and m.shape != w.shape):
         raise ValueError("mins/weights must be [n][sketch_size]")
     band_rows = int(band_rows)
     if not 0 <= band_rows < 2 ** 32:
         raise ValueError("band_rows must be a multiple of 32 (0 = default)")
-    o = _lib.DendrogramOpts(metric=_lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
+    o = _lib.DendrogramOpts(metric=_METRIC_CODE[metric],
                             band_rows=band_rows)
     n = m.shape[0]
     a = np.zeros(max(n, 1), dtype=np.uint32); b = np.zeros(max(n, 1), dtype=np.uint32); d = np.zeros(max(n, 1), dtype=np.float64)
     ne = ctypes.c_uint32(0)
     st = _lib.DendrogramStats()
     L = _lib.load()
-    rc = L.hulk_dendrogram(device, m.ctypes.data, w.ctypes.data, n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data, d.ctypes.data,
+    rc = L.hulk_dendrogram(device, m.ctypes.data, None if w is None else w.ctypes.data, n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data, d.ctypes.data,
                            ctypes.byref(ne), ctypes.byref(st))
     if rc != 0:
         raise HulkError(rc, L.hulk_last_error(None).decode())
@@ -478,10 +491,14 @@ def smash_python(sketch_dir, out_file, ksize=21, algo="histosketch", metric="jac
             raise HulkError(-30, f"sketch length mismatch: {size} vs {len(a.mins)}\n")
     mins = np.stack([a.mins for a in sk])
     if algo == "histosketch":
+        if metric == "bottomk":
+            raise HulkError(-30, "bottomk is only supported for kmv sketches")
         weights = np.stack([a.weights for a in sk])
     elif metric == "weightedjaccard":                           # sketchio.go:287-293
         raise HulkError(-30, "weighted jaccard is only supported for histosketches")
     else:
+        if metric == "bottomk" and algo != "kmv":
+            raise HulkError(-30, "bottomk is only supported for kmv sketches")
         weights = np.zeros(mins.shape)                          # MinHash signatures carry no weights (khf.go:12-16)
     t_loaded = time.perf_counter()
     dist = distance_matrix(mins, weights, metric, device)

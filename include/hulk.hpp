@@ -298,6 +298,16 @@ class Boss {
     std::unique_ptr<SnapState> snap_;      // OnSnapshot: lives on the heap, the library holds its address
 };
 
+// the metric names of Smash, Search, Cluster and Dendrogram -> HULK_METRIC_*.  "bottomk" is the estimator of KMV sketches
+// (KMVsketch.GetSimilarity, the multiset intersection of the two value lists as uint64; HistoSketch::Sketch carries the values,
+// SketchWeights is not read); the *Files forms take it with algo "kmv" only
+inline int MetricCode(const std::string &metric) {
+    if (metric == "jaccard") return HULK_METRIC_JACCARD;
+    if (metric == "weightedjaccard") return HULK_METRIC_WEIGHTED_JACCARD;
+    if (metric == "bottomk") return HULK_METRIC_BOTTOMK;
+    throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+}
+
 // sketchio's pairwise distances over loaded sketches (cmd/smash.go:183-226): distances[s*N+q]
 inline std::vector<double> Smash(const std::vector<HistoSketch> &sketches, const std::string &metric, int device = 0) {
     const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
@@ -307,10 +317,7 @@ inline std::vector<double> Smash(const std::vector<HistoSketch> &sketches, const
         if (sketches[i].Sketch.size() != S) throw Error(HULK_ERR_ARG, "sketch length mismatch");
         for (uint32_t j = 0; j < S; j++) { mins[(size_t)i * S + j] = sketches[i].Sketch[j]; weights[(size_t)i * S + j] = sketches[i].SketchWeights[j]; }
     }
-    int m;
-    if (metric == "jaccard") m = HULK_METRIC_JACCARD;
-    else if (metric == "weightedjaccard") m = HULK_METRIC_WEIGHTED_JACCARD;
-    else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+    const int m = MetricCode(metric);
     const int rc = hulk_smash(device, mins.data(), weights.data(), N, S, m, out.data());
     if (rc != HULK_OK) throw Error(rc, hulk_strerror(rc));
     return out;
@@ -341,9 +348,7 @@ inline std::vector<std::vector<Hit>> Search(const std::vector<HistoSketch> &quer
     hulk_search_opts o = hulk_search_opts();
     o.k = k; o.role = queryIsSubject ? HULK_PANEL_ROW : HULK_PANEL_COLUMN; o.flags = P ? 0u : HULK_SEARCH_SELF;
     o.max_distance = maxDistance; o.scratch_bytes = scratchBytes;
-    if (metric == "jaccard") o.metric = HULK_METRIC_JACCARD;
-    else if (metric == "weightedjaccard") o.metric = HULK_METRIC_WEIGHTED_JACCARD;
-    else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+    o.metric = MetricCode(metric);
     const size_t kk = k ? k : 1;
     std::vector<uint32_t> index(M * kk + 1), count((size_t)M + 1);
     std::vector<double> distance(M * kk + 1);
@@ -372,9 +377,7 @@ inline std::vector<uint32_t> Cluster(const std::vector<HistoSketch> &sketches, d
     }
     hulk_cluster_opts o = hulk_cluster_opts();
     o.max_distance = maxDistance; o.band_rows = bandRows;
-    if (metric == "jaccard") o.metric = HULK_METRIC_JACCARD;
-    else if (metric == "weightedjaccard") o.metric = HULK_METRIC_WEIGHTED_JACCARD;
-    else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+    o.metric = MetricCode(metric);
     std::vector<uint32_t> label((size_t)N + 1);
     const int rc = hulk_cluster(device, mins.data(), weights.data(), N, S, &o, label.data(), stats);
     if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
@@ -418,9 +421,7 @@ inline std::vector<DendrogramEdge> Dendrogram(const std::vector<HistoSketch> &sk
     }
     hulk_dendrogram_opts o = hulk_dendrogram_opts();
     o.band_rows = bandRows;
-    if (metric == "jaccard") o.metric = HULK_METRIC_JACCARD;
-    else if (metric == "weightedjaccard") o.metric = HULK_METRIC_WEIGHTED_JACCARD;
-    else throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
+    o.metric = MetricCode(metric);
     std::vector<uint32_t> a((size_t)N + 1), b((size_t)N + 1);
     std::vector<double> d((size_t)N + 1);
     uint32_t m = 0;

@@ -530,6 +530,15 @@ int hulk_get_cws_tables(hulk_ctx *ctx, double *r, double *c, double *b);
  * distances.GetWJD (distances.go:44-72) with the subject's weights on both sides, as the reference does. */
 #define HULK_METRIC_JACCARD 0
 #define HULK_METRIC_WEIGHTED_JACCARD 1
+/* Bottom-k set similarity, the estimator of a KMV sketch (KMVsketch.GetSimilarity, src/minhash/kmv.go:119-159): with the two value
+ * lists taken as multisets of uint64 (never through float64), intersect = the sum over the distinct values v of
+ * min(multiplicity in A, multiplicity in B), distance = 1.0 - (double)intersect / (double)sketch_size.  Symmetric: no subject, the
+ * role of a search is ignored.  The order of a sketch's values does not matter (the device sorts every sketch once); `weights` is
+ * never read and may be NULL.  sketch_size at most HULK_MINHASH_MAX_SKETCH.  Both lists have sketch_size values, as everywhere in
+ * this interface: lists of unequal length, which GetSimilarity tolerates, are not supported.  Accepted by hulk_smash, hulk_smash_ex,
+ * hulk_search, hulk_cluster and hulk_dendrogram, with the same bits for a pair in all of them; not by the panel entry points.
+ * (The value 2 is no metric.) */
+#define HULK_METRIC_BOTTOMK 3
 int hulk_smash(int device, const uint64_t *mins, const double *weights, uint32_t n_sketches,
                uint32_t sketch_size, int metric, double *distances);
 /* The same; *kernel_ms (may be NULL) receives the duration of the distance kernel alone (HIP events), without the PCIe copies. */
@@ -569,7 +578,9 @@ typedef struct hulk_smash_stats {
 /* runSmash + makeMatrix: load, smash on `device`, and — matrix_csv_path != NULL — write the file encoding/csv would: the sorted
  * paths as header, then one row per subject of strconv.FormatFloat(100 - 100 * distance, 'f', 2, 64) (cmd/smash.go:183-226);
  * banner_csv_path != NULL: makeBannerMatrix's file (cmd/smash.go:229-261: a sketch's mins + its banner label per line, in
- * sorted file order).  metric: "jaccard" | "weightedjaccard"; algo: "histosketch" | "kmv" | "khf".  `distances` (may be NULL)
+ * sorted file order).  metric: "jaccard" | "weightedjaccard" | "bottomk" (HULK_METRIC_BOTTOMK; with algo "kmv" only: any other
+ * algorithm is HULK_ERR_ARG, "bottomk is only supported for kmv sketches", where "weighted jaccard is only supported for
+ * histosketches" is checked; the same in hulk_search_files, hulk_cluster_files and hulk_dendrogram_files); algo: "histosketch" | "kmv" | "khf".  `distances` (may be NULL)
  * receives [n][n] in sorted-path order; `stats` may be NULL. */
 int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
                      uint32_t threads, const char *matrix_csv_path, const char *banner_csv_path, double *distances,
@@ -596,7 +607,7 @@ int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uin
 #define HULK_SEARCH_SELF 1u
 typedef struct hulk_search_opts {
     uint32_t k;              /* hits per query, 1 .. HULK_SEARCH_MAX_K */
-    int metric;              /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD */
+    int metric;              /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD / HULK_METRIC_BOTTOMK */
     int role;                /* HULK_PANEL_ROW / HULK_PANEL_COLUMN */
     uint32_t flags;          /* HULK_SEARCH_SELF */
     double max_distance;     /* in [0, 1]: only hits with distance <= max_distance; negative or NaN: no limit */
@@ -615,7 +626,7 @@ int hulk_search(int device, const uint64_t *q_mins, const double *q_weights, uin
 /* The directory form: both sets of sketch files go through hulk_load_sketches' loader (MD5, FindSketch, the reference's error texts;
  * sorted path order within each set, a path given twice counts once) — but a set of ONE sketch is valid here: "needs at least 2" is
  * smash's rule.  Different sketch lengths across the sets: "sketch length mismatch: %d vs %d\n" (the queries', the database's).
- * HULK_SEARCH_SELF in flags: db_paths NULL, the queries are searched among themselves.  metric: "jaccard" | "weightedjaccard"; algo:
+ * HULK_SEARCH_SELF in flags: db_paths NULL, the queries are searched among themselves.  metric: "jaccard" | "weightedjaccard" | "bottomk" (kmv only); algo:
  * "histosketch" | "kmv" | "khf".  csv_path != NULL: a file with the header "query,rank,hit,similarity" and one line per hit, in query
  * order and then rank order from 1: the two paths as encoding/csv quotes them and strconv.FormatFloat(100 - 100 * distance, 'f', 2, 64),
  * the string `smash` prints for that pair.  hit_index / hit_distance [unique query paths][k] and hit_count may be NULL; the indices
@@ -640,7 +651,7 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
  * HULK_CLUSTER_MAX_N (the set is prepared in one launch).  n == 1 is valid: one cluster, 0 links. */
 #define HULK_CLUSTER_MAX_N 2097088u
 typedef struct hulk_cluster_opts {
-    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD */
+    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD / HULK_METRIC_BOTTOMK */
     double max_distance;   /* tau in [0, 1]; anything else (NaN included): HULK_ERR_ARG */
     uint32_t band_rows;    /* subject rows per launch; 0 = default (2048, search's block); a multiple of 32 (above 2^20: 2^20) */
     uint32_t flags;        /* zero */
@@ -654,7 +665,7 @@ typedef struct hulk_cluster_stats {
 int hulk_cluster(int device, const uint64_t *mins, const double *weights, uint32_t n, uint32_t sketch_size,
                  const hulk_cluster_opts *opts, uint32_t *label, hulk_cluster_stats *stats);
 /* The directory form: the files go through hulk_load_sketches' loader (MD5, FindSketch, the reference's error texts; sorted unique
- * paths; a set of ONE sketch is valid).  metric: "jaccard" | "weightedjaccard" (histosketches only: hulk_smash_files' text); algo:
+ * paths; a set of ONE sketch is valid).  metric: "jaccard" | "weightedjaccard" (histosketches only: hulk_smash_files' text) | "bottomk" (kmv only: likewise); algo:
  * "histosketch" | "kmv" | "khf".  label [unique paths] may be NULL.  csv_path != NULL: a file with the header
  * "sketch,cluster,size,representative" and one line per sketch in sorted path order: its path, the 1-based ordinal of its cluster
  * (clusters ordered by their smallest member), the cluster's member count, the path of its smallest member; paths as encoding/csv
@@ -683,7 +694,7 @@ int hulk_cluster_files(int device, const char *const *paths, uint32_t n, uint32_
  * HULK_ERR_ARG before any HIP call, with a text in hulk_last_error(NULL): NULL arrays, opts or n_edges; n or sketch_size == 0; an
  * unknown metric; band_rows not a multiple of 32; non-zero flags or reserved; n above HULK_CLUSTER_MAX_N. */
 typedef struct hulk_dendrogram_opts {
-    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD */
+    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD / HULK_METRIC_BOTTOMK */
     uint32_t band_rows;    /* subject rows per launch; 0 = default (2048); a multiple of 32 (above 2^20: 2^20) */
     uint32_t flags;        /* zero */
     uint64_t reserved[4];  /* zero */
@@ -697,7 +708,7 @@ int hulk_dendrogram(int device, const uint64_t *mins, const double *weights, uin
                     uint32_t *n_edges, hulk_dendrogram_stats *stats);
 /* The directory form: the files go through hulk_load_sketches' loader (MD5, FindSketch, the reference's error texts; sorted unique
  * paths, which the indices count; a set of ONE sketch is valid).  metric: "jaccard" | "weightedjaccard" (histosketches only:
- * hulk_smash_files' text); algo: "histosketch" | "kmv" | "khf".  edge_a / edge_b / edge_distance [unique paths - 1] and n_edges may be
+ * hulk_smash_files' text) | "bottomk" (kmv only: likewise); algo: "histosketch" | "kmv" | "khf".  edge_a / edge_b / edge_distance [unique paths - 1] and n_edges may be
  * NULL.  csv_path != NULL: a file with the header "merge,sketch_a,sketch_b,distance,similarity,size" and one line per edge in merge
  * order: the 1-based ordinal, the two paths as encoding/csv quotes them, the distance as %.17g (it reads back to the same double: a
  * cut can be repeated exactly), strconv.FormatFloat(100 - 100 * distance, 'f', 2, 64) as `smash` prints it, and the size of the
