@@ -32,12 +32,31 @@ namespace {
 // state at a step boundary) and finished in a denser round of the wave's pool (below).
 // p >= n is tested on the upper dwords alone: p is a non-negative finite double and n < 2^20 is an integer whose
 // double has a zero lower dword, so bits(p) >= bits(n) <=> hi(p) >= hi(n)  (v_cmp_lt_u32 instead of v_cmp_nge_f64).
-__device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, double fn, double t0, uint32_t cut,
-                                                 unsigned long long &left) {
-    uint32_t tlo, thi, mlo, mhi, olo, ohi;
-    const uint64_t fb = (uint64_t)__double_as_longlong(fn), tb = (uint64_t)__double_as_longlong(t0);
-    const uint32_t fhi = (uint32_t)(fb >> 32), t0lo = (uint32_t)tb, t0hi = (uint32_t)(tb >> 32);
+//
+// The block is entered and left without a copy: the C++ values are bound to the loop's registers by physical-register
+// constraints.  The three loop-invariant registers (v47, v[56:57], v58) are written once per kernel by jump_consts() and only
+// read here; key and t are in/out operands in v[40:41] and v[44:45], so a caller's value is computed into them and used out
+// of them; the only move left in the block is the odd exit's, which brings the live key back from v[42:43].
+// The block runs in wave-uniform control flow and takes the lanes it is to work on as a scalar mask (`entry`): lanes outside
+// it keep key and t as they came and are never in `left`.  `left` comes out as what it is, EXEC at the exit in a scalar
+// pair, and is used as a mask from there on (lane_in, rank_in): no lane ever holds it as a bool.
+struct JumpConsts { uint32_t two52_hi; uint64_t bias; uint32_t n_hi; };        // v47, v[56:57], v58
+__device__ __forceinline__ JumpConsts jump_consts(double fn) {
+    JumpConsts K;
     const uint64_t cb = (uint64_t)__double_as_longlong(0x1p-31 - 0x1p21);       // exact: 2^21 - 2^-31 is a double
+    const uint32_t fhi = (uint32_t)((uint64_t)__double_as_longlong(fn) >> 32);
+    // (asm, not plain constants: a constant would be materialised again in front of every block)
+    asm volatile("v_mov_b32 v47, 0x43300000\n\t"
+                 "v_mov_b32 v56, %[clo]\n\t"
+                 "v_mov_b32 v57, %[chi]\n\t"
+                 "v_mov_b32 v58, %[fhi]"
+                 : "={v47}"(K.two52_hi), "={v[56:57]}"(K.bias), "={v58}"(K.n_hi)
+                 : [clo] "s"((uint32_t)cb), [chi] "s"((uint32_t)(cb >> 32)), [fhi] "v"(fhi));
+    return K;
+}
+__device__ __forceinline__ unsigned long long jump_steps_asm(uint64_t &key, double &t, const JumpConsts &K,
+                                                             unsigned long long entry, uint32_t cut) {
+    unsigned long long left;
 #define HULK_JSTEP(KS_LO, KS_HI, KD, KD_HI, EXIT)                                    \
     "v_mad_u64_u32 v[52:53], s[62:63], " KS_LO ", %[ahi], 0\n\t"                     \
     "v_mad_u64_u32 v[54:55], s[62:63], " KS_HI ", %[alo], v[52:53]\n\t"              \
@@ -59,15 +78,7 @@ __device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, d
     "s_cmp_le_u32 s62, %[cut]\n\t"                                                   \
     "s_cbranch_scc1 " EXIT "\n\t"
     asm volatile(
-        "s_mov_b64 s[60:61], exec\n\t"
-        "v_mov_b32 v40, %[klo]\n\t"
-        "v_mov_b32 v41, %[khi]\n\t"
-        "v_mov_b32 v47, 0x43300000\n\t"
-        "v_mov_b32 v56, %[clo]\n\t"
-        "v_mov_b32 v57, %[chi]\n\t"
-        "v_mov_b32 v58, %[fhi]\n\t"
-        "v_mov_b32 v44, %[t0lo]\n\t"
-        "v_mov_b32 v45, %[t0hi]\n\t"
+        "s_and_saveexec_b64 s[60:61], %[entry]\n\t"
         "1:\n\t"
         HULK_JSTEP("v40", "v41", "v[42:43]", "v43", "3f")
         HULK_JSTEP("v42", "v43", "v[40:41]", "v41", "2f")
@@ -76,69 +87,65 @@ __device__ __forceinline__ double jump_steps_asm(uint32_t &klo, uint32_t &khi, d
         "v_mov_b32 v40, v42\n\t"
         "v_mov_b32 v41, v43\n\t"
         "2:\n\t"
-        "s_mov_b32 %[mlo], exec_lo\n\t"
-        "s_mov_b32 %[mhi], exec_hi\n\t"
+        "s_mov_b64 %[left], exec\n\t"
         "s_mov_b64 exec, s[60:61]\n\t"
-        "v_mov_b32 %[tlo], v44\n\t"
-        "v_mov_b32 %[thi], v45\n\t"
-        "v_mov_b32 %[olo], v40\n\t"
-        "v_mov_b32 %[ohi], v41\n\t"
-        : [tlo] "=v"(tlo), [thi] "=v"(thi), [olo] "=v"(olo), [ohi] "=v"(ohi), [mlo] "=s"(mlo), [mhi] "=s"(mhi)
-        : [klo] "v"(klo), [khi] "v"(khi), [fhi] "v"(fhi), [t0lo] "v"(t0lo), [t0hi] "v"(t0hi),
-          [clo] "s"((uint32_t)cb), [chi] "s"((uint32_t)(cb >> 32)),
+        : [left] "=s"(left), "+{v[40:41]}"(key), "+{v[44:45]}"(t)
+        : [entry] "s"(entry), "{v47}"(K.two52_hi), "{v[56:57]}"(K.bias), "{v58}"(K.n_hi),
           [alo] "s"(0x87B0B0FDu), [ahi] "s"(0x27BB2EE6u), [cut] "s"(cut), [p31] "s"(0x3E00000000000000ull /* 2^-31 */)
-        : "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55",
-          "v56", "v57", "v58", "s60", "s61", "s62", "s63", "vcc", "scc", "memory");
+        : "v42", "v43", "v46", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55",
+          "s60", "s61", "s62", "s63", "vcc", "scc", "memory");
 #undef HULK_JSTEP
-    klo = olo; khi = ohi;
-    left = ((unsigned long long)mhi << 32) | mlo;
-    return __longlong_as_double((long long)(((uint64_t)thi << 32) | tlo));
+    return left;
 }
 
-// The pool: the slow chains of a wave, kept in four registers per lane — {key lo, key hi, slot << 20 | t, index into ml.key} in
+// The pool: the slow chains of a wave, kept in four registers per lane — {key (a pair), slot << 20 | t, index into ml.key} in
 // pool position = lane, positions [0, pc) in use, pc wave-uniform.  The index is global and the slot travels with the entry, so
 // one pool holds chains of several regions and spectra; the third word is the output word once the chain has ended.
 // Chains change lanes with ds_permute_b32: it goes through the LDS crossbar and allocates no LDS.  Only lanes in EXEC send or
-// receive, so every move below is a true permutation of all 64 lanes, made in wave-uniform control flow.
-__device__ __forceinline__ void permute4(uint32_t dest, uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) {
+// receive, so every move below is made in wave-uniform control flow with all 64 lanes.  Which lanes move is a wave-uniform mask
+// in a scalar pair, and that pair is itself the select operand of v_cndmask_b32 / the EXEC of a store (lane_in): the
+// destination needs no per-lane membership test and no branch.  The lanes that hand nothing over all send to ONE position
+// nobody reads (ds_permute_b32 keeps one of the values sent to a lane): no second numbering for them.
+__device__ __forceinline__ bool lane_in(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ unsigned long long lanes_below(uint32_t n) { return n >= 64u ? ~0ull : (1ull << n) - 1ull; }   // n wave-uniform
+__device__ __forceinline__ void permute4(uint32_t dest, uint64_t &k, uint32_t &c, uint32_t &d) {
     const int addr = (int)(dest << 2);
-    a = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)a);
-    b = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)b);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)k);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)(k >> 32));
     c = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)c);
     d = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)d);
+    k = ((uint64_t)hi << 32) | lo;
 }
 __device__ __forceinline__ uint32_t rank_in(unsigned long long m) {       // set bits of m below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
-constexpr int JUMP_CUT_DEFAULT = 24, JUMP_PCUT_DEFAULT = 32, JUMP_REGIONS_DEFAULT = 4;     // swept: profiles/k1b_pool.md
-struct JumpPool { uint32_t klo, khi, word, at, pc; };
+constexpr int JUMP_CUT_DEFAULT = 24, JUMP_PCUT_DEFAULT = 32, JUMP_REGIONS_DEFAULT = 4;     // swept: profiles/k1b_lean.md
+struct JumpPool { uint64_t key; uint32_t word, at, pc; };
 
-// the chains of the lanes in m (pc + popcount(m) <= 64) go to pool positions pc, pc + 1, ... in lane order; the other lanes
-// take the remaining positions, whose owners keep what they had
-__device__ __forceinline__ void pool_push(JumpPool &p, unsigned long long m, uint32_t klo, uint32_t khi, uint32_t word, uint32_t at,
-                                          int lane) {
-    const uint32_t n = (uint32_t)__popcll(m), rank = rank_in(m), others = (uint32_t)lane - rank;
-    const uint32_t dest = ((m >> lane) & 1ull) ? p.pc + rank : (others < p.pc ? others : others + n);
-    permute4(dest, klo, khi, word, at);
-    if ((uint32_t)lane - p.pc < n) { p.klo = klo; p.khi = khi; p.word = word; p.at = at; }
-    p.pc += n;
+// the chains of the lanes in m (m != 0, pc + popcount(m) <= 64) go to pool positions pc, pc + 1, ... in lane order.  The other
+// lanes send to the first position past the window (modulo 64: position 0 when the window ends at 64 — then pc > 0, or every
+// lane is a sender), whose owner, like everyone outside the window, keeps what it had
+__device__ __forceinline__ void pool_push(JumpPool &p, unsigned long long m, uint64_t k, uint32_t word, uint32_t at) {
+    const uint32_t n = (uint32_t)__popcll(m), end = p.pc + n;
+    const uint32_t to = p.pc + rank_in(m);                        // (both computed in front of the select: no branch)
+    permute4(lane_in(m) ? to : (end & 63u), k, word, at);
+    if (lane_in(lanes_below(n) << p.pc)) { p.key = k; p.word = word; p.at = at; }
+    p.pc = end;
 }
-// one dense round over the pool: runs until at most pcut of its chains are live, stores the keys of those that ended and
-// moves the survivors to the front
-__device__ __forceinline__ void pool_round(JumpPool &p, uint32_t *__restrict__ key, double fn, uint32_t pcut, int lane) {
-    bool live = false;
-    if ((uint32_t)lane < p.pc) {
-        unsigned long long left = 0;
-        const double t = jump_steps_asm(p.klo, p.khi, fn, (double)(int32_t)(p.word & 0xFFFFFu), pcut, left);
-        live = (left >> lane) & 1ull;
-        p.word = (p.word & ~0xFFFFFu) | (uint32_t)(int32_t)t;
-        if (!live) key[p.at] = p.word;
-    }
-    const unsigned long long m = __ballot(live);
-    const uint32_t n = (uint32_t)__popcll(m);
-    if (m) {
-        const uint32_t rank = rank_in(m);
-        permute4(live ? rank : n + (uint32_t)lane - rank, p.klo, p.khi, p.word, p.at);
+// one dense round over the pool (pc >= 1): runs until at most pcut of its chains are live, stores the keys of those that ended
+// and moves the survivors to the front; the positions behind them are unused and take whatever arrives
+__device__ __forceinline__ void pool_round(JumpPool &p, uint32_t *__restrict__ key, const JumpConsts &K, uint32_t pcut) {
+    const unsigned long long entry = lanes_below(p.pc);
+    uint64_t k = p.key;
+    double t = (double)(p.word & 0xFFFFFu);
+    const unsigned long long left = jump_steps_asm(k, t, K, entry, pcut);
+    p.word = (p.word & ~0xFFFFFu) | (uint32_t)(int32_t)t;
+    if (lane_in(entry & ~left)) key[p.at] = p.word;
+    const uint32_t n = (uint32_t)__popcll(left);
+    if (left) {
+        const uint32_t to = rank_in(left);
+        permute4(lane_in(left) ? to : n, k, p.word, p.at);
+        p.key = k;
     }
     p.pc = n;
 }
@@ -155,7 +162,8 @@ __global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_r
     if (r0 >= n_regions) return;
     const uint32_t r1 = n_regions - r0 < R ? n_regions : r0 + R;
     const double fn = (double)num_bins;
-    JumpPool pool{0u, 0u, 0u, 0u, 0u};
+    const JumpConsts K = jump_consts(fn);
+    JumpPool pool{0ull, 0u, 0u, 0u};
     for (uint32_t region = r0; region < r1; region++) {
         const uint32_t cnt = ml.cnt[region];
         const uint64_t *xl = ml.x + (size_t)region * ml.rcap;
@@ -165,21 +173,19 @@ __global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_r
         if ((uint32_t)lane < cnt) { nx = xl[lane]; ns = sl[lane]; }
         for (uint32_t first = 0; first < cnt; first += 64) {      // wave-uniform: lane 0 is active in every round
             const uint32_t idx = first + (uint32_t)lane;
-            const uint64_t key = nx;
+            uint64_t key = nx;                                      // (the prefetched value becomes the key in the loop's registers)
             uint32_t word = ns << 20;
             if (idx + 64 < cnt) { nx = xl[idx + 64]; ns = sl[idx + 64]; }      // prefetch the lane's next value
-            uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-            bool mine = false;                                     // this lane's chain is not finished
-            if (idx < cnt) {
-                // Literally the reference's step: j = int64(float64(b+1) * (float64(1<<31) / float64(r))).  float64(b) = t is
-                // carried; (t + 1) * q is ONE fma(t, q, q) — the exact product rounded once, as the multiplication is —
-                // so a step needs no add and no ldexp.
-                double t = 0.0;                                     // float64(b), b = 0 before the first step
-                if (!use_c) {
-                    unsigned long long left = 0;
-                    t = jump_steps_asm(klo, khi, fn, 0.0, cut, left);
-                    mine = (left >> lane) & 1ull;
-                } else {
+            const unsigned long long entry = lanes_below(cnt - first);         // the lanes with idx < cnt
+            // Literally the reference's step: j = int64(float64(b+1) * (float64(1<<31) / float64(r))).  float64(b) = t is
+            // carried; (t + 1) * q is ONE fma(t, q, q) — the exact product rounded once, as the multiplication is —
+            // so a step needs no add and no ldexp.
+            double t = 0.0;                                         // float64(b), b = 0 before the first step
+            unsigned long long left;                                // the lanes whose chain is not finished
+            if (!use_c) {
+                left = jump_steps_asm(key, t, K, entry, cut);
+            } else {
+                if (idx < cnt) {
                     uint64_t kk = key;
                     for (;;) {
                         kk = kk * 2862933555777941757ull + 1;
@@ -189,22 +195,24 @@ __global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_r
                         t = __builtin_trunc(p);                     // j = int64(p): exact, < 2^31
                     }
                 }
-                word |= (uint32_t)(int32_t)t;
-                if (!mine) ml.key[base + idx] = word;
+                // (a scalar zero the compiler cannot fold into the divergent branch above: merged with it, `left` — and
+                //  the pool count after it — would count as divergent and move into vector registers)
+                asm volatile("s_mov_b64 %0, 0" : "=s"(left));
             }
-            unsigned long long send = __ballot(mine);
-            if (send) {
-                if (pool.pc + (uint32_t)__popcll(send) > 64u) {
-                    const unsigned long long head = __ballot(mine && rank_in(send) < 64u - pool.pc);
-                    if (head) pool_push(pool, head, klo, khi, word, base + idx, lane);
-                    pool_round(pool, ml.key, fn, pcut, lane);
-                    send &= ~head;
+            word |= (uint32_t)(int32_t)t;
+            if (lane_in(entry & ~left)) ml.key[base + idx] = word;
+            if (left) {
+                if (pool.pc + (uint32_t)__popcll(left) > 64u) {
+                    const unsigned long long head = __ballot(rank_in(left) < 64u - pool.pc) & left;   // its first 64 - pc
+                    if (head) pool_push(pool, head, key, word, base + idx);
+                    pool_round(pool, ml.key, K, pcut);
+                    left &= ~head;
                 }
-                pool_push(pool, send, klo, khi, word, base + idx, lane);
+                pool_push(pool, left, key, word, base + idx);
             }
         }
     }
-    while (pool.pc) pool_round(pool, ml.key, fn, 0u, lane);
+    while (pool.pc) pool_round(pool, ml.key, K, 0u);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -8,10 +8,16 @@ lanes) and rounds per 64 values for
     one wave, to the last one (the scheme until round 6: cut 10 + k_jump_left);
   * `pool`: a wave owns R regions; a round ends when <= cut lanes are live, the leftovers go to a 64-entry pool of the wave; a
     pool that would pass 64 is filled to 64 and run as a dense round until <= pcut are live; the pool is drained at the wave's end.
-Cost model: 17 instructions per wave-step (14 VALU + the exit test) and a flat 30 per round (load, prefetch, key store).  The flat
-30 does not price the hand-over as k_jump_bin does it (per push four ds_permute_b32, two mbcnt and the selects; two pushes and a
-compaction when the pool wraps), and the pool schemes run more rounds than `left`, so their instruction column is a lower bound:
-profiles/k1b_pool.md sets the measured SQ_INSTS_VALU beside it.
+Cost model, counted in k_jump_bin's gfx950 assembly (tests/test_k1b_lean.py compiles it): 17 instructions per wave-step (14
+VALU + the exit test) and, outside the step loop, in VALU instructions
+  * 11 per main round (index, prefetch address, t = 0, bucket -> word, store address, next value into the loop's registers),
+  * 10 per hand-over (two mbcnt, destination = select on the scalar mask, four conditional receives) + four ds_permute_b32,
+  * 12 per pool round (t from the word and back, store address, compaction's destination) + four ds_permute_b32,
+  *  5 more when the pool wraps (the mask of the chains that still fit; the round's key set aside and brought back).
+Scalar instructions and loads are not priced.  profiles/k1b_lean.md sets the measured counters beside the model: outside the
+loop, per 64 values, 38.4 VALU + 8.3 ds_permute_b32 = 46.7 measured at cut 24 / pcut 32 / R 4 against 44.5 modelled, and 54.8
+against 52.2 at cut 32 (the difference is the per-region set-up, which is not modelled).
+The `left` scheme is history (its second kernel is gone); its rounds are priced like main rounds and its hand-over like a push.
 
     python tools/jump_pool_sim.py [--keys 1300000] [--bins 194481] [--region 432]
 """
@@ -19,7 +25,8 @@ import argparse
 
 import numpy as np
 
-STEP_INSTR, ROUND_INSTR = 17, 30
+STEP_INSTR = 17
+ROUND_VALU, PUSH_VALU, POOL_ROUND_VALU, WRAP_VALU, PERMUTES = 11, 10, 12, 5, 4
 
 
 def chain_lengths(keys, n):
@@ -58,39 +65,48 @@ def rounds_of(region):
 
 
 def sim_left(regions, cut):
-    wsteps = rounds = 0
+    """-> (wave-steps, rounds, instructions outside the step loop)"""
+    wsteps = rounds = outside = 0
     for reg in regions:
         lo = []
         for r in rounds_of(reg):
             s, left = run_round(r, cut)
-            wsteps += s; rounds += 1
+            wsteps += s; rounds += 1; outside += ROUND_VALU
             room = 64 - sum(map(len, lo))
             if len(left) > room:                               # the hand-over area is full: finished in place
                 wsteps += int(left[room:].max()); left = left[:room]
+            if len(left):
+                outside += PUSH_VALU
             lo.append(left)
         lo = np.concatenate(lo) if lo else np.zeros(0, dtype=np.int32)
         if cut and len(lo):
-            wsteps += int(lo.max()); rounds += 1
-    return wsteps, rounds
+            wsteps += int(lo.max()); rounds += 1; outside += ROUND_VALU
+    return wsteps, rounds, outside
 
 
 def sim_pool(regions, cut, pcut, R):
-    wsteps = rounds = 0
+    """-> (wave-steps, rounds, instructions outside the step loop: VALU + ds_permute_b32)"""
+    wsteps = rounds = outside = 0
+    push, pool_round = PUSH_VALU + PERMUTES, POOL_ROUND_VALU + PERMUTES
     for w in range(0, len(regions), R):
         pool = np.zeros(0, dtype=np.int32)
         for reg in regions[w:w + R]:
             for r in rounds_of(reg):
                 s, left = run_round(r, cut)
-                wsteps += s; rounds += 1
+                wsteps += s; rounds += 1; outside += ROUND_VALU
+                if len(left) == 0:
+                    continue
                 if len(pool) + len(left) > 64:
                     room = 64 - len(pool)
+                    outside += WRAP_VALU + (push if room else 0) + pool_round
                     s, pool = run_round(np.concatenate([pool, left[:room]]), pcut)
                     wsteps += s; rounds += 1
                     left = left[room:]
+                outside += push
                 pool = np.concatenate([pool, left])
         if len(pool):
-            wsteps += int(pool.max()); rounds += 1
-    return wsteps, rounds
+            wsteps += int(pool.max()); rounds += 1; outside += pool_round
+    return wsteps, rounds, outside
 
 
 def main():
@@ -107,9 +123,9 @@ def main():
     regions = [L[i:i + a.region] for i in range(0, len(L), a.region)]
     per64 = len(L) / 64.0
 
-    def row(name, ws, rd):
-        print(f"{name:34s} {ws / per64:7.2f} {rd / per64:7.2f} {(ws * STEP_INSTR + rd * ROUND_INSTR) / per64:8.0f}")
-    print(f"{'scheme':34s} {'wsteps':>7s} {'rounds':>7s} {'instr':>8s}   (per 64 values)")
+    def row(name, ws, rd, outside):
+        print(f"{name:34s} {ws / per64:7.2f} {rd / per64:7.2f} {outside / per64:8.1f} {(ws * STEP_INSTR + outside) / per64:8.0f}")
+    print(f"{'scheme':34s} {'wsteps':>7s} {'rounds':>7s} {'outside':>8s} {'instr':>8s}   (per 64 values)")
     row("every round to its end (cut 0)", *sim_left(regions, 0))
     row("cut 10 + second kernel", *sim_left(regions, 10))
     for R in (1, 2, 4, 8):
