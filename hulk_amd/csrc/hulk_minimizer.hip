@@ -270,8 +270,10 @@ __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict
 // Eligible reads: no code-4 base, 1 <= w <= WM <= 16, k-mer positions <= 16*w, length <= 256,
 // <= 64 run starts.  Anything else is marked in the region's deferred mask and handled by k_minimizer_bin.
 //
-// LDS: 16 x tab[128] u32 (8,192 B) | 16 x pk[20] u32 | 16 x pkn[20] u32 (code-4 flags; 2,560 B) | per wave: raw ASCII of its 16
-// reads (4 x 3,136 B; PAIR 4 x 5,184) | 16 x cs[64] u64 (8,192 B) = 31,488 B (PAIR 39,680): 5 (4) workgroups per CU
+// LDS: 16 x tab[128] u32 (8,192 B) | 16 x pk[20] u32 | 16 x pkn[20] u32 (code-4 flags; 2,560 B: the per-trip staging of waves
+// whose reads do not fit the staged span) | per wave: its 16 reads as 2-bit codes, converted once in the prologue, and their
+// marks in the same layout (code stream + flag stream: 4 x 2 x 784 B; PAIR 4 x 2 x 1,296) | 16 x cs[64] u64 (8,192 B)
+// = 25,216 B (PAIR 29,312): the LDS admits 6 (5) workgroups per CU
 // ------------------------------------------------------------------------------------------
 #ifndef HULK_FAST_TAB
 #define HULK_FAST_TAB 128
@@ -282,8 +284,14 @@ __global__ __launch_bounds__(256) void k_minimizer_bin(const uint8_t *__restrict
 constexpr int FAST_TAB = HULK_FAST_TAB;       // set slots per 16-lane group (a pair of groups sharing a read uses both tables)
 constexpr int FAST_PAD = HULK_FAST_PAD;
 constexpr int FAST_CAND = 64;          // max run starts per read on the fast path
-constexpr int FAST_RAW = 3072 + 64;    // raw ASCII of the wave's 16 reads, staged once (bytes per wave)
-constexpr int FAST_RAW_PAIR = 5120 + 64;   // ... when two groups share a read (reads of up to ~300 bases)
+// The wave's 16 reads, staged once in the prologue: every lane converts FAST_NCH aligned 16-byte chunks of ASCII to one dword of
+// 2-bit codes each (base s of the staged span at bits 2(s & 15) of dword s >> 4: pk's layout, contiguous across chunks) and one
+// dword of marks (bit 2i: base i has code 4; bit 2i + 1: base i is a raw byte 0..3, which this kernel does not take).
+// Unchanged from the raw-ASCII staging these streams replace: 3 chunks per lane (3,072 bytes: 16 reads of up to 191 bases),
+// 5 with PAIR (5,120 bytes: up to 319 bases).  4 dwords of slack behind each stream for the 3-dword window reads.
+constexpr int FAST_NCH = 3, FAST_NCH_PAIR = 5;
+constexpr int FAST_STREAM = (64 * FAST_NCH + 4) * 4;             // bytes of ONE stream of one wave
+constexpr int FAST_STREAM_PAIR = (64 * FAST_NCH_PAIR + 4) * 4;
 // The per-read set holds 32-bit INDICES into the candidate list(s) of the read, not the 64-bit values: a candidate is
 // new iff its compare-and-swap (empty -> own index) finds the slot empty; an occupied slot names the candidate to compare with.
 constexpr uint32_t TAB_EMPTY32 = 0xFFFFFFFFu;
@@ -381,6 +389,27 @@ template <int KC> __device__ __forceinline__ uint64_t hash64_pack_kc(uint64_t ke
     return ((uint64_t)xh << 32) | xl;
 }
 
+// the n lowest bits (any n: the shifts of instances that never run a statement stay defined)
+__device__ constexpr uint64_t low_bits64(int n) { return n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << (n & 63)) - 1; }
+
+// x - C * one for one in {0, 1} and an inline constant C, as ONE v_mad_i32_i24 (the span fix-up of a read's first block)
+template <int C> __device__ __forceinline__ uint32_t sub_c_if(uint32_t x, uint32_t one) {
+    static_assert(C >= 1 && C <= 16, "-C must be an inline constant");
+    uint32_t d;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(d) : "v"(one), "n"(-C), "v"(x));
+    return d;
+}
+__device__ __forceinline__ uint32_t sub_small_if(uint32_t x, uint32_t one, int c) {   // c: a constant once the caller's loop is unrolled
+    switch (c) {
+    case 1: return sub_c_if<1>(x, one);   case 2: return sub_c_if<2>(x, one);   case 3: return sub_c_if<3>(x, one);
+    case 4: return sub_c_if<4>(x, one);   case 5: return sub_c_if<5>(x, one);   case 6: return sub_c_if<6>(x, one);
+    case 7: return sub_c_if<7>(x, one);   case 8: return sub_c_if<8>(x, one);   case 9: return sub_c_if<9>(x, one);
+    case 10: return sub_c_if<10>(x, one); case 11: return sub_c_if<11>(x, one); case 12: return sub_c_if<12>(x, one);
+    case 13: return sub_c_if<13>(x, one); case 14: return sub_c_if<14>(x, one); case 15: return sub_c_if<15>(x, one);
+    default: return x - one * (uint32_t)c;
+    }
+}
+
 // 64-bit unsigned minimum.  For k <= 27 every minimizer value (hash64 << 8 | span < 2^62) and every
 // 2k-bit k-mer is the bit pattern of a non-negative finite double, whose order is the integer order, so
 // v_min_f64 (denormals preserved, kernel descriptor float_denorm_mode_16_64 = 3) does in ONE instruction
@@ -430,7 +459,9 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
     const int32_t k = KC ? KC : (int32_t)P.k, w = WEQ ? WM : (int32_t)P.w;   // KC: k fixed at compile time (21 = the default)
     const uint64_t mask = (1ull << (2 * k)) - 1;
     const uint64_t shift = (uint64_t)(2 * (k - 1));
-    constexpr int RAWB = PAIR ? FAST_RAW_PAIR : FAST_RAW;          // raw ASCII of the wave's 16 reads (bytes per wave)
+    constexpr int NCH = PAIR ? FAST_NCH_PAIR : FAST_NCH;           // 16-byte chunks per lane staged in the prologue
+    constexpr int STW = (PAIR ? FAST_STREAM_PAIR : FAST_STREAM) / 4;   // dwords of one stream
+    constexpr uint32_t STCAP = 16u * 64u * NCH;                    // bases a stream holds
     constexpr int RPI = PAIR ? 2 : 4;                              // reads per iteration of a wave
     constexpr bool DX = KC != 0 && WEQ && 2 * (KC + WM - 1) <= 64;     // direct k-mer extraction (phase A)
     constexpr bool HP = FM && WEQ && KC >= 17 && KC <= 27;                    // hash + packing in explicit dword form
@@ -456,8 +487,9 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
     uint32_t *tab = (uint32_t *)(smem + FAST_PAD) + (size_t)(PAIR ? (grp & ~1) : grp) * FAST_TAB;   // the per-read set (candidate indices)
     uint32_t *pk32 = (uint32_t *)(smem + FAST_PAD + FAST_TAB_BYTES) + grp * 20;
     uint32_t *pkn32 = (uint32_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 16 * 20 * 4) + grp * 20;   // "code 4" flags, pk's layout
-    uint32_t *raw32 = (uint32_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 2 * 16 * 20 * 4) + (size_t)wid * (RAWB / 4);
-    uint64_t *cs = (uint64_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 2 * 16 * 20 * 4 + 4 * RAWB) + (size_t)grp * FAST_CAND;
+    uint32_t *code32 = (uint32_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 2 * 16 * 20 * 4) + (size_t)wid * (2 * STW);   // the wave's code stream
+    uint32_t *flag32 = code32 + STW;                                                                                 // ... and its flag stream
+    uint64_t *cs = (uint64_t *)(smem + FAST_PAD + FAST_TAB_BYTES + 2 * 16 * 20 * 4 + 4 * 2 * 4 * STW) + (size_t)grp * FAST_CAND;
     // what a set index addresses: the group's own candidates, or (PAIR) the pair's two neighbouring lists as one
     const uint64_t *csp = PAIR ? cs - (size_t)half * FAST_CAND : cs;
     {   // every group empties its OWN table (a pair's set spans both of its groups' tables)
@@ -482,8 +514,9 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
         atomicAdd(&st->total_len, (unsigned long long)(offsets[n_reads] - offsets[0]));
 
     // ---- wave prologue: the 17 offsets of the wave's reads in ONE round trip, then (when the reads
-    // fit) all their bases in ONE more: 16-byte chunks straight into LDS.  The per-iteration code then
-    // never waits on global memory (it used to cost 3 dependent round trips per iteration).
+    // fit) all their bases in ONE more: 16-byte chunks, converted to 2-bit codes + marks where they arrive and stored as the
+    // wave's code and flag streams.  The per-iteration code then never waits on global memory, converts nothing and — in a
+    // wave without a mark — votes on nothing: its window is one 3-dword read of the code stream.
     const uint32_t nrd = wave_first < n_reads ? (uint32_t)((n_reads - wave_first < FAST_READS_PER_WAVE) ? n_reads - wave_first : FAST_READS_PER_WAVE) : 0u;
     uint64_t myoff = 0;
     if ((uint32_t)lane <= nrd && nrd) myoff = offsets[wave_first + (uint32_t)lane];
@@ -493,12 +526,13 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
     const uint64_t span_hi = (uint64_t)__builtin_amdgcn_readlane((uint32_t)myoff, nrd_s) | (uint64_t)__builtin_amdgcn_readlane((uint32_t)(myoff >> 32), nrd_s) << 32;
     const uintptr_t raw_a0 = ((uintptr_t)bases + span_lo) & ~(uintptr_t)15;
     const uintptr_t raw_end = (uintptr_t)bases + span_hi;
-    const bool bulk = nrd && (raw_end - raw_a0) <= (uintptr_t)(RAWB - 64);
+    const bool bulk = nrd && (raw_end - raw_a0) <= (uintptr_t)STCAP;
+    const uint32_t delta = (uint32_t)(((uintptr_t)bases + span_lo) - raw_a0);      // 0..15: first base within the staged bytes
+    bool anymark = false;                                          // wave-uniform: some chunk of this wave carries a mark
     if (bulk) {
         // all chunks are requested before the first one is waited for: a chunk that is not wanted (past the wave's
         // reads) or not wholly inside the buffer re-reads the wave's first chunk instead of branching around the load
         const uintptr_t lim = (uintptr_t)bases + P.bases_bytes;
-        constexpr int NCH = PAIR ? 5 : 3;
         uint4 v[NCH]; bool whole[NCH];
         const bool first_ok = raw_a0 < lim;
 #pragma unroll
@@ -507,13 +541,65 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
             whole[x] = a < raw_end + 16 && a < lim;       // (an aligned 16-byte chunk with a byte inside the buffer lies in its last page)
             v[x] = first_ok ? *(const uint4 *)(whole[x] ? a : raw_a0) : make_uint4(0, 0, 0, 0);
         }
+        // ASCII -> 2-bit, four bases per dword, no table: fold the case, code = (c >> 1 ^ c >> 2) & 3 (A 0, C 1, G 2, T 3), and
+        // prove it by mapping the codes back to letters with one v_perm_b32: any byte that does not come back (N, U, 0..3,
+        // anything else) is looked at below.  (c * 0x01041040) >> 24 gathers the four codes of a dword into one byte.
+        // A chunk that was not loaded (behind the wave's reads or behind the buffer) is stored as zeros: every dword of both
+        // streams is written, so what a lane reads past its read's end is the next read's bases or zero, never stale LDS.
+        const uint32_t endoff = (uint32_t)(raw_end - raw_a0);  // the wave's own bytes are [delta, endoff) of the staged span
+        bool marked = false;
 #pragma unroll
         for (int x = 0; x < NCH; x++) {
-            const uintptr_t a = raw_a0 + 16u * (uint32_t)(lane + 64 * x);
-            if (whole[x]) *(uint4 *)(raw32 + 4 * (lane + 64 * x)) = v[x];
-            else if (a < raw_end + 16)                          // the chunk lies behind the buffer
-                for (int y = 0; y < 4; y++) raw32[4 * (lane + 64 * x) + y] = 0u;
+            const uint32_t d[4] = {v[x].x, v[x].y, v[x].z, v[x].w};
+            uint32_t pack = 0, fpack = 0, bad = 0;
+#pragma unroll
+            for (int y = 0; y < 4; y++) {
+                const uint32_t up = d[y] & 0xDFDFDFDFu;
+                const uint32_t e = up >> 1;
+                const uint32_t c = (e ^ (e >> 1)) & 0x03030303u;
+                bad |= __builtin_amdgcn_perm(0u, 0x54474341u, c) ^ up;
+                pack |= ((c * 0x01041040u) >> 24) << (8 * y);
+            }
+            if (!whole[x]) { pack = 0; bad = 0; }
+            if (bad != 0) {                                    // rare: look at the bytes one by one
+                // Only the wave's own bytes count.  Behind endoff lies the next wave's first read, a buffer's padding or —
+                // behind a call's last read — whatever follows the reads (zero padding must not mark anything); in front of
+                // delta lies the previous wave's last read.
+                const int32_t c0 = 16 * (lane + 64 * x);
+                const int32_t lo = (int32_t)delta - c0, hi = (int32_t)endoff - c0;   // bytes [lo, hi) of the chunk count
+#pragma unroll
+                for (int y = 0; y < 4; y++) {
+                    const uint32_t by = d[y], up = by & 0xDFDFDFDFu, e = up >> 1, c = (e ^ (e >> 1)) & 0x03030303u;
+                    const int nl = lo - 4 * y, nh = hi - 4 * y;
+                    const uint32_t ml = nl >= 4 ? ~0u : nl <= 0 ? 0u : (1u << (8 * nl)) - 1u;
+                    const uint32_t mh = nh >= 4 ? ~0u : nh <= 0 ? 0u : (1u << (8 * nh)) - 1u;
+                    const uint32_t mm = (__builtin_amdgcn_perm(0u, 0x54474341u, c) ^ up) & mh & ~ml;   // bytes that did not come back
+                    // 0x80 per byte that did not come back.  seq_nt4_table (minimizer.go:23-40) gives U / u the code of
+                    // T — which the formula already produced — the raw bytes 0..3 their own value (not taken here: the
+                    // read is deferred: "hard", an odd bit), and EVERY other byte code 4: N, the IUPAC letters, anything else.
+                    // Those get a flag (an even bit), and code 0 is what is stored for them (the formula gives 0 for N / n
+                    // only: cleared below).  Instances without the N variant defer on every such byte: all marks are hard.
+                    const uint32_t nz = (((mm & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | mm) & 0x80808080u;
+                    uint32_t hard4 = nz >> 7, soft4 = 0;                                 // bits 0, 8, 16, 24
+                    if (NV) {
+                        const uint32_t tU = up ^ 0x55555555u, t3 = by & 0xFCFCFCFCu;
+                        const uint32_t isU = ~(((tU & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | tU | 0x7F7F7F7Fu);
+                        const uint32_t is03 = ~(((t3 & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t3 | 0x7F7F7F7Fu);
+                        hard4 = (nz & is03) >> 7;
+                        soft4 = (nz & ~isU & ~is03) >> 7;
+                    }
+                    const uint32_t b4 = soft4 | (hard4 << 1);                            // bits 0-1, 8-9, 16-17, 24-25
+                    const uint32_t fl = (b4 & 3u) | ((b4 >> 6) & 12u) | ((b4 >> 12) & 48u) | ((b4 >> 18) & 192u);   // -> bits 0-1, 2-3, 4-5, 6-7
+                    fpack |= fl << (8 * y);
+                }
+                pack &= ~((fpack & 0x55555555u) * 3u);
+            }
+            code32[lane + 64 * x] = pack;
+            flag32[lane + 64 * x] = fpack;
+            marked = marked || fpack != 0;
         }
+        if (lane < 4) { code32[64 * NCH + lane] = 0u; flag32[64 * NCH + lane] = 0u; }   // slack for the 3-dword window reads
+        anymark = __ballot(marked) != 0ull;
     }
     wave_sync();
 
@@ -535,14 +621,17 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
     }
 
     const bool crosses = P.interval && rem0 + FAST_READS_PER_WAVE > P.interval;
-    // Per-read bookkeeping in 32 bits: offsets relative to the wave's first base.  (A wave whose 16 reads span
-    // 2 GB or more hands all of them to the generic kernel, which works on the 64-bit offsets.)
+    // Per-read bookkeeping in 32 bits: offsets relative to raw_a0, the aligned start of the wave's staged span (the wave's
+    // first base is at delta = 0..15), so that a read's offset is its base position in the code stream as it stands.  (A wave whose 16 reads span
+    // 2 GB or more hands all of them to the generic kernel, which works on the 64-bit offsets: behind the main loop.)
     const bool wide = nrd && (span_hi - span_lo) >= 0x7fffffffull;
-    const uint32_t myrel = (uint32_t)(myoff - span_lo);
-    const uint32_t delta = (uint32_t)(((uintptr_t)bases + span_lo) - raw_a0);      // 0..15: first base within the staged bytes
+    const uint32_t myrel = (uint32_t)(myoff - span_lo) + delta;
     const bool lastwave = wave_first + nrd == n_reads;
-    for (int it = 0; it < FAST_READS_PER_WAVE / RPI; it++) {
-        if ((uint32_t)(RPI * it) >= nrd) break;
+    // One trip of the main loop, compiled twice: for a wave whose window comes from its code stream (BULK) and for one that
+    // stages per trip from global memory — rare, and with its pointers, limits and conversion constants out of the way it
+    // costs the common loop no scalar registers.
+    auto trip = [&](auto bulk_tag, const int it) __attribute__((always_inline)) {
+        constexpr bool BULK = decltype(bulk_tag)::value;
         const uint32_t idx = (uint32_t)(RPI * it + sub);       // read of the wave
         // gl and half once more, opaque to the optimiser, for the loop's per-lane PREDICATES (gl == 0, half, ...): computed
         // from gl and half themselves each of them is loop-invariant, is hoisted, and then holds a 64-bit lane mask — two
@@ -562,8 +651,7 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
         }
         bool defer = false;
         if (act) {
-            if (wide) defer = true;
-            else if (L < 1 || L < w + k - 1) { if (gl == 0) set_error(st, L < 1 ? -3 : -4); act = false; }   // (one atomic's operands to keep around, not two)
+            if (L < 1 || L < w + k - 1) { if (gl == 0) set_error(st, L < 1 ? -3 : -4); act = false; }   // (one atomic's operands to keep around, not two)
             else {
                 npos = L - k + 1;
                 if (npos > (PAIR ? 2 * 16 * w - (w - 1) : 16 * w) || L > (PAIR ? 512 : 256)) defer = true;
@@ -572,24 +660,61 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
         // this group's part of the read: bases from posoff on, k-mer positions posoff .. posoff + 16w - 1
         const int32_t Lg = L - posoff;
         const int32_t nposg = npos - posoff < 0 ? 0 : (npos - posoff > 16 * w ? 16 * w : npos - posoff);
-        if (dbg & 64u) { sink += a32 + (uint32_t)npos + hslot; continue; }   // ablation: per-iteration bookkeeping only
-        // ---- stage 16 bases per lane: ASCII -> 2-bit pack (one dword per lane), detect code 4
+        if (dbg & 64u) { sink += a32 + (uint32_t)npos + hslot; return; }   // ablation: per-iteration bookkeeping only
+        // ---- the window's source.  Bulk: the wave's code stream, at the block's first base; the flag stream is looked at only
+        // in a wave with a marked chunk.  Otherwise: stage 16 bases per lane from global memory (ASCII -> 2-bit pack, one
+        // dword per lane, detect code 4), as before the streams existed.
+        const int32_t p0 = gl * w;                              // first position of the lane's block, within the group
+        const int32_t ap0 = posoff + p0;                        // ... within the read
         bool sawN = false, softN = false;                      // sawN: a byte this kernel cannot take; softN (NV): an `N`
-        if (act && !defer) {
+        // NV: Xn = the code-4 flags of bases p0-1, p0, p0+1, ... at bits 0, 2, 4, ... (p0 - 1 may be the partner group's)
+        uint64_t Xn = 0; uint32_t nn = 0;
+        const uint32_t *cw = pk32, *fw = pkn32;                 // code and flag words of the window, and its first base in them
+        uint32_t cb = (uint32_t)p0;
+        // 64 bits of a 2-bit stream from base `at` on (one 3-dword funnel shift)
+        auto win64 = [](const uint32_t *base, uint32_t at) -> uint64_t {
+            const uint32_t bo = 2u * at, d = bo >> 5, o = bo & 31u;
+            const uint64_t lo = (uint64_t)base[d] | ((uint64_t)base[d + 1] << 32);
+            return o ? (lo >> o) | ((uint64_t)base[d + 2] << (64 - o)) : lo;
+        };
+        auto win32 = [](const uint32_t *base, uint32_t at) -> uint32_t {
+            const uint32_t bo = 2u * at, d = bo >> 5, o = bo & 31u;
+            return (uint32_t)(((uint64_t)base[d] | ((uint64_t)base[d + 1] << 32)) >> o);
+        };
+        if (BULK) {
+            // (a lane without a position of its own may stand behind the staged span: it reads the stream's last dwords)
+            cw = code32; fw = flag32;
+            cb = a32 + (uint32_t)ap0; cb = cb < STCAP ? cb : STCAP;
+            if (anymark) {
+                // The window's marks: bases ap0 - 1 (the base in front of a read's first block belongs to the previous read:
+                // it reads as zero) .. the block's last base.  Marks of the next read's first bases may be seen too: that read
+                // then takes the N variant or is deferred without need, which is exact.
+                Xn = win64(fw, ap0 ? cb - 1u : cb);
+                if (ap0 == 0) Xn <<= 2;
+                uint64_t seen;
+                if (DX) {
+                    constexpr int NBW = KC + WM - 1;
+                    Xn &= low_bits64(2 * (NBW + 1));
+                    seen = Xn;
+                } else {
+                    const uint32_t at = cb + (uint32_t)k;
+                    nn = win32(fw, at < STCAP ? at : STCAP);
+                    seen = Xn | nn;
+                }
+                const bool counts = act && !defer && p0 < nposg;
+                sawN = counts && (seen & 0xAAAAAAAAAAAAAAAAull) != 0;
+                softN = NV && counts && (seen & 0x5555555555555555ull) != 0;
+                Xn &= 0x5555555555555555ull;
+            }
+        } else if (act && !defer) {
             const int32_t p = 16 * gl;
             uint32_t pack = 0, npack = 0;
             if (p < Lg) {
-                const uint32_t ro = a32 + (uint32_t)posoff + (uint32_t)p;     // first of the lane's bytes, from the wave's first base
+                const uint32_t ro = a32 + (uint32_t)posoff + (uint32_t)p;     // first of the lane's bytes, from raw_a0
                 unsigned sh;
                 uint32_t d[5];
-                if (bulk) {
-                    const uint32_t lo = ro + delta;                // raw_a0 is 16-byte aligned
-                    const uint32_t *src = raw32 + (lo >> 2);
-                    sh = (lo & 3u) * 8u;
-#pragma unroll
-                    for (int x = 0; x < 5; x++) d[x] = src[x];
-                } else {
-                    const uintptr_t addr = (uintptr_t)bases + span_lo + ro;
+                {
+                    const uintptr_t addr = raw_a0 + ro;
                     const uintptr_t al = addr & ~(uintptr_t)3, end = (uintptr_t)bases + P.bases_bytes;
                     sh = (unsigned)(addr & 3) * 8;
 #pragma unroll
@@ -647,19 +772,19 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
             if (glq < 4) pk32[16 + gl] = 0;                    // slack for 3-dword window reads
             if (NV) { pkn32[gl] = npack; if (glq < 4) pkn32[16 + gl] = 0; }
         }
-        {
+        // (wave-uniform) the votes exist only where something can be marked: a wave staged per trip, or one with a marked chunk
+        const bool voting = !BULK || anymark;
+        if (voting) {
             // a byte the kernel cannot take anywhere in the read defers it as a whole (both groups of a pair must agree)
             const uint32_t gN = PAIR ? (uint32_t)(__ballot(sawN) >> (lane & 32)) : (uint32_t)(__ballot(sawN) >> gsh) & 0xffffu;
             if (gN) defer = true;
         }
         // NV: does any read of this iteration carry an N?  (wave-uniform; reads deferred for another reason do not count)
-        const bool waveN = NV && __ballot(softN && !defer) != 0ull;
-        wave_sync();
-        if (dbg & 32u) { sink += pk32[gl]; wave_sync(); continue; }      // ablation: staging only
+        const bool waveN = NV && voting && __ballot(softN && !defer) != 0ull;
+        if (!BULK) wave_sync();
+        if (dbg & 32u) { sink += cw[gl]; wave_sync(); return; }      // ablation: staging only
 
         // ---- phase A: rolling k-mers over the own block (registers)
-        const int32_t p0 = gl * w;                              // first position of the lane's block, within the group
-        const int32_t ap0 = posoff + p0;                        // ... within the read
         const bool mine = act && !defer && p0 < nposg;
         uint32_t validbits = 0;
         uint64_t X[WM];
@@ -675,11 +800,10 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
             if (mine) validbits = (1u << (nposg - p0 < w ? nposg - p0 : w)) - 1u;
             const int32_t span0 = ap0 + k - 1 - w + 2;
             uint64_t f = 0, r = 0;
-            uint32_t nb = 0, nn = 0;                            // next <=15 bases, 2 bits each; their code-4 flags (N variant)
+            uint32_t nb = 0;                                    // next <=15 bases, 2 bits each (nn: their code-4 flags, N variant)
             uint64_t Bb = 0, Cl = 0;
-            // NV: Xn = the code-4 flags of bases p0-1, p0, p0+1, ... at bits 0, 2, 4, ... (p0 - 1 may be the partner group's)
-            uint64_t Xn = 0, Hb = 0;
-            if (NV && waveN) {
+            uint64_t Hb = 0;
+            if (NV && waveN && !BULK) {
                 const uint32_t bo = 2u * (uint32_t)p0, nbo = p0 > 0 ? bo - 2u : 0u, d = nbo >> 5, o = nbo & 31u;
                 const uint64_t lo = (uint64_t)pkn32[d] | ((uint64_t)pkn32[d + 1] << 32);
                 Xn = o ? (lo >> o) | ((uint64_t)pkn32[d + 2] << (64 - o)) : lo;
@@ -695,25 +819,21 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
                 // the block's w+k-1 bases fit one 64-bit window: every k-mer of the block is a shift + mask of the
                 // window in the forward (first base on top: Bb) or the complemented (first base at the bottom: Cl)
                 // layout, instead of the rolling update per base
-                constexpr int NBW = KC + WM - 1;
-                const uint32_t bo = 2u * (uint32_t)p0, d = bo >> 5, o = bo & 31u;
-                const uint64_t lo = (uint64_t)pk32[d] | ((uint64_t)pk32[d + 1] << 32);
-                uint64_t Wl = o ? (lo >> o) | ((uint64_t)pk32[d + 2] << (64 - o)) : lo;
-                if (NBW < 32) Wl &= (1ull << (2 * NBW)) - 1;
+                constexpr int NBW = DX ? KC + WM - 1 : 1;
+                uint64_t Wl = win64(cw, cb);
+                Wl &= low_bits64(2 * NBW);
                 const uint64_t rv = __brevll(Wl) >> (64 - 2 * NBW);
                 Bb = ((rv >> 1) & 0x5555555555555555ull) | ((rv & 0x5555555555555555ull) << 1);
                 Cl = ~Wl;
             } else {
                 {
-                    const uint32_t bo = 2u * (uint32_t)p0, d = bo >> 5, o = bo & 31u;
-                    const uint64_t lo = (uint64_t)pk32[d] | ((uint64_t)pk32[d + 1] << 32);
-                    uint64_t W = o ? (lo >> o) | ((uint64_t)pk32[d + 2] << (64 - o)) : lo;
+                    uint64_t W = win64(cw, cb);
                     W &= mask;
                     r = (~W) & mask;
                     if (NV && waveN) {
                         // the block's first k-mer in closed form (as k_minimizer_bin): f's pairs |= N(p+1) but the last base's,
                         // r's pairs |= N(p-1) and bit 2k = N(last base); the positions behind it roll the literal recurrence
-                        const uint64_t X0 = (2 * k + 2 < 64) ? (Xn & ((1ull << (2 * k + 2)) - 1)) : Xn;
+                        const uint64_t X0 = Xn & low_bits64(2 * k + 2);
                         W |= (X0 >> 4) & (mask >> 2);
                         r |= X0 & ((mask << 1) | 1ull);
                     }
@@ -721,31 +841,30 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
                     f = ((rev >> 1) & 0x5555555555555555ull) | ((rev & 0x5555555555555555ull) << 1);
                 }
                 {
-                    const uint32_t bo = 2u * (uint32_t)(p0 + k), d = bo >> 5, o = bo & 31u;
-                    const uint64_t lo = (uint64_t)pk32[d] | ((uint64_t)pk32[d + 1] << 32);
-                    nb = (uint32_t)(lo >> o);
-                    if (NV && waveN) {
-                        const uint64_t ln = (uint64_t)pkn32[d] | ((uint64_t)pkn32[d + 1] << 32);
-                        nn = (uint32_t)(ln >> o);
-                    }
+                    uint32_t at = cb + (uint32_t)k;
+                    if (BULK) at = at < STCAP ? at : STCAP;
+                    nb = win32(cw, at);
+                    if (NV && waveN && !BULK) nn = win32(fw, at);
                 }
             }
             // NV, one-window form: Xn cut to the window (for r, bit 2k included); Hb = the flags of bases p0+1 .. in the forward
             // (first base on top) layout of Bb, one pair down (for f)
             if (NV && DX && waveN) {
-                constexpr int NBW = KC + WM - 1;
-                Xn &= (NBW + 1 < 32) ? ((1ull << (2 * (NBW + 1))) - 1) : ~0ull;
-                const uint64_t Fn = (Xn >> 4) & ((1ull << (2 * (NBW - 1))) - 1);      // pair u: N(p0 + u + 1), u < NBW - 1
+                constexpr int NBW = DX ? KC + WM - 1 : 1;
+                Xn &= low_bits64(2 * (NBW + 1));
+                const uint64_t Fn = (Xn >> 4) & low_bits64(2 * (NBW - 1));      // pair u: N(p0 + u + 1), u < NBW - 1
                 const uint64_t rv = __brevll(Fn) >> (64 - 2 * NBW);
                 Hb = ((rv >> 1) & 0x5555555555555555ull) | ((rv & 0x5555555555555555ull) << 1);
             }
             // span = min(span0 + t, k) is k everywhere but in the read's first block (ap0 == 0: k - (w-1-t)), since every
-            // other block starts at ap0 >= w.  With k and w fixed, one select between two constants per position — computed
-            // here, behind an opaque copy of ap0: left visible, the nine loop-invariant spans are hoisted out of the main
-            // loop and occupy nine VGPRs across all of it.
+            // other block starts at ap0 >= w.  With k and w fixed every position is packed with the constant k, and the first
+            // block's positions t < w-1 are corrected on the low dword: x -= w-1-t (no borrow: the low bits hold k >= 17 and
+            // w-1-t <= 15), in front of the replacement by "no value".  first_block is computed here, behind an opaque copy of
+            // ap0: left visible it is hoisted out of the main loop and held across all of it.
             uint32_t ap0_now = (uint32_t)ap0;
             if (KC != 0 && WEQ) asm volatile("" : "+v"(ap0_now));
             const bool first_block = ap0_now == 0u;
+            const uint32_t fb1 = first_block ? 1u : 0u;
             auto phaseA = [&](auto nvx_tag) {
             constexpr bool NVX = decltype(nvx_tag)::value;
 #pragma unroll
@@ -783,12 +902,13 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
                     //  bit pattern is a signalling NaN, which v_min_f64 does not pass through — integer minimum there)
                     const uint64_t canon = (NVX && k >= 31) ? (f < r ? f : r) : umin64<true>(f, r);
                     int32_t span;
-                    if (KC != 0 && WEQ) span = first_block ? k - (w - 1 - t) : k;
+                    if (KC != 0 && WEQ) span = k;
                     else { span = span0 + t; if (span >= k) span = k; }
                     uint64_t x;
                     if (HP && !(dbg & 16u)) x = hash64_pack_kc<HP ? KC : 21>(canon, (uint32_t)span);
                     else if (KEY5) x = (hash64(canon, mask) & 0x00FFFFFFFFFFFFFFull) << 5 | (uint64_t)(uint32_t)span;
                     else x = ((dbg & 16u) ? canon * 0x9E3779B97F4A7C15ull : hash64_fm<FM>(canon, mask)) << 8 | (uint64_t)(int64_t)span;
+                    if (KC != 0 && WEQ && t < w - 1) x = (x & 0xffffffff00000000ull) | sub_small_if((uint32_t)x, fb1, w - 1 - t);
                     // f == r (a k-mer that is its own reverse complement: even k only — or any k once code-4 flags are in
                     // play) is skipped by the reference: the position neither reports nor takes part in a window
                     if ((NVX || !(k & 1)) && f == r) { x = XN; validbits &= ~(1u << t); }
@@ -802,7 +922,7 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
 #pragma unroll
             for (int t = 0; t < WM; t++) sink += (uint32_t)X[t];
             wave_sync();
-            continue;
+            return;
         }
 
         // ---- phase B: windowed minimum m(pos) = min(prev block's suffix-min, own prefix-min)
@@ -946,7 +1066,12 @@ __global__ __launch_bounds__(256, (fast_blocks_per_cu<WM, DBG, WEQ, KC>())) void
         for (int rnd = 0; rnd < FAST_CAND / 16; rnd++)
             if ((newmask >> rnd) & 1u) tab[myslot[rnd]] = TAB_EMPTY32;
         wave_sync();
-    }
+    };
+    if (bulk) {
+        for (int it = 0; it < FAST_READS_PER_WAVE / RPI && (uint32_t)(RPI * it) < nrd; it++) trip(std::true_type{}, it);
+    } else if (!wide) {
+        for (int it = 0; it < FAST_READS_PER_WAVE / RPI && (uint32_t)(RPI * it) < nrd; it++) trip(std::false_type{}, it);
+    } else dmask = (1u << nrd_s) - 1u;                             // all of its reads (bit = read of the wave)
     if (lane == 0 && wave_first < n_reads) { ml.cnt[region] = wcount; ml.dmask[region] = dmask; }
     if (dbg && sink == 0xdeadbeefu) xl[0] = sink;
     __shared__ unsigned long long blk_nmin[4];
@@ -1265,18 +1390,19 @@ hipError_t launch_minimizer_bin(hipStream_t s, const uint8_t *d_bases, const uin
 }
 
 constexpr size_t fast_lds_bytes(bool pair) {
-    return FAST_PAD + (size_t)FAST_TAB_BYTES + 2 * 16 * 20 * 4 + 4 * (size_t)(pair ? FAST_RAW_PAIR : FAST_RAW) + 16 * (size_t)FAST_CAND * 8;
+    return FAST_PAD + (size_t)FAST_TAB_BYTES + 2 * 16 * 20 * 4 + 4 * 2 * (size_t)(pair ? FAST_STREAM_PAIR : FAST_STREAM) + 16 * (size_t)FAST_CAND * 8;
 }
 // Workgroups per CU by LDS: the dynamic request + the kernel's 32 B of static LDS (blk_nmin), rounded up to the allocation
-// granule (1280 B on gfx950: 160 KB / 128), against the CU's 160 KB.  One read per group: 31,488 + 32 -> 32,000 B, 5 per CU —
-// what fast_blocks_per_cu() budgets the registers of the default instances for.  PAIR: 39,680 + 32 -> 40,960 B, 4 per CU
-// (its registers are budgeted for 5 all the same: the LDS is the limit there until its raw-read staging shrinks).
+// granule (1280 B on gfx950: 160 KB / 128), against the CU's 160 KB.  One read per group: 25,216 + 32 -> 25,600 B, 6 per CU
+// (fast_blocks_per_cu() budgets the registers of the default instances for 5: an instance at <= 80 VGPRs is resident at 6).
+// PAIR: 29,312 + 32 -> 29,440 B, 5 per CU — what its registers are budgeted for (it ran at 4 while the reads were staged as
+// raw ASCII: 40,960 B).
 constexpr size_t FAST_LDS_GRANULE = 1280, FAST_LDS_STATIC = 32, CU_LDS_BYTES = 160 * 1024;
 constexpr size_t fast_lds_alloc(bool pair) { return (fast_lds_bytes(pair) + FAST_LDS_STATIC + FAST_LDS_GRANULE - 1) / FAST_LDS_GRANULE * FAST_LDS_GRANULE; }
 #if HULK_FAST_PAD == 0 && HULK_FAST_TAB == 128
 static_assert(fast_blocks_per_cu<9, false, true, 21>() == 5 && fast_blocks_per_cu<9, false, true, 31>() == 5, "the default instances are built for 5 workgroups per CU");
-static_assert(5 * fast_lds_alloc(false) <= CU_LDS_BYTES, "k_minimizer_fast: the LDS no longer admits the 5 workgroups per CU its registers are budgeted for");
-static_assert(4 * fast_lds_alloc(true) <= CU_LDS_BYTES, "k_minimizer_fast (PAIR): the LDS no longer admits 4 workgroups per CU");
+static_assert(6 * fast_lds_alloc(false) <= CU_LDS_BYTES, "k_minimizer_fast: the LDS no longer admits 6 workgroups per CU (its registers are budgeted for 5)");
+static_assert(5 * fast_lds_alloc(true) <= CU_LDS_BYTES, "k_minimizer_fast (PAIR): the LDS no longer admits the 5 workgroups per CU its registers are budgeted for");
 #endif
 size_t minimizer_fast_lds(uint32_t, bool pair) { return fast_lds_bytes(pair); }
 

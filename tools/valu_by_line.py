@@ -23,6 +23,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("asm"); ap.add_argument("kernel"); ap.add_argument("source")
     ap.add_argument("--loop", action="store_true"); ap.add_argument("--min", type=int, default=1)
+    ap.add_argument("--loop-at", type=int, default=0, help="the loop closed by the backward CONDITIONAL branch attributed to this source line (the "
+                    "`for` statement): its straight-line body, without the rare blocks the compiler places behind the kernel's end.  "
+                    "k_minimizer_fast holds its main loop twice (code-stream form and per-trip staging form): one `for` line each")
     ap.add_argument("--reads-per-trip", type=float, default=0.0)
     ap.add_argument("--skip-lines", default="")
     ap.add_argument("--lines", default="", help="a-b: only instructions attributed to these source lines (e.g. the body of the main loop); "
@@ -72,6 +75,16 @@ def main():
                 if t is not None and t < i and i - t > best[0]:
                     best = (i - t, t, i + 1)
         lo, hi = best[1], best[2]
+    if a.loop_at:
+        hits = []
+        for i, (mn, ops, (f, ln)) in enumerate(ins):
+            if mn.startswith("s_cbranch") and f in want and ln == a.loop_at:
+                t = labels.get(ops.strip())
+                if t is not None and t < i:
+                    hits.append((i - t, t, i + 1))
+        if not hits:
+            sys.exit(f"no backward conditional branch at line {a.loop_at}")
+        lo, hi = max(hits)[1], max(hits)[2]
     keep = None
     if a.lines:
         lo_l, _, hi_l = a.lines.partition("-")
@@ -93,7 +106,7 @@ def main():
             r["vmem"] += 1; tot["vmem"] += 1
     rpt = a.reads_per_trip
     print(f"# {a.title or a.kernel}\n")
-    print(f"`{a.kernel}` — {'main loop' if a.loop else 'whole kernel'}: **{tot['valu']} VALU** wave-instructions ({tot['cyc']:.0f} issue cycles at the "
+    print(f"`{a.kernel}` — {'main loop' if a.loop or a.loop_at else 'whole kernel'}: **{tot['valu']} VALU** wave-instructions ({tot['cyc']:.0f} issue cycles at the "
           f"measured costs, mean {tot['cyc'] / max(tot['valu'], 1):.2f}), {tot['salu']} SALU, {tot['lds']} LDS, {tot['vmem']} VMEM"
           + (f"; per read (/{rpt:g}): **{tot['valu'] / rpt:.1f} VALU**, {tot['cyc'] / rpt:.0f} cycles" if rpt else "") + "\n")
     print("| line | VALU | cycles | " + ("VALU / read | " if rpt else "") + "SALU | LDS | VMEM | source |")
