@@ -35,6 +35,7 @@ HULK_PANEL_MAX = 65536
 HULK_SEARCH_MAX_K = 64          # hulk_search: hits per query
 HULK_SEARCH_SELF = 1            # ... the database is the query set itself, the pair (i, i) left out
 HULK_CLUSTER_MAX_N = 2097088     # hulk_cluster: sketches in one set
+HULK_LINKS_UPPER = 1            # hulk_links: only the edges (i, j) with j > i
 HULK_MINHASH_MAX_SKETCH = 4096
 HULK_MAX_BINS = 1 << 20
 HULK_INJECT_NONE, HULK_INJECT_STALE_SEAL, HULK_INJECT_STALE_STAGE = 0, 1, 2
@@ -56,6 +57,8 @@ ABI_SYMBOLS = (
     "hulk_set_panel", "hulk_get_snapshot_distances", "hulk_set_snapshot_panel_callback", "hulk_panel_distances",
     "hulk_search", "hulk_search_files", "hulk_cluster", "hulk_cluster_files",
     "hulk_dendrogram", "hulk_dendrogram_files",
+    "hulk_links", "hulk_links_files", "hulk_link_list_info", "hulk_link_list_row_start", "hulk_link_list_cols",
+    "hulk_link_list_distances", "hulk_link_list_free",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -133,6 +136,17 @@ class ClusterOpts(ctypes.Structure):
 class ClusterStats(ctypes.Structure):
     _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_link", ctypes.c_double), ("kernel_ms_flatten", ctypes.c_double),
                 ("links", ctypes.c_uint64), ("bands", ctypes.c_uint32), ("clusters", ctypes.c_uint32)]
+
+
+class LinksOpts(ctypes.Structure):
+    """hulk_links_opts (include/hulk_hip.h)."""
+    _fields_ = [("metric", ctypes.c_int), ("max_distance", ctypes.c_double), ("band_rows", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("max_edges", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class LinksStats(ctypes.Structure):
+    _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_count", ctypes.c_double), ("kernel_ms_fill", ctypes.c_double),
+                ("edges", ctypes.c_uint64), ("bands", ctypes.c_uint32), ("max_degree", ctypes.c_uint32)]
 
 
 class DendrogramOpts(ctypes.Structure):
@@ -345,6 +359,16 @@ def load():
     L.hulk_cluster_files.restype = ctypes.c_int
     L.hulk_cluster_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, dbl, u32, ctypes.c_char_p, vp,
                                      ctypes.POINTER(ClusterStats), ctypes.c_char_p, u64]
+    L.hulk_links.restype = ctypes.c_int
+    L.hulk_links.argtypes = [ctypes.c_int, vp, vp, u32, u32, ctypes.POINTER(LinksOpts), ctypes.POINTER(vp), ctypes.POINTER(LinksStats)]
+    L.hulk_links_files.restype = ctypes.c_int
+    L.hulk_links_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, dbl, u32, u64, u32, ctypes.c_char_p,
+                                   ctypes.POINTER(vp), ctypes.POINTER(LinksStats), ctypes.c_char_p, u64]
+    L.hulk_link_list_info.restype = ctypes.c_int
+    L.hulk_link_list_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u64)]
+    for name in ("hulk_link_list_row_start", "hulk_link_list_cols", "hulk_link_list_distances"):
+        getattr(L, name).restype = vp; getattr(L, name).argtypes = [vp]
+    L.hulk_link_list_free.restype = None; L.hulk_link_list_free.argtypes = [vp]
     L.hulk_dendrogram.restype = ctypes.c_int
     L.hulk_dendrogram.argtypes = [ctypes.c_int, vp, vp, u32, u32, ctypes.POINTER(DendrogramOpts), vp, vp, vp, vp, ctypes.POINTER(DendrogramStats)]
     L.hulk_dendrogram_files.restype = ctypes.c_int

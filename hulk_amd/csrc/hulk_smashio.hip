@@ -755,6 +755,71 @@ int hulk_cluster_files(int device, const char *const *paths, uint32_t n_paths, u
     return HULK_OK;
 }
 
+// "sketch,neighbour,distance,similarity" of hulk_links_files: one line per edge in CSR order, the rows formatted in parallel
+static bool write_links_csv(const hulk_sketch_set &set, const hulk_link_list *list, uint32_t threads, const char *csv_path, std::string &err) {
+    const uint32_t n = (uint32_t)set.files.size();
+    const uint64_t *row_start = hulk_link_list_row_start(list);
+    const uint32_t *col = hulk_link_list_cols(list);
+    const double *dist = hulk_link_list_distances(list);
+    std::vector<std::string> rows((size_t)n + 1);
+    rows[0] = "sketch,neighbour,distance,similarity\n";
+    parallel_for(n, pick_threads(threads, n), [&](size_t i) {
+        std::string &r = rows[i + 1];
+        std::string subject;
+        csv_field(subject, set.files[i].path);
+        for (uint64_t e = row_start[i]; e < row_start[i + 1]; e++) {
+            char tmp[40];
+            snprintf(tmp, sizeof tmp, "%.17g", dist[e]);
+            r += subject; r += ',';
+            csv_field(r, set.files[col[e]].path); r += ','; r += tmp; r += ',';
+            format_f2(r, 100 - (dist[e] * 100));                    // cmd/smash.go:217
+            r += '\n';
+        }
+    });
+    return write_all(csv_path, rows, err);
+}
+
+int hulk_links_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
+                     double max_distance, uint32_t flags, uint64_t max_edges, uint32_t threads, const char *csv_path, hulk_link_list **out,
+                     hulk_links_stats *stats, char *errbuf, uint64_t errbuf_len) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (out) *out = nullptr;
+    if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    const std::string metric_s = metric, algo_s = algo;
+    if (!metric_name_ok(metric_s))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
+    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (!(max_distance >= 0.0 && max_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_links: max_distance must be in [0, 1]");
+    if (flags & ~HULK_LINKS_UPPER) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_links: unknown flags");
+    hulk_sketch_set *set = nullptr;
+    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
+    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
+    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    const uint32_t n = (uint32_t)set->files.size();
+    hulk_links_opts o;
+    memset(&o, 0, sizeof o);
+    o.metric = metric_code(metric_s);
+    o.max_distance = max_distance;
+    o.flags = flags;
+    o.max_edges = max_edges;
+    hulk_link_list *list = nullptr;
+    {
+        const int rc = hulk_links(device, set->mins.data(), set->weights.data(), n, set->size, &o, &list, stats);
+        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
+    }
+    struct ListGuard { hulk_link_list *l; ~ListGuard() { hulk_link_list_free(l); } } list_guard{list};
+    if (csv_path) {
+        std::string err;
+        if (!write_links_csv(*set, list, threads, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    }
+    if (out) { *out = list; list_guard.l = nullptr; }
+    return HULK_OK;
+}
+
 int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
                           uint32_t threads, const char *csv_path, double cut_distance, const char *cut_csv_path,
                           uint32_t *edge_a, uint32_t *edge_b, double *edge_distance, uint32_t *n_edges,

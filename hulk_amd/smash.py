@@ -245,6 +245,88 @@ def cluster_files(files, max_distance, ksize=21, algo="histosketch", metric="jac
     return ordering, labels[:len(ordering)], int(st.clusters)
 
 
+def _links_stats_dict(st):
+    return dict(seconds_total=st.seconds_total, kernel_ms_count=st.kernel_ms_count, kernel_ms_fill=st.kernel_ms_fill,
+                edges=st.edges, bands=st.bands, max_degree=st.max_degree)
+
+
+def _take_link_list(L, handle):
+    """numpy copies of a hulk_link_list; the list is freed"""
+    import ctypes
+    try:
+        n, edges = ctypes.c_uint32(), ctypes.c_uint64()
+        L.hulk_link_list_info(handle, ctypes.byref(n), ctypes.byref(edges))
+
+        def copy(ptr, count, dtype):
+            if not count:
+                return np.zeros(0, dtype=dtype)
+            return np.frombuffer(ctypes.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype).copy()
+        return (copy(L.hulk_link_list_row_start(handle), n.value + 1, np.uint64), copy(L.hulk_link_list_cols(handle), edges.value, np.uint32),
+                copy(L.hulk_link_list_distances(handle), edges.value, np.float64))
+    finally:
+        L.hulk_link_list_free(handle)
+
+
+def links(mins, weights, max_distance, metric="jaccard", upper=False, max_edges=0, band_rows=0, device=0, stats=None):
+    """The links of a sketch collection as a sparse graph, on the GPU (hulk_links): -> (indptr uint64[N + 1], indices uint32[E],
+    distances float64[E]), CSR.  With D = distance_matrix(mins, weights, metric), row i lists every j != i with D[i, j] <=
+    max_distance in ascending j (a NaN never is listed, equality is) and distances holds D[i, j] bit for bit; E is cluster()'s
+    `links` at the same threshold.  weightedjaccard is directed (the subject's weights on both sides); upper=True keeps j > i only.
+    Without upper every metric pays the full square.  max_edges (0 = none): more edges than that is a HulkError that names the cap
+    and the count reached (stats["edges"] has the count so far).  band_rows as in cluster(): it cannot change the result.
+    scipy.sparse.csr_matrix((distances, indices, indptr), shape=(N, N)) takes the three arrays as they are.  stats: a dict that
+    receives seconds_total, kernel_ms_count, kernel_ms_fill, edges, bands, max_degree."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
+    if m.ndim != 2 or (w is not None and m.shape != w.shape):
+        raise ValueError("mins/weights must be [n][sketch_size]")
+    band_rows, max_edges = int(band_rows), int(max_edges)
+    if not 0 <= band_rows < 2 ** 32:
+        raise ValueError("band_rows must be a multiple of 32 (0 = default)")
+    if not 0 <= max_edges < 2 ** 64:
+        raise ValueError("max_edges must be non-negative (0 = no cap)")
+    o = _lib.LinksOpts(metric=_METRIC_CODE[metric], max_distance=float(max_distance), band_rows=band_rows,
+                       flags=_lib.HULK_LINKS_UPPER if upper else 0, max_edges=max_edges)
+    st = _lib.LinksStats()
+    handle = ctypes.c_void_p()
+    L = _lib.load()
+    rc = L.hulk_links(device, m.ctypes.data, None if w is None else w.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), ctypes.byref(handle), ctypes.byref(st))
+    if stats is not None:
+        stats.update(_links_stats_dict(st))
+    if rc != 0:
+        raise HulkError(rc, L.hulk_last_error(None).decode())
+    return _take_link_list(L, handle)
+
+
+def links_files(files, max_distance, ksize=21, algo="histosketch", metric="jaccard", upper=False, max_edges=0, csv_path=None, threads=0,
+                device=0, stats=None):
+    """The directory form (hulk_links_files): the sketch files are loaded and MD5-verified by the native loader (one file is fine),
+    the links are listed on the GPU and, csv_path given, the library writes "sketch,neighbour,distance,similarity" — one line per
+    edge in CSR order: the two paths, the distance as %.17g and the similarity string `smash` prints for the pair.
+    -> (ordering, indptr, indices, distances); ordering = the sorted unique paths, which the rows and indices count."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if algo not in AVAIL_ALGORITHMS:
+        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    ordering = sorted(set(files))
+    arr, n = _paths(files)
+    st = _lib.LinksStats()
+    err = ctypes.create_string_buffer(4096)
+    handle = ctypes.c_void_p()
+    L = _lib.load()
+    rc = L.hulk_links_files(device, arr, n, ksize, algo.encode(), metric.encode(), float(max_distance), _lib.HULK_LINKS_UPPER if upper else 0,
+                            int(max_edges), threads, None if csv_path is None else os.fsencode(csv_path), ctypes.byref(handle), ctypes.byref(st),
+                            err, len(err))
+    if stats is not None:
+        stats.update(_links_stats_dict(st))
+    if rc != 0:
+        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    return (ordering,) + _take_link_list(L, handle)
+
+
 def _dendrogram_stats_dict(st):
     return dict(seconds_total=st.seconds_total, kernel_ms_offer=st.kernel_ms_offer, kernel_ms_fold=st.kernel_ms_fold,
                 rounds=st.rounds, bands=st.bands, edges=st.edges, components=st.components)

@@ -404,6 +404,74 @@ inline std::vector<uint32_t> ClusterFiles(const std::vector<std::string> &jsonFi
     return label;
 }
 
+// The links of a collection as a sparse graph, on the GPU (hulk_links): row i lists every j != i whose Smash entry [i][j] is <=
+// maxDistance (in [0, 1]; a NaN never is listed, equality is) in ascending j, with that entry bit for bit.  CSR: the edges of row i
+// are Indices / Distances [RowStart[i], RowStart[i + 1]).  weightedjaccard is directed; upper keeps j > i only; without it every
+// metric pays the full square.  maxEdges (0 = none): more edges than that throws (HULK_ERR_ARG; the text names the cap and the count).
+// The struct owns the library's list and frees it; the three pointers are valid while it lives.
+struct LinkList {
+    uint32_t N = 0;
+    uint64_t Edges = 0;
+    const uint64_t *RowStart = nullptr;    // [N + 1]
+    const uint32_t *Indices = nullptr;     // [Edges]
+    const double *Distances = nullptr;     // [Edges]
+    LinkList() = default;
+    explicit LinkList(hulk_link_list *list) : list_(list) {
+        hulk_link_list_info(list, &N, &Edges);
+        RowStart = hulk_link_list_row_start(list); Indices = hulk_link_list_cols(list); Distances = hulk_link_list_distances(list);
+    }
+    LinkList(LinkList &&o) noexcept { *this = std::move(o); }
+    LinkList &operator=(LinkList &&o) noexcept {
+        if (this != &o) {
+            hulk_link_list_free(list_);
+            list_ = o.list_; N = o.N; Edges = o.Edges; RowStart = o.RowStart; Indices = o.Indices; Distances = o.Distances;
+            o.list_ = nullptr; o.N = 0; o.Edges = 0; o.RowStart = nullptr; o.Indices = nullptr; o.Distances = nullptr;
+        }
+        return *this;
+    }
+    LinkList(const LinkList &) = delete;
+    LinkList &operator=(const LinkList &) = delete;
+    ~LinkList() { hulk_link_list_free(list_); }
+
+  private:
+    hulk_link_list *list_ = nullptr;
+};
+inline LinkList Links(const std::vector<HistoSketch> &sketches, double maxDistance, const std::string &metric, bool upper = false,
+                      uint64_t maxEdges = 0, uint32_t bandRows = 0, int device = 0, hulk_links_stats *stats = nullptr) {
+    const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
+    std::vector<uint64_t> mins((size_t)N * S + 1);
+    std::vector<double> weights((size_t)N * S + 1);
+    for (uint32_t i = 0; i < N; i++) {
+        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
+            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
+        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
+        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
+    }
+    hulk_links_opts o = hulk_links_opts();
+    o.max_distance = maxDistance; o.band_rows = bandRows; o.flags = upper ? HULK_LINKS_UPPER : 0u; o.max_edges = maxEdges;
+    o.metric = MetricCode(metric);
+    hulk_link_list *list = nullptr;
+    const int rc = hulk_links(device, mins.data(), weights.data(), N, S, &o, &list, stats);
+    if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+    return LinkList(list);
+}
+
+// The directory form (hulk_links_files): the files through the library's loader (sorted unique paths, which the rows and indices
+// count; the reference's error texts); linksCSV, if not empty, receives "sketch,neighbour,distance,similarity", one line per edge.
+inline LinkList LinksFiles(const std::vector<std::string> &jsonFiles, uint32_t kSize, const std::string &algo, const std::string &metric,
+                           double maxDistance, bool upper = false, uint64_t maxEdges = 0, const std::string &linksCSV = std::string(),
+                           hulk_links_stats *stats = nullptr, int device = 0, uint32_t threads = 0) {
+    std::vector<const char *> ptr;
+    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
+    char err[4096] = {0};
+    hulk_link_list *list = nullptr;
+    const int rc = hulk_links_files(device, ptr.data(), (uint32_t)ptr.size(), kSize, algo.c_str(), metric.c_str(), maxDistance,
+                                    upper ? HULK_LINKS_UPPER : 0u, maxEdges, threads, linksCSV.empty() ? nullptr : linksCSV.c_str(), &list, stats,
+                                    err, sizeof err);
+    if (rc != HULK_OK) throw Error(rc, err);
+    return LinkList(list);
+}
+
 // The single-linkage dendrogram of a collection, on the GPU (hulk_dendrogram): the minimum spanning forest of the graph whose edge
 // {i, j} weighs fmin(Smash's [i][j], [j][i]) (NaNs ignored; two NaNs: no edge), edges ordered by (weight, A, B): A < B, ascending —
 // the merge order.  Cut at any distance it is hulk::Cluster at that maxDistance.  bandRows cannot change the result.

@@ -674,6 +674,60 @@ int hulk_cluster_files(int device, const char *const *paths, uint32_t n, uint32_
                        double max_distance, uint32_t threads, const char *csv_path, uint32_t *label,
                        hulk_cluster_stats *stats, char *errbuf, uint64_t errbuf_len);
 
+/* ---- the links of a sketch collection as a sparse graph: every pair within a distance, with its distance ----------------------------
+ * d(i, j) = entry [i][j] of the matrix hulk_smash gives (sketch i the subject), bit for bit.  Row i of the result lists every j != i
+ * with d(i, j) <= max_distance, in ascending j: the compare is on the double itself, equality is in, a NaN never is — hulk_cluster's
+ * link rule for ONE direction.  The result is CSR: row_start[n + 1] (uint64), col[edges] (uint32), distance[edges] (double, the very
+ * bits hulk_smash gives); edges = row_start[n] is hulk_cluster's stats->links at the same threshold.  weightedjaccard is directed
+ * (the subject's weights are used on both sides); jaccard and bottomk come out symmetric.  HULK_LINKS_UPPER: only j > i — for the two
+ * symmetric metrics the graph without its mirror image, for weightedjaccard the upper part of the directed graph; the tiles wholly
+ * below the diagonal are not computed.  Without it every metric pays the full square, about twice hulk_cluster's triangle for jaccard
+ * and bottomk.  A function of the inputs alone: bands, tile shape, scheduling and repeats cannot change a byte; the host sorts nothing.
+ * The set is prepared once and stays on the device as in hulk_cluster (the same peak of 32 * sketch_size * n bytes); no n x n array
+ * exists on the device or the host.  Per band of band_rows subject rows: k_links_count (hulk_links.hip: hulk_cluster's tile; one 64-bit
+ * mask per row and tile of 64 columns), a scan of the masks' popcounts, one synchronisation in which the host reads the band's edge
+ * count, and k_links_fill over the tiles that hold an edge, which computes those tiles again and writes every edge to its final
+ * slot.  Beside the set the device holds 12.25 bytes per (row of the band, 64 columns) — the band is shrunk, in steps of 32 rows, to
+ * fit — and 12 bytes per edge of the densest band.  When everything links the call costs two passes of the tile.
+ * The result is an object the library owns (as hulk_sketch_set): the caller cannot know `edges` in advance.
+ * HULK_ERR_ARG before any HIP call, with a text in hulk_last_error(NULL): NULL arrays (weights may be NULL for bottomk), opts or out;
+ * n or sketch_size == 0; an unknown metric; bottomk above HULK_MINHASH_MAX_SKETCH; max_distance outside [0, 1] (NaN included);
+ * band_rows not a multiple of 32; unknown flags; non-zero reserved; n above HULK_CLUSTER_MAX_N.  n == 1 is valid: 0 edges.
+ * max_edges != 0 and more edges than that: the call stops behind the first band whose running count crosses the cap and returns
+ * HULK_ERR_ARG (the cap is an argument the input does not fit) with a text that names the cap and the count reached, *out = NULL and
+ * the count so far in stats->edges (stats->bands: the bands counted).  A band whose edges do not fit in device memory ends the call
+ * the same way with HULK_ERR_HIP. */
+#define HULK_LINKS_UPPER 1u
+typedef struct hulk_links_opts {
+    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD / HULK_METRIC_BOTTOMK */
+    double max_distance;   /* tau in [0, 1]; anything else (NaN included): HULK_ERR_ARG */
+    uint32_t band_rows;    /* subject rows per launch; 0 = default (2048); a multiple of 32 (above 2^20: 2^20) */
+    uint32_t flags;        /* HULK_LINKS_UPPER */
+    uint64_t max_edges;    /* 0 = no cap other than memory */
+    uint64_t reserved[4];  /* zero */
+} hulk_links_opts;
+typedef struct hulk_links_stats {
+    double seconds_total, kernel_ms_count, kernel_ms_fill;   /* the whole call; k_links_count / k_links_fill summed over the bands (HIP events) */
+    uint64_t edges;
+    uint32_t bands, max_degree;   /* max_degree: the longest row */
+} hulk_links_stats;
+typedef struct hulk_link_list hulk_link_list;
+int hulk_links(int device, const uint64_t *mins, const double *weights, uint32_t n, uint32_t sketch_size,
+               const hulk_links_opts *opts, hulk_link_list **out, hulk_links_stats *stats);
+int hulk_link_list_info(const hulk_link_list *list, uint32_t *n, uint64_t *edges);   /* HULK_ERR_ARG for NULL; n / edges may be NULL */
+const uint64_t *hulk_link_list_row_start(const hulk_link_list *list);   /* [n + 1]; NULL for NULL (the three of them) */
+const uint32_t *hulk_link_list_cols(const hulk_link_list *list);        /* [edges] */
+const double *hulk_link_list_distances(const hulk_link_list *list);     /* [edges] */
+void hulk_link_list_free(hulk_link_list *list);                         /* NULL is fine */
+/* The directory form: hulk_cluster_files' loader, error texts and their order, "one sketch is valid", and its weightedjaccard /
+ * bottomk algorithm checks.  The rows count the sorted unique paths.  csv_path != NULL: a file with the header
+ * "sketch,neighbour,distance,similarity" and one line per edge in CSR order: the two paths as encoding/csv quotes them, the distance
+ * as %.17g (it reads back to the same double) and strconv.FormatFloat(100 - 100 * distance, 'f', 2, 64), the string `smash` prints
+ * for that pair.  out may be NULL (the list is freed); otherwise *out is the caller's to free. */
+int hulk_links_files(int device, const char *const *paths, uint32_t n, uint32_t ksize, const char *algo, const char *metric,
+                     double max_distance, uint32_t flags, uint64_t max_edges, uint32_t threads, const char *csv_path,
+                     hulk_link_list **out /* may be NULL */, hulk_links_stats *stats, char *errbuf, uint64_t errbuf_len);
+
 /* ---- the single-linkage dendrogram of a sketch collection: every threshold of hulk_cluster at once ---------------------------------
  * d(i, j) = entry [i][j] of the matrix hulk_smash gives (sketch i the subject), bit for bit.  The undirected edge {i, j}, i != j,
  * weighs w(i, j) = fmin(d(i, j), d(j, i)) — a NaN direction is ignored, two NaN directions are no edge: hulk_cluster's "either
