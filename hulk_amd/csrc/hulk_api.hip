@@ -142,6 +142,8 @@ int hulk_create(const hulk_params *params, hulk_ctx **out) {
     c->stream = c->own_stream;
     const size_t B = (size_t)c->B, S = c->S, SL = c->slots;
     CHK_CREATE(dalloc(&c->d_state, 1));
+    CHK_CREATE(hipHostMalloc((void **)&c->h_verdict, 8, hipHostMallocMapped));   // k_flush_decide's word to the host (steady_adopt)
+    *c->h_verdict = 0;
     // (the HULK_* variables read here are overrides for profiling scripts; a host sets the fields)
     auto knob = [](const char *name, uint32_t field, uint32_t dflt, uint32_t lo, uint32_t hi) {
         uint32_t v = field ? field : dflt;
@@ -260,6 +262,7 @@ void hulk_destroy(hulk_ctx *c) {
     for (auto &pr : c->prof) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); }
     for (auto &m : c->marks) hipEventDestroy(m.e);
     hipFree(c->d_state); hipFree(c->d_hist); hipFree(c->d_hist_tmp);
+    if (c->h_verdict) hipHostFree(c->h_verdict);
     hipFree(c->d_meta8); hipFree(c->d_segsum); hipFree(c->d_cbase);
     hipFree(c->d_segadd); hipFree(c->d_segfac); hipFree(c->d_cstart); hipFree(c->d_sege0);
     hipFree(c->d_ctr); hipFree(c->d_pos16); hipFree(c->d_mins); hipFree(c->d_f64); hipFree(c->d_weights);

@@ -1,6 +1,7 @@
 // hulk_countmin.hip — KmerSpectrum.Cardinality and count-min Add() for a batch of spectra, bin order.
 //   K2  k_count_used       the 1 % rule (kmerspectrum.go:53-55,84-96)
 //   K3  k_cms_segsum/k_cms_base/k_cms_freq   src/countmin/countmin.go:103-147
+//       k_cms_steady_sums/k_cms_steady_add   what is left of K3 in a flush the host knows k_flush_decide passes over
 //       k_elem_*/k_cmsd_*  the same with uniform scaling (0 < decay < 1)
 // The replay (k_*_freq) is a 2 x 2 over one skeleton, cms_replay<order>(arithmetic):
 //                         LDS order (default)       chain order (fallback)
@@ -72,23 +73,91 @@ __device__ __forceinline__ void cms_seg_row_sums(uint32_t *lctr, const uint32_t 
     }
 }
 
-__global__ __launch_bounds__(512) void k_cms_segsum(const uint32_t *__restrict__ hists,
-                                                    const uint16_t *__restrict__ pos16,
-                                                    uint32_t *__restrict__ segsum, int depth, int width,
-                                                    int seg_chunks, const DevState *st, FlushBatch fb) {
+// Workgroup (segment, spectrum): the segment's row sums to segsum[t][d][seg][p].  STEADY (k_cms_steady_sums, "The steady
+// flush" below): the sums are all the count-min still needs of the spectrum, so the workgroup also wipes its segment — what
+// cms_replay does for a batch k_flush_decide passed over — and touches nothing when the device-side proof is missing.
+template <bool STEADY, class Hist>
+__device__ __forceinline__ void cms_segsum(Hist *__restrict__ hists, const uint16_t *__restrict__ pos16,
+                                           uint32_t *__restrict__ segsum, int depth, int width, int seg_chunks,
+                                           const DevState *st, const FlushBatch &fb) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint32_t *lctr = (uint32_t *)smem;                           // [depth][width]
     const int seg = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
     const uint32_t gomask = batch_gomask(st, fb);
     if (!((gomask >> t) & 1u)) return;
+    if (STEADY && !st->skip_exact[fb.parity]) return;            // (k_cms_steady_add raises the error)
     const size_t B = (size_t)fb.num_bins;
-    cms_seg_row_sums(lctr, hists + (size_t)ring_slot(fb, t) * B, pos16, B, (int64_t)seg * seg_chunks * 64, depth, width, seg_chunks);
+    Hist *hist = hists + (size_t)ring_slot(fb, t) * B;
+    const int64_t b0 = (int64_t)seg * seg_chunks * 64;
+    cms_seg_row_sums(lctr, hist, pos16, B, b0, depth, width, seg_chunks);
     __syncthreads();
     uint32_t *out = segsum + (((size_t)t * depth) * CMS_SEGS + 0) * width;
     for (int i = tid; i < depth * width; i += blockDim.x) {
         const int dd = i / width, p = i - dd * width;
         out[((size_t)dd * CMS_SEGS + seg) * width + p] = lctr[i];
     }
+    if constexpr (STEADY) {
+        const int64_t w1 = b0 + (int64_t)seg_chunks * 64;
+        for (int64_t b = b0 + tid; b < w1 && b < (int64_t)B; b += blockDim.x) hist[b] = 0;      // Wipe (kmerspectrum.go:58-64)
+    }
+}
+__global__ __launch_bounds__(512) void k_cms_segsum(const uint32_t *__restrict__ hists,
+                                                    const uint16_t *__restrict__ pos16,
+                                                    uint32_t *__restrict__ segsum, int depth, int width,
+                                                    int seg_chunks, const DevState *st, FlushBatch fb) {
+    cms_segsum<false>(hists, pos16, segsum, depth, width, seg_chunks, st, fb);
+}
+
+// ------------------------------------------------------------------------------------------
+// The steady flush.  Once k_flush_decide has passed over a whole batch of a context without decay, it passes over every later
+// one: the counters only grow, so their minimum m only grows; kminslot is static; the weights change only in a batch that was
+// evaluated; hence bound = kminslot / m rises towards 0 while every threshold stays where it is.  The host learns the verdict
+// from the word k_flush_decide stores to its memory (hulk_flush.hip, steady_adopt) and from then on queues, behind k_count_used
+// and k_flush_decide, only what such a batch still changes: the counters (countmin.go:122-127), the element count and the
+// 1 % rule (kmerspectrum.go:84-96), and the wipe (kmerspectrum.go:58-64).
+//   k_cms_steady_sums : k_cms_segsum + the wipe of the workgroup's own segment
+//   k_cms_steady_add  : thread per counter, ctr += the sums of the intervals that go; thread 0 keeps the books
+// k_flush_decide still runs in front of them and stays the proof on the device: without skip_exact neither kernel changes
+// anything and the batch ends in HULK_ERR_STATE — lost loudly.  No `base`, no replay workgroups with 112 KB of LDS, no scan.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void k_cms_steady_sums(uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
+                                                         uint32_t *__restrict__ segsum, int depth, int width,
+                                                         int seg_chunks, const DevState *st, FlushBatch fb) {
+    cms_segsum<true>(hists, pos16, segsum, depth, width, seg_chunks, st, fb);
+}
+
+__global__ __launch_bounds__(256) void k_cms_steady_add(const uint32_t *__restrict__ segsum,
+                                                        unsigned long long *__restrict__ ctr, int depth, int width,
+                                                        DevState *st, FlushBatch fb) {
+    const uint32_t gomask = batch_gomask(st, fb);
+    const bool proven = st->skip_exact[fb.parity] != 0u;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        if (!proven) set_error(st, -34);                                             // HULK_ERR_STATE: the host's verdict does not hold
+        else {
+            unsigned long long elems = 0; bool few = false;
+            for (int t = 0; t < (int)fb.count; t++) {
+                const unsigned used = st->used[fb.parity][ring_slot(fb, t)];
+                if ((gomask >> t) & 1u) elems += used;
+                else if (used != 0) few = true;                                      // "not used yet" (kmerspectrum.go:94-96)
+            }
+            if (few) set_error(st, -5);
+            if (elems) atomicAdd(&st->n_elements, elems);
+        }
+    }
+    if (!proven || i >= depth * width) return;
+    const int d = i / width, p = i - d * width;
+    unsigned long long sum = 0;
+    for (int t = 0; t < (int)fb.count; t++) {
+        if (!((gomask >> t) & 1u)) continue;
+        uint32_t sv[CMS_SEGS];
+        const size_t at0 = (((size_t)t * depth + d) * CMS_SEGS) * width + p;
+#pragma unroll
+        for (int seg = 0; seg < CMS_SEGS; seg++) sv[seg] = segsum[at0 + (size_t)seg * width];   // independent loads
+#pragma unroll
+        for (int seg = 0; seg < CMS_SEGS; seg++) sum += sv[seg];
+    }
+    if (sum) ctr[i] += sum;
 }
 
 // base[t][d][seg][p] = counter (d,p) in front of segment seg of spectrum t; advances the persistent counters
@@ -582,6 +651,16 @@ hipError_t launch_cms_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t 
         hipLaunchKernelGGL(k_cms_freq, dim3(CMS_SEGS, fb.count), dim3(512), lds3, s, d_base, d_hists, d_pos16, d_f64,
                            d_rcp32, depth, width, seg_chunks, row_stride, st, fb);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_cms_steady(hipStream_t s, uint32_t *d_hists, const uint16_t *d_pos16, unsigned long long *d_ctr,
+                             uint32_t *d_segsum, int depth, int width, DevState *st, const FlushBatch &fb) {
+    prof_mark(s, "k_cms_steady_sums");
+    hipLaunchKernelGGL(k_cms_steady_sums, dim3(CMS_SEGS, fb.count), dim3(512), (size_t)depth * width * 4, s, d_hists, d_pos16,
+                       d_segsum, depth, width, cms_seg_chunks(fb.num_bins), st, fb);
+    prof_mark(s, "k_cms_steady_add");
+    hipLaunchKernelGGL(k_cms_steady_add, dim3((depth * width + 255) / 256), dim3(256), 0, s, d_segsum, d_ctr, depth, width, st, fb);
     return hipGetLastError();
 }
 

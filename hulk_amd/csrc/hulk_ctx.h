@@ -176,6 +176,13 @@ struct hulk_ctx {
         std::vector<Group> groups; size_t group_head = 0;                    // queued flushes whose snapshots are not delivered yet
         std::vector<hipEvent_t> free_events;
     } snap;
+    // The steady flush (hulk_flush.hip, steady_adopt; hulk_countmin.hip): h_verdict is one word of mapped pinned memory into
+    // which k_flush_decide stores {flush tag : skip_exact}; `steady` goes false -> true when a word of this epoch says skip, and
+    // from then on flush_kernels queues the four-kernel chain.  steady_tag_min: the first flush tag of the epoch (words of
+    // flushes queued before the premises last changed do not count).
+    unsigned long long *h_verdict = nullptr;
+    bool steady = false;
+    uint32_t flush_tag = 0, steady_tag_min = 1;                   // the tag of the latest k_flush_decide launch (they count from 1)
     // host-side run state
     uint64_t seq_count = 0, flush_index = 0;
     uint32_t T = 16, ring_n = 17, ring_base = 0;   // interval batch size and spectrum ring
@@ -230,6 +237,8 @@ int lanes_join(hulk_ctx *c);
 int lanes_prereserve(hulk_ctx *c);
 int stage_mark_busy(hulk_ctx *c, hulk_ctx::HostStage &hs);
 int flush_kernels(hulk_ctx *c, hipStream_t s, uint32_t *hist, const FlushBatch &fb);
+bool steady_eligible(const hulk_ctx *c);
+void steady_reset(hulk_ctx *c);
 bool no_overlap_mode(const hulk_ctx *c);
 hipStream_t flush_stream_of(hulk_ctx *c);
 // what closed the spectra of a flush (for the snapshots' n_reads): an explicit hulk_flush, the interval rule, hulk_finish's EOF flush

@@ -65,7 +65,8 @@ __global__ __launch_bounds__(1024) void k_flush_decide(const unsigned long long 
                                                        const float *__restrict__ kminslot,
                                                        const double *__restrict__ weights, int slots, int slot_begin,
                                                        DevState *st, FlushBatch fb, int enable,
-                                                       unsigned long long *seal, uint32_t seal_tag) {
+                                                       unsigned long long *seal, uint32_t seal_tag,
+                                                       unsigned long long *h_verdict, uint32_t flush_tag) {
     __shared__ unsigned long long red[16];
     __shared__ int anypass;
     const int tid = threadIdx.x;
@@ -97,7 +98,12 @@ __global__ __launch_bounds__(1024) void k_flush_decide(const unsigned long long 
     // in front of this one on the stream): a block with the step's tag has all of its content, a block without is void
     if (tid == 0) {
         if (seal) *seal = ((unsigned long long)seal_tag << 32) | (anypass ? 1ull : 0ull);
-        else st->skip_exact[fb.parity] = anypass ? 0u : 1u;
+        else {
+            st->skip_exact[fb.parity] = anypass ? 0u : 1u;
+            // ... and to the host, which may queue the steady chain for a later flush of the context (hulk_flush.hip, steady_adopt):
+            // a vector store to its mapped memory, no copy engine and no wait between the verdict and the host's view of it
+            if (h_verdict) { __builtin_nontemporal_store(verdict_word(flush_tag, !anypass), h_verdict); __threadfence_system(); }
+        }
     }
 }
 __global__ __launch_bounds__(256) void k_slot_kmin(const float *__restrict__ kmin32, float *__restrict__ kminslot, int wtiles) {
@@ -933,10 +939,11 @@ hipError_t launch_slot_kmin(hipStream_t s, const float *d_kmin32, float *d_kmins
 
 hipError_t launch_flush_decide(hipStream_t s, const unsigned long long *d_ctr, int ncounters, const float *d_kminslot,
                                const double *d_weights, int slots, int slot_begin, DevState *st, const FlushBatch &fb,
-                               int enable, unsigned long long *d_seal, uint32_t seal_tag) {
+                               int enable, unsigned long long *d_seal, uint32_t seal_tag, unsigned long long *h_verdict,
+                               uint32_t flush_tag) {
     prof_mark(s, "k_flush_decide");
     hipLaunchKernelGGL(k_flush_decide, dim3(1), dim3(1024), 0, s, d_ctr, ncounters, d_kminslot, d_weights, slots,
-                       slot_begin, st, fb, enable, d_seal, seal_tag);
+                       slot_begin, st, fb, enable, d_seal, seal_tag, h_verdict, flush_tag);
     return hipGetLastError();
 }
 

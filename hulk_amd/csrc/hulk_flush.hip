@@ -74,6 +74,29 @@ int fatal_status(hulk_ctx *c) {
     return HULK_OK;
 }
 
+// The steady flush ("The steady flush", hulk_countmin.hip).  A context whose flushes k_flush_decide can pass over for good:
+// the conditions under which the kernel is enabled, integer counters, and nothing that wants the sketch after a PREFIX of a
+// batch (snapshots, a panel) or flushes through another chain (a communicator, the sliced step's all-reduce).
+bool steady_eligible(const hulk_ctx *c) {
+    return c->prune && !c->drift && !c->scaling && !c->no_skip && c->slots && !c->snap.every && !c->snap.panel.n &&
+           !c->comm.kind && !c->deferred.allreduce && !HULK_EXP_ENV("HULK_NO_STEADY_FLUSH");   // (the switch: the full chain as comparator)
+}
+// The host looks at the word k_flush_decide stores to its memory — one load, no wait — and goes steady if a flush of this
+// epoch was passed over.  Two call sites: the end of sync_all (the streams are idle: the word is the last flush's, the same
+// for the same calls) and, on a context that overlaps, issue_flush (a stream that never synchronises: hulk_sketch_files).
+static void steady_adopt(hulk_ctx *c) {
+    if (c->steady || !c->h_verdict || !steady_eligible(c)) return;
+    const unsigned long long w = __atomic_load_n(c->h_verdict, __ATOMIC_RELAXED);
+    const uint32_t tag = (uint32_t)(w >> 32);
+    if ((w & 1ull) && tag >= c->steady_tag_min && tag <= c->flush_tag) c->steady = true;
+}
+// the premises of the verdict change (the CWS tables are installed or rebuilt): the full chain until a flush is passed over again
+void steady_reset(hulk_ctx *c) {
+    c->steady = false;
+    c->steady_tag_min = c->flush_tag + 1;
+    if (c->h_verdict) __atomic_store_n(c->h_verdict, 0ull, __ATOMIC_RELAXED);
+}
+
 int sync_all(hulk_ctx *c) {
     { const int rc = fatal_status(c); if (rc != HULK_OK) return rc; }
     { const int rc = issue_flush(c, nullptr); if (rc != HULK_OK) return rc; }
@@ -81,6 +104,7 @@ int sync_all(hulk_ctx *c) {
     if (c->lane[1].stream) HIPCHK(c, hipStreamSynchronize(c->lane[1].stream));
     c->stagger = 1;                                             // both lanes idle: see bin_fast
     HIPCHK(c, hipStreamSynchronize(c->flush_stream));
+    steady_adopt(c);
     return HULK_OK;
 }
 
@@ -414,7 +438,14 @@ int flush_kernels(hulk_ctx *c, hipStream_t s, uint32_t *hist, const FlushBatch &
     if (!c->scaling) HIPCHK(c, launch_count_used(s, hist, c->d_state, fb));    // (with decay k_elem_index delivers the count)
     {   // whole-batch bound on the counters as they stand BEFORE this batch is added (see k_flush_decide)
         HIPCHK(c, launch_flush_decide(s, c->d_ctr, c->cms_depth * c->cms_width, c->d_kminslot, c->d_weights, (int)c->slots,
-                                      (int)c->slot_begin, c->d_state, fb, (c->prune && !c->drift && !c->no_skip && c->slots) ? 1 : 0));
+                                      (int)c->slot_begin, c->d_state, fb, (c->prune && !c->drift && !c->no_skip && c->slots) ? 1 : 0,
+                                      nullptr, 0, c->h_verdict, ++c->flush_tag));
+    }
+    if (c->steady && steady_eligible(c)) {
+        // the host knows the verdict: what is left of the flush is the counters, the element count, the 1 % rule and the wipe
+        HIPCHK(c, launch_cms_steady(s, hist, c->d_pos16, c->d_ctr, c->d_segsum, c->cms_depth, c->cms_width, c->d_state, fb));
+        c->scan_tiles_total += (uint64_t)((c->slots + SCAN_ROWS - 1) / SCAN_ROWS) * (uint64_t)c->ntiles * 4u;   // (as the scan it stands for)
+        return HULK_OK;
     }
     if (c->scaling) {
         HIPCHK(c, launch_elem_index(s, hist, c->d_blkcnt, c->d_eidx, c->d_etot, fb, c->d_state));
@@ -478,6 +509,7 @@ int issue_flush(hulk_ctx *c, hipEvent_t gate) {
         const int rc = comm_allreduce_u32(c, s, hist + (size_t)fb.ring_base * (size_t)c->B, (size_t)fb.count * (size_t)c->B);
         if (rc != HULK_OK) return rc;
     }
+    if (!no_overlap_mode(c)) steady_adopt(c);                   // (a one-stream context adopts in sync_all only: reproducible launch tables)
     { const int rc = flush_kernels(c, s, hist, fb); if (rc != HULK_OK) return rc; }
     if (c->deferred.snap_n) { const int rc = snap_flush_issued(c, s, c->deferred.snap_first, c->deferred.snap_n); if (rc != HULK_OK) return rc; }
     HIPCHK(c, hipEventRecord(c->ev_flushed[ring], s));

@@ -137,6 +137,10 @@ hipError_t launch_cms_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t 
                                unsigned long long *d_ctr, uint32_t *d_segsum, unsigned long long *d_base,
                                double *d_f64, float *d_rcp32, int depth, int width, size_t row_stride,
                                DevState *st, const FlushBatch &fb, bool chain = false);
+// the count-min part of a flush the host knows k_flush_decide passes over ("The steady flush", hulk_countmin.hip): row sums +
+// wipe, then counters += sums with the element count and the 1 % rule; queued behind k_count_used and k_flush_decide
+hipError_t launch_cms_steady(hipStream_t s, uint32_t *d_hists, const uint16_t *d_pos16, unsigned long long *d_ctr,
+                             uint32_t *d_segsum, int depth, int width, DevState *st, const FlushBatch &fb);
 int lds_order_verified(int device);   // 1 / 0 / -(hipError_t): see hulk_countmin.hip
 size_t cms_binorder_entries(int depth, int width);   // entries of segsum / base per spectrum
 hipError_t launch_cmsd_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t *d_pos16, const uint8_t *d_meta8,
@@ -154,7 +158,11 @@ hipError_t launch_tile_kmin(hipStream_t s, const float *d_k32, float *d_kmin32, 
 hipError_t launch_slot_kmin(hipStream_t s, const float *d_kmin32, float *d_kminslot, int slots, int ntiles);
 hipError_t launch_flush_decide(hipStream_t s, const unsigned long long *d_ctr, int ncounters, const float *d_kminslot,
                                const double *d_weights, int slots, int slot_begin, DevState *st, const FlushBatch &fb,
-                               int enable, unsigned long long *d_seal = nullptr, uint32_t seal_tag = 0);
+                               int enable, unsigned long long *d_seal = nullptr, uint32_t seal_tag = 0,
+                               unsigned long long *h_verdict = nullptr, uint32_t flush_tag = 0);
+// h_verdict (mapped pinned host memory, may be null; not with a seal): the kernel also stores {flush_tag : skip_exact} there as
+// one 64-bit word, for the host's choice of the chain of a LATER flush (hulk_flush.hip, steady_adopt)
+__host__ __device__ inline unsigned long long verdict_word(uint32_t flush_tag, bool skip) { return ((unsigned long long)flush_tag << 32) | (skip ? 1ull : 0ull); }
 // hulk_step_sharded's exchange (hulk_countmin.hip): a rank's block is SHARD_HDR header words — the 64-bit SEAL
 // {word 0: need_full verdict for the next step, word 1: step + 1}, written last and with one store by k_flush_decide, then the
 // used bins per interval — and, for the delta exchange, [T][depth * width] count-min increments

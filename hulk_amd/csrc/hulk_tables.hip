@@ -65,6 +65,7 @@ int build_chains(hulk_ctx *c) {
 // upload r,c,b rows owned by this context as interleaved {r,c,b} and derive the fp32 K table
 int install_tables(hulk_ctx *c, const double *r, const double *cc, const double *b) {
     const size_t B = (size_t)c->B;
+    steady_reset(c);                                             // kminslot changes: a verdict from before says nothing
     std::vector<double> row(B * 3);
     for (uint32_t s = 0; s < c->slots; s++) {
         const size_t src = (size_t)(c->slot_begin + s) * B;
@@ -272,6 +273,7 @@ int ensure_tables(hulk_ctx *c) {
     if (c->tables_ready) return HULK_OK;
     if (c->p.cws_source == HULK_CWS_EXTERNAL)
         return fail(c, HULK_ERR_STATE, "cws_source is EXTERNAL but hulk_set_cws_tables was not called");
+    steady_reset(c);                                             // (as install_tables)
     return generate_tables(c);
 }
 
