@@ -530,8 +530,12 @@ int flush_batch(hulk_ctx *c, uint32_t count, hipStream_t dep_stream, bool use_de
     fb.parity = (int)(c->flush_index & 1); fb.num_bins = c->B;
     uint64_t snap_first = 0; uint32_t snap_n = 0;
     if (c->snap.every) { rc = snap_plan(c, fb, count, closed_by, &snap_first, &snap_n); if (rc != HULK_OK) return rc; }
-    // everything binned so far (or the caller's all-reduce on dep_stream) ends where this event is recorded
-    HIPCHK(c, hipEventRecord(c->ev_binned, use_dep ? dep_stream : ring_stream(c)));
+    // everything binned so far (or the caller's all-reduce on dep_stream) ends where this event is recorded.  On a caller's
+    // stream that is the stream itself, not the ring's lane: lane 1 was joined into it when the binning call returned, and
+    // what the caller queued there since — a copy of hulk_histogram_device(), an all-reduce into it — has to be passed
+    // before the flush reads and wipes the spectra (ONE stream towards the caller)
+    hipStream_t binned_on = c->stream != c->own_stream ? c->stream : ring_stream(c);
+    HIPCHK(c, hipEventRecord(c->ev_binned, use_dep ? dep_stream : binned_on));
     c->deferred.armed = true; c->deferred.fb = fb; c->deferred.ring = c->cur_ring;
     c->deferred.use_dep = use_dep; c->deferred.allreduce = allreduce;
     c->deferred.snap_first = snap_first; c->deferred.snap_n = snap_n;

@@ -355,6 +355,7 @@ class GpuSketcher:
         return self._L.hulk_batch_size(self._ctx)
 
     def histogram_device_ptr(self):
+        """hulk_histogram_device: the spectra of the batch being binned — one of two rings, so ask again after every flush_batch."""
         return self._L.hulk_histogram_device(self._ctx)
 
     def add_histogram(self, hist):

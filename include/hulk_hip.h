@@ -295,6 +295,13 @@ int hulk_bin_reads_device(hulk_ctx *ctx, const uint8_t *d_bases, const uint64_t 
 int hulk_bin_reads_device_at(hulk_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets,
                              uint64_t n_reads, uint32_t max_read_len, uint64_t bases_bytes,
                              uint64_t reads_per_spectrum, uint32_t first_spectrum);
+/* Spectrum 0 of the batch being binned: hulk_batch_size() spectra of num_bins uint32, contiguous.  The context keeps two
+ * such rings and every hulk_flush_batch[_after] (n_spectra > 0) moves on to the other one, so the pointer takes exactly
+ * two values, alternating from batch to batch: query it again after every hulk_flush_batch[_after].  Stream order: on a
+ * caller's stream (hulk_set_stream) the spectra are complete where that stream has passed hulk_bin_reads_device[_at], and
+ * what the caller queues on that stream before hulk_flush_batch — a copy out of the spectra, an all-reduce into them — is
+ * passed before the flush reads and wipes them.  A context on its private stream has no such stream to offer: synchronise
+ * (hulk_synchronize) before touching the spectra, and hand the stream that touched them to hulk_flush_batch_after. */
 uint32_t *hulk_histogram_device(hulk_ctx *ctx);
 int hulk_flush_batch(hulk_ctx *ctx, uint32_t n_spectra);
 /* Same, but the flush waits for the work queued so far on `dep_stream` (the stream the all-reduce
