@@ -202,6 +202,7 @@ int hulk_create(const hulk_params *params, hulk_ctx **out) {
     // holds for negative weights, which is what k_cws_scan tests then; decayRatio == 0 (decayWeight 0) is left alone
     c->prune = !(c->drift && c->decay_weight <= 0.0) && !HULK_EXP_ENV("HULK_NO_PRUNE") && !(p.flags & HULK_FLAG_NO_PRUNE);
     c->no_skip = HULK_EXP_ENV("HULK_NO_SKIP") != nullptr || (p.flags & HULK_FLAG_NO_SKIP) != 0;
+    if (steady_possible(c)) CHK_CREATE(dalloc(&c->d_hsum, B));    // the summed spectrum of a steady flush (hulk_countmin.hip)
     if (c->scaling) {
         const size_t NC = (size_t)c->cms_depth * c->cms_width;
         CHK_CREATE(dalloc(&c->d_blkcnt, T * (size_t)elem_index_blocks(c->B)));
@@ -263,7 +264,7 @@ void hulk_destroy(hulk_ctx *c) {
     for (auto &m : c->marks) hipEventDestroy(m.e);
     hipFree(c->d_state); hipFree(c->d_hist); hipFree(c->d_hist_tmp);
     if (c->h_verdict) hipHostFree(c->h_verdict);
-    hipFree(c->d_meta8); hipFree(c->d_segsum); hipFree(c->d_cbase);
+    hipFree(c->d_meta8); hipFree(c->d_segsum); hipFree(c->d_cbase); hipFree(c->d_hsum);
     hipFree(c->d_segadd); hipFree(c->d_segfac); hipFree(c->d_cstart); hipFree(c->d_sege0);
     hipFree(c->d_ctr); hipFree(c->d_pos16); hipFree(c->d_mins); hipFree(c->d_f64); hipFree(c->d_weights);
     hipFree(c->d_blkcnt); hipFree(c->d_eidx); hipFree(c->d_etot); hipFree(c->d_ctrd);

@@ -1,7 +1,8 @@
 // hulk_countmin.hip — KmerSpectrum.Cardinality and count-min Add() for a batch of spectra, bin order.
 //   K2  k_count_used       the 1 % rule (kmerspectrum.go:53-55,84-96)
 //   K3  k_cms_segsum/k_cms_base/k_cms_freq   src/countmin/countmin.go:103-147
-//       k_cms_steady_sums/k_cms_steady_add   what is left of K3 in a flush the host knows k_flush_decide passes over
+//       k_cms_steady_sums/k_cms_steady_add   what is left of K3 in a flush the host knows k_flush_decide passes over:
+//                          the batch's spectra summed per bin, then one count-min pass
 //       k_elem_*/k_cmsd_*  the same with uniform scaling (0 < decay < 1)
 // The replay (k_*_freq) is a 2 x 2 over one skeleton, cms_replay<order>(arithmetic):
 //                         LDS order (default)       chain order (fallback)
@@ -73,7 +74,7 @@ __device__ __forceinline__ void cms_seg_row_sums(uint32_t *lctr, const uint32_t 
     }
 }
 
-// Workgroup (segment, spectrum): the segment's row sums to segsum[t][d][seg][p].  STEADY (k_cms_steady_sums, "The steady
+// Workgroup (segment, spectrum): the segment's row sums to segsum[t][d][seg][p].  STEADY (k_cms_steady_segsum, "The steady
 // flush" below): the sums are all the count-min still needs of the spectrum, so the workgroup also wipes its segment — what
 // cms_replay does for a batch k_flush_decide passed over — and touches nothing when the device-side proof is missing.
 template <bool STEADY, class Hist>
@@ -85,7 +86,7 @@ __device__ __forceinline__ void cms_segsum(Hist *__restrict__ hists, const uint1
     const int seg = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
     const uint32_t gomask = batch_gomask(st, fb);
     if (!((gomask >> t) & 1u)) return;
-    if (STEADY && !st->skip_exact[fb.parity]) return;            // (k_cms_steady_add raises the error)
+    if (STEADY && !st->skip_exact[fb.parity]) return;            // (k_cms_steady_segadd raises the error)
     const size_t B = (size_t)fb.num_bins;
     Hist *hist = hists + (size_t)ring_slot(fb, t) * B;
     const int64_t b0 = (int64_t)seg * seg_chunks * 64;
@@ -115,36 +116,119 @@ __global__ __launch_bounds__(512) void k_cms_segsum(const uint32_t *__restrict__
 // from the word k_flush_decide stores to its memory (hulk_flush.hip, steady_adopt) and from then on queues, behind k_count_used
 // and k_flush_decide, only what such a batch still changes: the counters (countmin.go:122-127), the element count and the
 // 1 % rule (kmerspectrum.go:84-96), and the wipe (kmerspectrum.go:58-64).
-//   k_cms_steady_sums : k_cms_segsum + the wipe of the workgroup's own segment
-//   k_cms_steady_add  : thread per counter, ctr += the sums of the intervals that go; thread 0 keeps the books
+// Nothing reads an estimate in such a flush and the counters are integers, so the spectra of the batch need not be told
+// apart: counters += CM(sum over the spectra that go), one count-min pass over ONE summed spectrum.
+//   k_cms_steady_sums : thread per bin, hsum[b] = the 64-bit sum of bin b over the spectra that go; wipes those spectra
+//   k_cms_steady_add  : workgroup per (bin segment, row, part of the row): hsum into at most 8 KB of 64-bit LDS counters, the
+//                       non-zero ones into ctr with global 64-bit atomics (integer adds commute); thread 0 keeps the books
+// Every width from hsum to ctr is 64 bits: a sum spans up to RING_MAX spectra and a whole bin segment.
 // k_flush_decide still runs in front of them and stays the proof on the device: without skip_exact neither kernel changes
-// anything and the batch ends in HULK_ERR_STATE — lost loudly.  No `base`, no replay workgroups with 112 KB of LDS, no scan.
+// anything and the batch ends in HULK_ERR_STATE — lost loudly.  No `base`, no replay workgroups with 112 KB of LDS, no scan,
+// no LDS request that does not fit beside six k_minimizer_fast workgroups.
+// HULK_STEADY_SEGSUM (profiling build): the form in front of this one, per-(spectrum, segment) row sums in 56 KB of LDS
+// (k_cms_steady_segsum / k_cms_steady_segadd), under the same two marks — the A/B in one process image.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void k_cms_steady_sums(uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
-                                                         uint32_t *__restrict__ segsum, int depth, int width,
-                                                         int seg_chunks, const DevState *st, FlushBatch fb) {
-    cms_segsum<true>(hists, pos16, segsum, depth, width, seg_chunks, st, fb);
+constexpr int CMS_FOLD_SEGS = 16;     // bin segments of k_cms_steady_add (HULK_STEADY_SEGS: 4 / 8 / 16 were swept, profiles/steady_fold.md)
+constexpr int CMS_FOLD_PART = 1024;   // most counters of a row one workgroup keeps in LDS (8 KB of the 10,240 B six k_minimizer_fast workgroups leave)
+inline int cms_fold_seg_bins(int32_t num_bins, int segs) { return (((num_bins + segs - 1) / segs) + 255) & ~255; }
+
+__global__ __launch_bounds__(256) void k_cms_steady_sums(uint32_t *__restrict__ hists, unsigned long long *__restrict__ hsum,
+                                                         const DevState *st, FlushBatch fb) {
+    const uint32_t gomask = batch_gomask(st, fb);
+    if (!st->skip_exact[fb.parity]) return;                      // (k_cms_steady_add raises the error)
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t B = (size_t)fb.num_bins;
+    if (b >= (int64_t)B) return;
+    // one bin per thread and spectrum: a wave's 64 dwords are contiguous whatever the base of the spectrum (an odd num_bins
+    // leaves three ring slots of four off a 16-byte boundary, so nothing wider is loaded); every load is issued before the
+    // first is used
+    uint32_t v[RING_MAX];
+    uint32_t slot = fb.ring_base % fb.ring_n;
+#pragma unroll
+    for (int t = 0; t < RING_MAX; t++) {
+        v[t] = 0;
+        if (t < (int)fb.count && ((gomask >> t) & 1u)) v[t] = hists[(size_t)slot * B + (size_t)b];
+        if (++slot == fb.ring_n) slot = 0;
+    }
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int t = 0; t < RING_MAX; t++) sum += v[t];
+    hsum[b] = sum;
+    slot = fb.ring_base % fb.ring_n;
+#pragma unroll
+    for (int t = 0; t < RING_MAX; t++) {
+        if (t < (int)fb.count && ((gomask >> t) & 1u)) hists[(size_t)slot * B + (size_t)b] = 0;      // Wipe (kmerspectrum.go:58-64)
+        if (++slot == fb.ring_n) slot = 0;
+    }
 }
 
-__global__ __launch_bounds__(256) void k_cms_steady_add(const uint32_t *__restrict__ segsum,
-                                                        unsigned long long *__restrict__ ctr, int depth, int width,
-                                                        DevState *st, FlushBatch fb) {
+// the books of a steady flush (one thread): the proof, the element count over the spectra that go, the 1 % rule
+__device__ __forceinline__ void steady_books(DevState *st, const FlushBatch &fb, uint32_t gomask, bool proven) {
+    if (!proven) { set_error(st, -34); return; }                                     // HULK_ERR_STATE: the host's verdict does not hold
+    unsigned long long elems = 0; bool few = false;
+    for (int t = 0; t < (int)fb.count; t++) {
+        const unsigned used = st->used[fb.parity][ring_slot(fb, t)];
+        if ((gomask >> t) & 1u) elems += used;
+        else if (used != 0) few = true;                                              // "not used yet" (kmerspectrum.go:94-96)
+    }
+    if (few) set_error(st, -5);
+    if (elems) atomicAdd(&st->n_elements, elems);
+}
+
+// grid (segments, depth, parts of a row); dynamic LDS: part_w 64-bit counters
+__global__ __launch_bounds__(256) void k_cms_steady_add(const unsigned long long *__restrict__ hsum,
+                                                        const uint16_t *__restrict__ pos16,
+                                                        unsigned long long *__restrict__ ctr, int width, int part_w,
+                                                        int seg_bins, DevState *st, FlushBatch fb) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned long long *lctr = (unsigned long long *)smem;       // [part_w]
+    const uint32_t gomask = batch_gomask(st, fb);
+    const bool proven = st->skip_exact[fb.parity] != 0u;
+    const int tid = threadIdx.x, seg = blockIdx.x, d = blockIdx.y;
+    if (tid == 0 && seg == 0 && d == 0 && blockIdx.z == 0) steady_books(st, fb, gomask, proven);
+    if (!proven) return;
+    const int p0 = (int)blockIdx.z * part_w;
+    const int pw = width - p0 < part_w ? width - p0 : part_w;    // counters [p0, p0 + pw) of row d
+    for (int i = tid; i < pw; i += 256) lctr[i] = 0;
+    __syncthreads();
+    const int64_t B = fb.num_bins;
+    const int64_t b0 = (int64_t)seg * seg_bins, b1 = b0 + seg_bins < B ? b0 + seg_bins : B;
+    const uint16_t *pd = pos16 + (size_t)d * (size_t)B;
+    for (int64_t c0 = b0; c0 < b1; c0 += 8 * 256) {              // 8 x 256 bins of loads in flight
+        unsigned long long h[8]; uint32_t p[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int64_t b = c0 + u * 256 + tid;
+            const bool ok = b < b1;
+            h[u] = ok ? hsum[b] : 0ull; p[u] = ok ? pd[b] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const uint32_t q = p[u] - (uint32_t)p0;
+            if (h[u] && q < (uint32_t)pw) atomicAdd(&lctr[q], h[u]);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < pw; i += 256) {
+        const unsigned long long s = lctr[i];
+        if (s) atomicAdd(&ctr[(size_t)d * width + p0 + i], s);
+    }
+}
+
+// HULK_STEADY_SEGSUM: k_cms_segsum + the wipe of the workgroup's own segment ...
+__global__ __launch_bounds__(512) void k_cms_steady_segsum(uint32_t *__restrict__ hists, const uint16_t *__restrict__ pos16,
+                                                           uint32_t *__restrict__ segsum, int depth, int width,
+                                                           int seg_chunks, const DevState *st, FlushBatch fb) {
+    cms_segsum<true>(hists, pos16, segsum, depth, width, seg_chunks, st, fb);
+}
+// ... and thread per counter, ctr += the sums of the intervals that go
+__global__ __launch_bounds__(256) void k_cms_steady_segadd(const uint32_t *__restrict__ segsum,
+                                                           unsigned long long *__restrict__ ctr, int depth, int width,
+                                                           DevState *st, FlushBatch fb) {
     const uint32_t gomask = batch_gomask(st, fb);
     const bool proven = st->skip_exact[fb.parity] != 0u;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) {
-        if (!proven) set_error(st, -34);                                             // HULK_ERR_STATE: the host's verdict does not hold
-        else {
-            unsigned long long elems = 0; bool few = false;
-            for (int t = 0; t < (int)fb.count; t++) {
-                const unsigned used = st->used[fb.parity][ring_slot(fb, t)];
-                if ((gomask >> t) & 1u) elems += used;
-                else if (used != 0) few = true;                                      // "not used yet" (kmerspectrum.go:94-96)
-            }
-            if (few) set_error(st, -5);
-            if (elems) atomicAdd(&st->n_elements, elems);
-        }
-    }
+    if (i == 0) steady_books(st, fb, gomask, proven);
     if (!proven || i >= depth * width) return;
     const int d = i / width, p = i - d * width;
     unsigned long long sum = 0;
@@ -655,12 +739,25 @@ hipError_t launch_cms_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t 
 }
 
 hipError_t launch_cms_steady(hipStream_t s, uint32_t *d_hists, const uint16_t *d_pos16, unsigned long long *d_ctr,
-                             uint32_t *d_segsum, int depth, int width, DevState *st, const FlushBatch &fb) {
+                             uint32_t *d_segsum, unsigned long long *d_hsum, int depth, int width, DevState *st,
+                             const FlushBatch &fb) {
+    static const bool segsum_form = HULK_EXP_ENV("HULK_STEADY_SEGSUM") != nullptr;
+    if (segsum_form) {
+        prof_mark(s, "k_cms_steady_sums");
+        hipLaunchKernelGGL(k_cms_steady_segsum, dim3(CMS_SEGS, fb.count), dim3(512), (size_t)depth * width * 4, s, d_hists, d_pos16,
+                           d_segsum, depth, width, cms_seg_chunks(fb.num_bins), st, fb);
+        prof_mark(s, "k_cms_steady_add");
+        hipLaunchKernelGGL(k_cms_steady_segadd, dim3((depth * width + 255) / 256), dim3(256), 0, s, d_segsum, d_ctr, depth, width, st, fb);
+        return hipGetLastError();
+    }
+    if (!d_hsum || fb.num_bins <= 0 || width <= 0 || fb.count > (uint32_t)RING_MAX) return hipErrorInvalidValue;
+    static const int segs = [] { const char *e = HULK_EXP_ENV("HULK_STEADY_SEGS"); const int v = e ? atoi(e) : CMS_FOLD_SEGS; return v < 1 ? 1 : v > 64 ? 64 : v; }();
+    const int parts = (width + CMS_FOLD_PART - 1) / CMS_FOLD_PART, part_w = (width + parts - 1) / parts;
     prof_mark(s, "k_cms_steady_sums");
-    hipLaunchKernelGGL(k_cms_steady_sums, dim3(CMS_SEGS, fb.count), dim3(512), (size_t)depth * width * 4, s, d_hists, d_pos16,
-                       d_segsum, depth, width, cms_seg_chunks(fb.num_bins), st, fb);
+    hipLaunchKernelGGL(k_cms_steady_sums, dim3((fb.num_bins + 255) / 256), dim3(256), 0, s, d_hists, d_hsum, st, fb);
     prof_mark(s, "k_cms_steady_add");
-    hipLaunchKernelGGL(k_cms_steady_add, dim3((depth * width + 255) / 256), dim3(256), 0, s, d_segsum, d_ctr, depth, width, st, fb);
+    hipLaunchKernelGGL(k_cms_steady_add, dim3(segs, depth, parts), dim3(256), (size_t)part_w * 8, s, d_hsum, d_pos16, d_ctr, width,
+                       part_w, cms_fold_seg_bins(fb.num_bins, segs), st, fb);
     return hipGetLastError();
 }
 

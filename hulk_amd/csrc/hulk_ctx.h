@@ -90,6 +90,7 @@ struct hulk_ctx {
     unsigned long long *d_ctr = nullptr, *d_mins = nullptr, *d_min_slots = nullptr;
     uint16_t *d_pos16 = nullptr;
     uint8_t *d_meta8 = nullptr; uint32_t *d_segsum = nullptr; unsigned long long *d_cbase = nullptr;   // bin-order count-min
+    unsigned long long *d_hsum = nullptr;                                          // [B] the steady flush's summed spectrum (contexts that can go steady)
     double *d_segadd = nullptr, *d_segfac = nullptr, *d_cstart = nullptr; uint32_t *d_sege0 = nullptr; // ... with decay
     double *d_f64 = nullptr, *d_weights = nullptr, *d_rcb = nullptr;
     float *d_rcp32 = nullptr, *d_k32 = nullptr, *d_tilemin = nullptr;
@@ -237,6 +238,7 @@ int lanes_join(hulk_ctx *c);
 int lanes_prereserve(hulk_ctx *c);
 int stage_mark_busy(hulk_ctx *c, hulk_ctx::HostStage &hs);
 int flush_kernels(hulk_ctx *c, hipStream_t s, uint32_t *hist, const FlushBatch &fb);
+bool steady_possible(const hulk_ctx *c);
 bool steady_eligible(const hulk_ctx *c);
 void steady_reset(hulk_ctx *c);
 bool no_overlap_mode(const hulk_ctx *c);

@@ -77,8 +77,9 @@ int fatal_status(hulk_ctx *c) {
 // The steady flush ("The steady flush", hulk_countmin.hip).  A context whose flushes k_flush_decide can pass over for good:
 // the conditions under which the kernel is enabled, integer counters, and nothing that wants the sketch after a PREFIX of a
 // batch (snapshots, a panel) or flushes through another chain (a communicator, the sliced step's all-reduce).
+bool steady_possible(const hulk_ctx *c) { return c->prune && !c->drift && !c->scaling && !c->no_skip && c->slots; }   // (fixed at hulk_create: d_hsum)
 bool steady_eligible(const hulk_ctx *c) {
-    return c->prune && !c->drift && !c->scaling && !c->no_skip && c->slots && !c->snap.every && !c->snap.panel.n &&
+    return steady_possible(c) && !c->snap.every && !c->snap.panel.n &&
            !c->comm.kind && !c->deferred.allreduce && !HULK_EXP_ENV("HULK_NO_STEADY_FLUSH");   // (the switch: the full chain as comparator)
 }
 // The host looks at the word k_flush_decide stores to its memory — one load, no wait — and goes steady if a flush of this
@@ -443,7 +444,7 @@ int flush_kernels(hulk_ctx *c, hipStream_t s, uint32_t *hist, const FlushBatch &
     }
     if (c->steady && steady_eligible(c)) {
         // the host knows the verdict: what is left of the flush is the counters, the element count, the 1 % rule and the wipe
-        HIPCHK(c, launch_cms_steady(s, hist, c->d_pos16, c->d_ctr, c->d_segsum, c->cms_depth, c->cms_width, c->d_state, fb));
+        HIPCHK(c, launch_cms_steady(s, hist, c->d_pos16, c->d_ctr, c->d_segsum, c->d_hsum, c->cms_depth, c->cms_width, c->d_state, fb));
         c->scan_tiles_total += (uint64_t)((c->slots + SCAN_ROWS - 1) / SCAN_ROWS) * (uint64_t)c->ntiles * 4u;   // (as the scan it stands for)
         return HULK_OK;
     }

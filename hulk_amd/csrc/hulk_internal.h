@@ -137,10 +137,12 @@ hipError_t launch_cms_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t 
                                unsigned long long *d_ctr, uint32_t *d_segsum, unsigned long long *d_base,
                                double *d_f64, float *d_rcp32, int depth, int width, size_t row_stride,
                                DevState *st, const FlushBatch &fb, bool chain = false);
-// the count-min part of a flush the host knows k_flush_decide passes over ("The steady flush", hulk_countmin.hip): row sums +
-// wipe, then counters += sums with the element count and the 1 % rule; queued behind k_count_used and k_flush_decide
+// the count-min part of a flush the host knows k_flush_decide passes over ("The steady flush", hulk_countmin.hip): the spectra
+// that go summed per bin into d_hsum [num_bins] + their wipe, then counters += CM(d_hsum) with the element count and the 1 %
+// rule; queued behind k_count_used and k_flush_decide.  (d_segsum: scratch of the HULK_STEADY_SEGSUM form only.)
 hipError_t launch_cms_steady(hipStream_t s, uint32_t *d_hists, const uint16_t *d_pos16, unsigned long long *d_ctr,
-                             uint32_t *d_segsum, int depth, int width, DevState *st, const FlushBatch &fb);
+                             uint32_t *d_segsum, unsigned long long *d_hsum, int depth, int width, DevState *st,
+                             const FlushBatch &fb);
 int lds_order_verified(int device);   // 1 / 0 / -(hipError_t): see hulk_countmin.hip
 size_t cms_binorder_entries(int depth, int width);   // entries of segsum / base per spectrum
 hipError_t launch_cmsd_binorder(hipStream_t s, uint32_t *d_hists, const uint16_t *d_pos16, const uint8_t *d_meta8,
