@@ -36,6 +36,8 @@ HULK_SEARCH_MAX_K = 64          # hulk_search: hits per query
 HULK_SEARCH_SELF = 1            # ... the database is the query set itself, the pair (i, i) left out
 HULK_CLUSTER_MAX_N = 2097088     # hulk_cluster: sketches in one set
 HULK_LINKS_UPPER = 1            # hulk_links: only the edges (i, j) with j > i
+HULK_LINKAGE_SINGLE, HULK_LINKAGE_COMPLETE, HULK_LINKAGE_AVERAGE = 0, 1, 2
+HULK_LINKAGE_MAX_N = 65536      # hulk_linkage: the n x n matrix lives on the device
 HULK_MINHASH_MAX_SKETCH = 4096
 HULK_MAX_BINS = 1 << 20
 HULK_INJECT_NONE, HULK_INJECT_STALE_SEAL, HULK_INJECT_STALE_STAGE = 0, 1, 2
@@ -56,7 +58,7 @@ ABI_SYMBOLS = (
     "hulk_set_snapshots", "hulk_snapshot_count", "hulk_get_snapshots", "hulk_set_snapshot_callback", "hulk_poll_snapshots",
     "hulk_set_panel", "hulk_get_snapshot_distances", "hulk_set_snapshot_panel_callback", "hulk_panel_distances",
     "hulk_search", "hulk_search_files", "hulk_cluster", "hulk_cluster_files",
-    "hulk_dendrogram", "hulk_dendrogram_files",
+    "hulk_dendrogram", "hulk_dendrogram_files", "hulk_linkage", "hulk_linkage_files",
     "hulk_links", "hulk_links_files", "hulk_link_list_info", "hulk_link_list_row_start", "hulk_link_list_cols",
     "hulk_link_list_distances", "hulk_link_list_free",
 )
@@ -157,6 +159,16 @@ class DendrogramOpts(ctypes.Structure):
 class DendrogramStats(ctypes.Structure):
     _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_offer", ctypes.c_double), ("kernel_ms_fold", ctypes.c_double),
                 ("rounds", ctypes.c_uint32), ("bands", ctypes.c_uint32), ("edges", ctypes.c_uint32), ("components", ctypes.c_uint32)]
+
+
+class LinkageOpts(ctypes.Structure):
+    """hulk_linkage_opts (include/hulk_hip.h)."""
+    _fields_ = [("metric", ctypes.c_int), ("method", ctypes.c_int), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class LinkageStats(ctypes.Structure):
+    _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_matrix", ctypes.c_double), ("kernel_ms_merge", ctypes.c_double),
+                ("merges", ctypes.c_uint32), ("components", ctypes.c_uint32), ("rows_rescanned", ctypes.c_uint64)]
 
 
 class HulkError(RuntimeError):
@@ -374,6 +386,11 @@ def load():
     L.hulk_dendrogram_files.restype = ctypes.c_int
     L.hulk_dendrogram_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, u32, ctypes.c_char_p, dbl, ctypes.c_char_p,
                                         vp, vp, vp, vp, ctypes.POINTER(DendrogramStats), ctypes.c_char_p, u64]
+    L.hulk_linkage.restype = ctypes.c_int
+    L.hulk_linkage.argtypes = [ctypes.c_int, vp, vp, u32, u32, ctypes.POINTER(LinkageOpts), vp, vp, vp, vp, vp, ctypes.POINTER(LinkageStats)]
+    L.hulk_linkage_files.restype = ctypes.c_int
+    L.hulk_linkage_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, u32, ctypes.c_char_p, dbl,
+                                     ctypes.c_char_p, vp, vp, vp, vp, vp, ctypes.POINTER(LinkageStats), ctypes.c_char_p, u64]
     _lib = L
     return L
 

@@ -884,4 +884,73 @@ int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n_paths
     return HULK_OK;
 }
 
+int hulk_linkage_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
+                       const char *method, uint32_t threads, const char *csv_path, double cut_distance, const char *cut_csv_path,
+                       uint32_t *merge_a, uint32_t *merge_b, double *merge_distance, uint32_t *merge_size, uint32_t *n_merges,
+                       hulk_linkage_stats *stats, char *errbuf, uint64_t errbuf_len) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_merges) *n_merges = 0;
+    if (!algo || !metric || !method) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    const std::string metric_s = metric, algo_s = algo, method_s = method;
+    if (!metric_name_ok(metric_s))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
+    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (method_s != "single" && method_s != "complete" && method_s != "average")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied linkage is not available: " + method_s + "\nplease select one of the following: [single complete average]");
+    const bool cut = cut_distance == cut_distance;                  // NaN: no cut
+    if (cut && !(cut_distance >= 0.0 && cut_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_linkage: cut_distance must be in [0, 1] (or NaN: no cut)");
+    if (cut && !cut_csv_path) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_linkage: a cut_distance without a cut_csv_path");
+    hulk_sketch_set *set = nullptr;
+    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
+    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
+    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    const uint32_t n = (uint32_t)set->files.size();
+    std::vector<uint32_t> own_a, own_b, own_s; std::vector<double> own_d;
+    uint32_t m = 0;
+    if (!merge_a) { own_a.resize(n); merge_a = own_a.data(); }
+    if (!merge_b) { own_b.resize(n); merge_b = own_b.data(); }
+    if (!merge_distance) { own_d.resize(n); merge_distance = own_d.data(); }
+    if (!merge_size) { own_s.resize(n); merge_size = own_s.data(); }
+    hulk_linkage_opts o;
+    memset(&o, 0, sizeof o);
+    o.metric = metric_code(metric_s);
+    o.method = method_s == "complete" ? HULK_LINKAGE_COMPLETE : method_s == "average" ? HULK_LINKAGE_AVERAGE : HULK_LINKAGE_SINGLE;
+    {
+        const int rc = hulk_linkage(device, set->mins.data(), set->weights.data(), n, set->size, &o, merge_a, merge_b, merge_distance, merge_size, &m, stats);
+        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
+    }
+    if (n_merges) *n_merges = m;
+    std::vector<std::string> rows((size_t)m + 1);
+    rows[0] = "merge,sketch_a,sketch_b,distance,similarity,size\n";
+    for (uint32_t e = 0; e < m; e++) {
+        std::string &r = rows[(size_t)e + 1];
+        char tmp[64];
+        r += std::to_string(e + 1); r += ',';
+        csv_field(r, set->files[merge_a[e]].path); r += ','; csv_field(r, set->files[merge_b[e]].path); r += ',';
+        snprintf(tmp, sizeof tmp, "%.17g", merge_distance[e]); r += tmp; r += ',';
+        format_f2(r, 100 - (merge_distance[e] * 100));              // cmd/smash.go:217
+        r += ','; r += std::to_string(merge_size[e]); r += '\n';
+    }
+    std::string err;
+    if (csv_path && !write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    if (cut) {
+        // the merges at or below the cut, whatever their place in the order (average linkage may step down by a rounding)
+        std::vector<uint32_t> up(n), label(n);
+        for (uint32_t i = 0; i < n; i++) up[i] = i;
+        auto find = [&](uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; };
+        for (uint32_t e = 0; e < m; e++) {
+            if (!(merge_distance[e] <= cut_distance)) continue;
+            const uint32_t a = find(merge_a[e]), b = find(merge_b[e]);
+            if (a != b) up[std::max(a, b)] = std::min(a, b);
+        }
+        for (uint32_t i = 0; i < n; i++) label[i] = find(i);
+        if (!write_clusters_csv(*set, label.data(), cut_csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    }
+    return HULK_OK;
+}
+
 }  // extern "C"

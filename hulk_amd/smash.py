@@ -9,6 +9,8 @@ cluster / cluster_files: the connected components of "distance <= threshold" ove
 single linkage, without the N x N matrix.
 dendrogram / dendrogram_files: every threshold at once — the minimum spanning forest of the distance graph (hulk_dendrogram,
 hulk_dendrogram_files); cut_dendrogram and linkage_matrix read it on the host.
+linkage / linkage_files: the single-, complete- or average-linkage dendrogram by agglomeration over the N x N matrix, which stays on the
+device (hulk_linkage, hulk_linkage_files); cut_dendrogram and linkage_matrix read its merges too.
 """
 import fnmatch
 import glob
@@ -394,6 +396,80 @@ def dendrogram_files(files, ksize=21, algo="histosketch", metric="jaccard", csv_
     if stats is not None:
         stats.update(_dendrogram_stats_dict(st))
     return ordering, a[:ne.value], b[:ne.value], d[:ne.value]
+
+
+AVAIL_LINKAGES = ["single", "complete", "average"]
+_LINKAGE_CODE = {"single": _lib.HULK_LINKAGE_SINGLE, "complete": _lib.HULK_LINKAGE_COMPLETE, "average": _lib.HULK_LINKAGE_AVERAGE}
+
+
+def _linkage_stats_dict(st):
+    return dict(seconds_total=st.seconds_total, kernel_ms_matrix=st.kernel_ms_matrix, kernel_ms_merge=st.kernel_ms_merge,
+                merges=st.merges, components=st.components, rows_rescanned=st.rows_rescanned)
+
+
+def linkage(mins, weights, method, metric="jaccard", device=0, stats=None):
+    """The dendrogram of a sketch collection under "single", "complete" or "average" linkage, on the GPU (hulk_linkage):
+    -> (a uint32[M], b uint32[M], d float64[M], size uint32[M]), a < b, the merges in the order performed.  With D =
+    distance_matrix(mins, weights, metric) and W = fmin(D, D.T) (+inf where both directions are NaN) the clusters start as the
+    singletons, named by their smallest member; the pair (p, q), p < q, smallest under (d(p, q), p, q) merges into p, and d(p, k)
+    becomes the min / max / size-weighted mean (each operation rounded on its own) of d(p, k) and d(q, k).  M = N - (components of
+    the finite graph).  a and b are members of the merged clusters: cut_dendrogram(N, a, b, d, tau) and linkage_matrix(N, a, b, d)
+    read the result as they read dendrogram()'s.  The N x N matrix stays on the device (8 * N * N bytes, N at most 65,536).
+    stats: a dict that receives seconds_total, kernel_ms_matrix, kernel_ms_merge, merges, components, rows_rescanned."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if method not in AVAIL_LINKAGES:
+        raise HulkError(-30, f"supplied linkage is not available: {method}\nplease select one of the following: {AVAIL_LINKAGES}")
+    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
+    if m.ndim != 2 or (w is not None and m.shape != w.shape):
+        raise ValueError("mins/weights must be [n][sketch_size]")
+    o = _lib.LinkageOpts(metric=_METRIC_CODE[metric], method=_LINKAGE_CODE[method])
+    n = m.shape[0]
+    a = np.zeros(max(n, 1), dtype=np.uint32); b = np.zeros(max(n, 1), dtype=np.uint32); d = np.zeros(max(n, 1), dtype=np.float64)
+    size = np.zeros(max(n, 1), dtype=np.uint32)
+    nm = ctypes.c_uint32(0)
+    st = _lib.LinkageStats()
+    L = _lib.load()
+    rc = L.hulk_linkage(device, m.ctypes.data, None if w is None else w.ctypes.data, n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data,
+                        d.ctypes.data, size.ctypes.data, ctypes.byref(nm), ctypes.byref(st))
+    if rc != 0:
+        raise HulkError(rc, L.hulk_last_error(None).decode())
+    if stats is not None:
+        stats.update(_linkage_stats_dict(st))
+    return a[:nm.value], b[:nm.value], d[:nm.value], size[:nm.value]
+
+
+def linkage_files(files, method, ksize=21, algo="histosketch", metric="jaccard", csv_path=None, cut_distance=None, cut_csv_path=None,
+                  threads=0, device=0, stats=None):
+    """The directory form (hulk_linkage_files): dendrogram_files' loader, CSV ("merge,sketch_a,sketch_b,distance,similarity,size", one
+    line per merge in the order performed) and cut (the clusters file of the merges with distance <= cut_distance: what
+    cut_dendrogram gives), under the linkage `method`.  -> (ordering, a, b, d, size); ordering = the sorted unique paths."""
+    import ctypes
+    if metric not in AVAIL_METRICS:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    if algo not in AVAIL_ALGORITHMS:
+        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    if method not in AVAIL_LINKAGES:
+        raise HulkError(-30, f"supplied linkage is not available: {method}\nplease select one of the following: {AVAIL_LINKAGES}")
+    ordering = sorted(set(files))
+    n = max(len(ordering), 1)
+    a = np.zeros(n, dtype=np.uint32); b = np.zeros(n, dtype=np.uint32); d = np.zeros(n, dtype=np.float64); size = np.zeros(n, dtype=np.uint32)
+    nm = ctypes.c_uint32(0)
+    arr, n_paths = _paths(files)
+    st = _lib.LinkageStats()
+    err = ctypes.create_string_buffer(4096)
+    L = _lib.load()
+    rc = L.hulk_linkage_files(device, arr, n_paths, ksize, algo.encode(), metric.encode(), method.encode(), threads,
+                              None if csv_path is None else os.fsencode(csv_path),
+                              float("nan") if cut_distance is None else float(cut_distance),
+                              None if cut_csv_path is None else os.fsencode(cut_csv_path),
+                              a.ctypes.data, b.ctypes.data, d.ctypes.data, size.ctypes.data, ctypes.byref(nm), ctypes.byref(st), err, len(err))
+    if rc != 0:
+        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    if stats is not None:
+        stats.update(_linkage_stats_dict(st))
+    return ordering, a[:nm.value], b[:nm.value], d[:nm.value], size[:nm.value]
 
 
 def cut_dendrogram(n, a, b, d, max_distance):

@@ -16,6 +16,8 @@
 //   (none: the k nearest sketches of a database for every query sketch)   hulk::Search (HULKdata.GetDistance per pair)
 //   (none: the sketches of a collection grouped at a distance threshold)  hulk::Cluster / hulk::ClusterFiles (single linkage)
 //   (none: every threshold at once, the single-linkage dendrogram)         hulk::Dendrogram / hulk::DendrogramFiles
+//   (none: the complete- and average-linkage dendrograms the paper's       hulk::Linkage / hulk::LinkageFiles
+//       notebooks draw with sns.clustermap from `smash`'s matrix)
 //
 // Header only; link with -lhulkhip.  A Boss is single-caller, like SeqMinimizer.Run's goroutine.
 #ifndef HULK_HPP
@@ -521,6 +523,62 @@ inline std::vector<DendrogramEdge> DendrogramFiles(const std::vector<std::string
     if (rc != HULK_OK) throw Error(rc, err);
     std::vector<DendrogramEdge> out(m);
     for (uint32_t e = 0; e < m; e++) { out[e].A = a[e]; out[e].B = b[e]; out[e].Distance = d[e]; }
+    return out;
+}
+
+// The dendrogram of a collection under "single", "complete" or "average" linkage, on the GPU (hulk_linkage): the agglomeration over
+// W = fmin(Smash's [i][j], [j][i]) (two NaNs: +inf, never merged); clusters are named by their smallest member and the pair (A, B),
+// A < B, smallest under (distance, A, B) merges into A.  The merges come in the order performed; Size: the members of the union.
+struct LinkageMerge { uint32_t A = 0, B = 0; double Distance = 0; uint32_t Size = 0; };
+inline int LinkageCode(const std::string &method) {
+    if (method == "single") return HULK_LINKAGE_SINGLE;
+    if (method == "complete") return HULK_LINKAGE_COMPLETE;
+    if (method == "average") return HULK_LINKAGE_AVERAGE;
+    throw Error(HULK_ERR_ARG, "supplied linkage is not available: " + method + "\nplease select one of the following: [single complete average]");
+}
+inline std::vector<LinkageMerge> Linkage(const std::vector<HistoSketch> &sketches, const std::string &method, const std::string &metric,
+                                         int device = 0, hulk_linkage_stats *stats = nullptr) {
+    const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
+    std::vector<uint64_t> mins((size_t)N * S + 1);
+    std::vector<double> weights((size_t)N * S + 1);
+    for (uint32_t i = 0; i < N; i++) {
+        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
+            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
+        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
+        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
+    }
+    hulk_linkage_opts o = hulk_linkage_opts();
+    o.method = LinkageCode(method);
+    o.metric = MetricCode(metric);
+    std::vector<uint32_t> a((size_t)N + 1), b((size_t)N + 1), s((size_t)N + 1);
+    std::vector<double> d((size_t)N + 1);
+    uint32_t m = 0;
+    const int rc = hulk_linkage(device, mins.data(), weights.data(), N, S, &o, a.data(), b.data(), d.data(), s.data(), &m, stats);
+    if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+    std::vector<LinkageMerge> out(m);
+    for (uint32_t e = 0; e < m; e++) { out[e].A = a[e]; out[e].B = b[e]; out[e].Distance = d[e]; out[e].Size = s[e]; }
+    return out;
+}
+
+// The directory form (hulk_linkage_files): DendrogramFiles' loader, files and cut under the linkage `method`.
+inline std::vector<LinkageMerge> LinkageFiles(const std::vector<std::string> &jsonFiles, uint32_t kSize, const std::string &algo,
+                                              const std::string &metric, const std::string &method, const std::string &dendrogramCSV = std::string(),
+                                              double cutDistance = std::numeric_limits<double>::quiet_NaN(),
+                                              const std::string &clustersCSV = std::string(), hulk_linkage_stats *stats = nullptr,
+                                              int device = 0, uint32_t threads = 0) {
+    std::vector<const char *> ptr;
+    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
+    const size_t n = jsonFiles.size() + 1;
+    std::vector<uint32_t> a(n), b(n), s(n);
+    std::vector<double> d(n);
+    uint32_t m = 0;
+    char err[4096] = {0};
+    const int rc = hulk_linkage_files(device, ptr.data(), (uint32_t)ptr.size(), kSize, algo.c_str(), metric.c_str(), method.c_str(), threads,
+                                      dendrogramCSV.empty() ? nullptr : dendrogramCSV.c_str(), cutDistance,
+                                      clustersCSV.empty() ? nullptr : clustersCSV.c_str(), a.data(), b.data(), d.data(), s.data(), &m, stats, err, sizeof err);
+    if (rc != HULK_OK) throw Error(rc, err);
+    std::vector<LinkageMerge> out(m);
+    for (uint32_t e = 0; e < m; e++) { out[e].A = a[e]; out[e].B = b[e]; out[e].Distance = d[e]; out[e].Size = s[e]; }
     return out;
 }
 

@@ -68,7 +68,8 @@ extern "C" {
  *    sketch snapshots (hulk_set_snapshots, hulk_snapshot_count, hulk_get_snapshots, hulk_set_snapshot_callback, hulk_poll_snapshots);
  *    a panel the snapshots are scored against (hulk_set_panel, hulk_get_snapshot_distances, hulk_set_snapshot_panel_callback,
  *    hulk_panel_distances); the nearest-neighbour search (hulk_search, hulk_search_files); single-linkage clustering (hulk_cluster,
- *    hulk_cluster_files) and its dendrogram (hulk_dendrogram, hulk_dendrogram_files).
+ *    hulk_cluster_files) and its dendrogram (hulk_dendrogram, hulk_dendrogram_files); complete- and average-linkage dendrograms
+ *    (hulk_linkage, hulk_linkage_files).
  * Bindings compare it with the value they were written for. */
 #define HULK_ABI_VERSION 4
 
@@ -780,6 +781,60 @@ int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n, uint
                           uint32_t threads, const char *csv_path, double cut_distance /* NaN: no cut */, const char *cut_csv_path,
                           uint32_t *edge_a, uint32_t *edge_b, double *edge_distance, uint32_t *n_edges,
                           hulk_dendrogram_stats *stats, char *errbuf, uint64_t errbuf_len);
+
+/* ---- single-, complete- and average-linkage dendrograms of a sketch collection -----------------------------------------------------
+ * D = the matrix hulk_smash gives for the set, bit for bit; W[i][j] = fmin(D[i][j], D[j][i]) for i != j, as in hulk_dendrogram; a pair
+ * whose two directions are NaN has W = +inf and never merges.  Clusters start as the n singletons and are named by their smallest
+ * member.  While some pair of live clusters is at a finite distance, the pair (p, q), p < q, that is smallest under the key
+ * (d(p, q), p, q) merges: merge t = (p, q, d(p, q), size_p + size_q), the union keeps the name p, and for every other live k
+ *   HULK_LINKAGE_SINGLE    d(p, k) = min(d(p, k), d(q, k))
+ *   HULK_LINKAGE_COMPLETE  d(p, k) = max(d(p, k), d(q, k))
+ *   HULK_LINKAGE_AVERAGE   d(p, k) = (n_p * d(p, k) + n_q * d(q, k)) / (n_p + n_q): n_p, n_q the sizes before the merge as doubles,
+ *                          each of the two products, the sum and the quotient rounded on its own (no fused multiply-add); +inf propagates
+ * *n_merges = n - (the clusters left when no finite pair remains): under single linkage the connected components of the finite graph;
+ * under complete and average linkage +inf propagates, so a pair at +inf keeps its two clusters apart for good and more may be left.
+ * merge_a[t] < merge_b[t], merge_distance[t] and merge_size[t], n - 1 entries each, receive the merges in the order performed.  The heights are non-decreasing exactly for single and complete; for average they
+ * are non-decreasing up to the rounding of the update, and nothing more is promised.  merge_a / merge_b are members of the two
+ * clusters (their smallest): a union-find over the merges in order rebuilds every cluster.  Under HULK_LINKAGE_SINGLE the heights are
+ * hulk_dendrogram's edge distances as a multiset and every cut gives hulk_cluster's labels; hulk_dendrogram computes that tree without
+ * the matrix.  A function of the inputs alone, however many distances tie: launch shapes, chunks and scheduling cannot change a bit.
+ * The n x n matrix lives on the device only: 8 * n * n bytes (n at most HULK_LINKAGE_MAX_N) beside the set; free device memory is
+ * checked before anything is allocated, and a matrix that does not fit is refused with HULK_ERR_HIP and a text that names the bytes
+ * needed.  hulk_smash's matrix kernel fills D, k_linkage_sym (hulk_linkage.hip) makes W in place; per row the nearest live neighbour
+ * behind it is cached under the key, and every merge is three launches of fixed shape (k_linkage_pick, k_linkage_update,
+ * k_linkage_rescan) that take p, q and "finished" from device memory: the host queues them without a synchronisation per merge and
+ * looks at "finished" once per 4096 merges.
+ * HULK_ERR_ARG before any HIP call, with a text in hulk_last_error(NULL): NULL arrays (weights may be NULL for bottomk), opts or
+ * n_merges; n or sketch_size == 0; an unknown metric or method; bottomk above HULK_MINHASH_MAX_SKETCH; non-zero flags or reserved; n
+ * above HULK_LINKAGE_MAX_N.  n == 1 is valid: 0 merges. */
+#define HULK_LINKAGE_SINGLE 0
+#define HULK_LINKAGE_COMPLETE 1
+#define HULK_LINKAGE_AVERAGE 2
+#define HULK_LINKAGE_MAX_N 65536u
+typedef struct hulk_linkage_opts {
+    int metric;            /* HULK_METRIC_JACCARD / HULK_METRIC_WEIGHTED_JACCARD / HULK_METRIC_BOTTOMK */
+    int method;            /* HULK_LINKAGE_SINGLE / HULK_LINKAGE_COMPLETE / HULK_LINKAGE_AVERAGE */
+    uint32_t flags;        /* zero */
+    uint64_t reserved[4];  /* zero */
+} hulk_linkage_opts;
+typedef struct hulk_linkage_stats {
+    double seconds_total, kernel_ms_matrix, kernel_ms_merge;   /* the whole call; the matrix kernel and k_linkage_sym; the cache's first fill and every merge (HIP events around each phase) */
+    uint32_t merges, components;
+    uint64_t rows_rescanned;   /* rows k_linkage_rescan scanned, the n of the first fill included */
+} hulk_linkage_stats;
+int hulk_linkage(int device, const uint64_t *mins, const double *weights, uint32_t n, uint32_t sketch_size,
+                 const hulk_linkage_opts *opts, uint32_t *merge_a, uint32_t *merge_b, double *merge_distance,
+                 uint32_t *merge_size /* n - 1 each */, uint32_t *n_merges, hulk_linkage_stats *stats);
+/* The directory form: hulk_dendrogram_files' loader, error texts and their order, metric and algo names and checks; method:
+ * "single" | "complete" | "average".  merge_a / merge_b / merge_distance / merge_size [unique paths - 1] and n_merges may be NULL.
+ * csv_path != NULL: hulk_dendrogram_files' file — the header "merge,sketch_a,sketch_b,distance,similarity,size" and one line per
+ * merge in the order performed.  cut_distance in [0, 1] and cut_csv_path != NULL: "sketch,cluster,size,representative" for the
+ * clusters that the merges with distance <= cut_distance build (a union-find over them, labels the smallest members); cut_distance
+ * NaN: no cut; any other cut_distance, or one in [0, 1] without a cut_csv_path, is HULK_ERR_ARG. */
+int hulk_linkage_files(int device, const char *const *paths, uint32_t n, uint32_t ksize, const char *algo, const char *metric,
+                       const char *method, uint32_t threads, const char *csv_path, double cut_distance /* NaN: no cut */,
+                       const char *cut_csv_path, uint32_t *merge_a, uint32_t *merge_b, double *merge_distance, uint32_t *merge_size,
+                       uint32_t *n_merges, hulk_linkage_stats *stats, char *errbuf, uint64_t errbuf_len);
 
 /* Device self-test: the jump hash replaces the fp64 division 2^31/r by a Newton reciprocal; this
  * checks RN(1/r) against IEEE division for EVERY r in [1, 2^31] and returns the mismatch count. */
