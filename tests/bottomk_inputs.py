@@ -180,3 +180,84 @@ def planted_set(n, s):
     rows = rows[:n]
     fill = random_set(n - len(rows), s, 77 + s) if n > len(rows) else np.zeros((0, s), dtype=np.uint64)
     return np.vstack([np.array(rows, dtype=np.uint64).reshape(len(rows), s), fill])
+
+
+NO_TEST = "the inputs are no test: "
+# ragged sizes above one position per thread of the preparation: E = ceil(S / PREP_THREADS) is 2, 3, 4, 9 and 16, the last threads own a
+# partial range of positions or none, and the sorting network for the next power of two skips a large share of its comparators
+RAGGED_SIZES = (257, 513, 1000, 2049, 4095)
+
+
+def prep_split(s):
+    """(E, threads that own a full range of E positions, positions of the partial one behind them, threads that own nothing)"""
+    t = tile_constants()["PREP_THREADS"]
+    e = -(-s // t)
+    return e, s // e, s % e, t - -(-s // e)
+
+
+def check_ragged_sizes():
+    """what the sizes claim: E > 1, a ragged end, and a network in which many comparators have no upper end"""
+    seen = set()
+    for s in RAGGED_SIZES:
+        e, full, part, idle = prep_split(s)
+        assert e > 1 and full * e + part == s, (s, e, full, part)
+        assert part or idle, NO_TEST + f"S {s}: every thread of the preparation owns a full range"
+        seen.add((part > 0, idle > 0))
+        p2 = 1 << (s - 1).bit_length()
+        assert p2 > s, NO_TEST + f"S {s} is a power of two: the network skips nothing"
+    assert {(True, False), (False, True)} <= seen or (True, True) in seen, NO_TEST + "no size with a partial range, or none with idle threads"
+
+
+@functools.lru_cache(maxsize=None)
+def tied_collection(s):
+    """130 sketches whose values come from a small range: ties between pairs abound"""
+    m = random_set(130, s, 130 + s, spread=2)
+    D = matrix(m)
+    off = D[~np.eye(len(m), dtype=bool)]
+    assert len(np.unique(off)) * 8 < off.size, NO_TEST + "few ties"
+    assert ((off > 0) & (off < 1)).mean() > 0.9, NO_TEST + "distances at the ends"
+    m.setflags(write=False); D.setflags(write=False)
+    return m, D
+
+
+def closest_pair(D):
+    """(a, b), a < b: the pair with the smallest key (distance, a, b) — the first edge of Kruskal's tree, the first merge of every
+    linkage, hit 0 of a's self search"""
+    n = len(D)
+    iu = np.triu_indices(n, 1)
+    at = np.lexsort((iu[1], iu[0], D[iu]))[0]
+    return int(iu[0][at]), int(iu[1][at])
+
+
+def density_set(n, s, seed=9):
+    """n lists of s values of very different density over one pool of s distinct values, 0 and the largest uint64 among them: list 0 is s
+    copies of one value, list 1 the s distinct values, lists 2 and 3 s copies of MaxUint64 and of 0, the others hold a geometric ladder
+    of 2 .. s - 1 distinct values with uneven multiplicities.  The tile's windows then advance at very different rates.  Shuffled"""
+    assert n >= 8 and s >= 16
+    rng = np.random.default_rng(seed + s)
+    inner = np.unique(rng.integers(1, 2 ** 63, size=2 * s, dtype=np.uint64) * np.uint64(2) + np.uint64(1))[:s - 2]
+    pool = np.sort(cat([0, U64_MAX], rng.permutation(inner)[:s - 2]))
+    assert len(pool) == s and len(np.unique(pool)) == s
+    rows = [np.full(s, pool[s // 2], dtype=np.uint64), pool.copy(), np.full(s, U64_MAX, dtype=np.uint64), np.zeros(s, dtype=np.uint64)]
+    ladder = np.unique(np.rint(np.geomspace(2, s - 1, n - 4)).astype(np.int64))
+    for r in range(n - 4):
+        d = int(ladder[r % len(ladder)])
+        vals = np.sort(rng.choice(pool[1:-1], size=d - (r % 3 != 0) - (r % 2 != 0), replace=False))
+        vals = cat([0] if r % 3 else [], vals, [U64_MAX] if r % 2 else [])
+        extra = rng.multinomial(s - d, rng.dirichlet(np.full(d, 0.3)))
+        rows.append(from_runs(vals, 1 + extra))
+    return np.array([rng.permutation(r) for r in rows], dtype=np.uint64)
+
+
+def check_density_set(n, s):
+    m = density_set(n, s)
+    assert m.shape == (n, s)
+    distinct = np.array([len(np.unique(r)) for r in m])
+    assert distinct[0] == 1 and distinct[1] == s and distinct.min() == 1 and distinct.max() == s, NO_TEST + "no list of one value or none of s"
+    assert len(set(distinct.tolist())) >= min(n - 4, 12), NO_TEST + f"the densities are {sorted(set(distinct.tolist()))}"
+    assert (m == 0).any(axis=1).sum() >= n // 3 and (m == U64_MAX).any(axis=1).sum() >= n // 3, NO_TEST + "0 and MaxUint64 are rare"
+    D = matrix(m)
+    off = D[~np.eye(n, dtype=bool)]
+    assert ((off > 0) & (off < 1)).mean() > 0.6, NO_TEST + "most distances are 0 or 1"
+    assert D[0, 1] == 1.0 - 1.0 / s and D[2, 3] == 1.0 and D[1, 2] == 1.0 - 1.0 / s, "the yardstick on the hand-worked pairs"
+    return m, D

@@ -216,7 +216,20 @@ def test_the_yardstick_is_the_counter_intersection_on_random_multisets():
     assert bi.go_similarity([9, 9, 9, 1, 2], [9, 9, 3, 4, 5]) == 2 / 5
 
 
-@pytest.mark.parametrize("s", [1, 2, 31, 33, 50, 512, 4096])
+def test_the_ragged_sizes_and_the_density_set_are_what_they_claim():
+    """S = 257 .. 4095: more than one position per thread of the preparation and a ragged end; the set of tests/test_gpu_bottomk.py's
+    density test holds a list of one value, a list of S values and a ladder between them"""
+    bi.check_ragged_sizes()
+    assert [bi.prep_split(s)[0] for s in bi.RAGGED_SIZES] == [2, 3, 4, 9, 16]
+    bi.check_density_set(40, 1000)
+    # the collection that goes through every user of the tile at S = 2049: ties abound, and its closest pair is one distance to follow
+    m, D = bi.tied_collection(2049)
+    a, b = bi.closest_pair(D)
+    assert a < b and D[a, b] == D[~np.eye(len(D), dtype=bool)].min() and 0 < D[a, b] < 1
+    assert not (D[a, :b] == D[a, b]).any(), "b is the first sketch at that distance from a"
+
+
+@pytest.mark.parametrize("s", [1, 2, 31, 33, 50, 512, 4096] + list(bi.RAGGED_SIZES))
 def test_the_planted_pairs_are_what_they_claim(s):
     from oracle import pyorc
     c = bi.tile_constants()

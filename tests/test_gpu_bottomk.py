@@ -4,7 +4,11 @@ tests/bottomk_inputs.py, which is KMVsketch.GetSimilarity (kmv.go:119-159) resta
 Planted pairs with the intersection worked out by hand, alone (N = 2) and inside sets of 33, 65 and 97 sketches, at S = 1, 2, 31, 33,
 50 and 512; the largest sketch the metric takes (4096) and the smallest; the order of a sketch's values; N around the tile's 32 and
 64; and the four users of the tile — hulk_smash's matrix, hulk_search, hulk_cluster, hulk_dendrogram — on one collection full of ties;
-and `sketch --kmv --feedMinHash` to `smash -a kmv -m bottomk` end to end.  Shapes are the smallest that can break the kernels."""
+and `sketch --kmv --feedMinHash` to `smash -a kmv -m bottomk` end to end.  Shapes are the smallest that can break the kernels.
+
+Above one position per thread of the preparation the sizes are ragged on purpose — 257, 513, 1000, 2049, 4095 (bottomk_inputs.RAGGED_SIZES):
+the planted pairs and sets at each, the four orders of a sketch's values at 1000, every user of the tile (links and the three
+linkages too) at 2049 with the closest pair's distance followed through all of them, and a set of lists of 1 .. S distinct values."""
 import functools
 import io
 import os
@@ -16,9 +20,13 @@ import pytest
 import bottomk_inputs as bi
 import cluster_inputs as ci
 import dendrogram_inputs as di
+import linkage_inputs as lni
+import links_inputs as lki
 from conftest import pack_reads
 from test_gpu_cluster import assert_same as assert_same_clusters, run as run_cluster
 from test_gpu_dendrogram import assert_same as assert_same_edges, run as run_dendrogram
+from test_gpu_linkage import assert_same as assert_same_merges, run as run_linkage
+from test_gpu_links import run as run_links
 from test_gpu_search import assert_hits, bits, select
 
 pytestmark = pytest.mark.gpu
@@ -38,13 +46,24 @@ def assert_matrix(got, want, what):
 @functools.lru_cache(maxsize=None)
 def planted_reference(n, s):
     m = bi.planted_set(n, s)
-    D = bi.matrix(m)
+    D = bi.matrix(m, sample=300 if s <= 512 else 100)               # (the pairs the yardstick's two forms are compared on)
     m.setflags(write=False); D.setflags(write=False)
     return m, D
 
 
 @pytest.mark.parametrize("s", [1, 2, 31, 33, 50, 512])
 def test_planted_pairs(s):
+    planted(s, (33, 65, 97))
+
+
+@pytest.mark.parametrize("s", bi.RAGGED_SIZES)
+def test_planted_pairs_at_ragged_sizes(s):
+    """S = 257 .. 4095: k_bottomk_prep finds the run heads with E = 2 .. 16 positions a thread, the last threads own a partial range or
+    none, and the network skips every comparator whose upper end is not below S (tests/bottomk_inputs.py: check_ragged_sizes)"""
+    planted(s, (33, 65))
+
+
+def planted(s, ns):
     from oracle import pyorc
     for name, a, b, want in bi.planted_pairs(s):
         m = np.vstack([a, b])
@@ -59,7 +78,7 @@ def test_planted_pairs(s):
             J = gpu_matrix(srt, "jaccard", np.zeros(srt.shape))
             assert J[0, 1] == 1.0 == pyorc.smash_matrix(srt, np.zeros(srt.shape), "jaccard")[0, 1] and D[0, 1] == 1.0 - (s - 1) / s
             assert_matrix(gpu_matrix(srt), D, f"S {s} {name}, sorted")
-    for n in (33, 65, 97):
+    for n in ns:
         m, want = planted_reference(n, s)
         assert_matrix(gpu_matrix(m), want, f"N {n} S {s} planted set")
 
@@ -79,7 +98,7 @@ def test_the_largest_and_the_smallest_sketch():
     assert D[0, 1] == 0.0 and D[0, 2] == 1.0 and D[3, 5] == 0.0 and D[3, 4] == 1.0
 
 
-@pytest.mark.parametrize("s", [50, 512])
+@pytest.mark.parametrize("s", [50, 512, 1000])
 def test_the_order_of_a_sketchs_values_does_not_matter(s):
     m = bi.random_set(70, s, 31 + s)
     want = bi.matrix(m)
@@ -111,24 +130,71 @@ def test_tile_borders():
             assert (got[2] == min(n - 1, 64)).all()
 
 
-@functools.lru_cache(maxsize=None)
 def collection(s):
-    """130 sketches whose values come from a small range: ties between pairs abound"""
-    m = bi.random_set(130, s, 130 + s, spread=2)
-    D = bi.matrix(m)
-    off = D[~np.eye(len(m), dtype=bool)]
-    assert len(np.unique(off)) * 8 < off.size, bi_no_test("few ties")
-    assert ((off > 0) & (off < 1)).mean() > 0.9, bi_no_test("distances at the ends")
-    m.setflags(write=False); D.setflags(write=False)
-    return m, D
+    """130 sketches whose values come from a small range: ties between pairs abound (tests/bottomk_inputs.py checks that they do)"""
+    return bi.tied_collection(s)
 
 
 def bi_no_test(why):
-    return "the inputs are no test: " + why
+    return bi.NO_TEST + why
 
 
 @pytest.mark.parametrize("s", [50, 512])
 def test_the_four_users_agree(s):
+    four_users(s)
+
+
+def test_every_user_of_the_tile_agrees_at_2049():
+    """S = 2049 (nine positions a thread of the preparation, a ragged end) through the matrix, search, cluster, dendrogram — as at 50 and
+    512 — and links and the three linkages; the closest pair of the collection is one distance, and it has the same bits wherever a
+    user reports it"""
+    from hulk_amd.smash import search
+    s = 2049
+    four_users(s)
+    m, D = collection(s)
+    n = len(m)
+    a, b = bi.closest_pair(D)
+    seen = {"yardstick": bits(D[a, b]).item(), "matrix": bits(gpu_matrix(m)[a, b]).item()}
+    index, dist, count = search(m, None, None, None, 1, "bottomk", self_search=True)
+    assert index[a, 0] == b and count[a] == 1
+    seen["search"] = bits(dist[a, 0]).item()
+    tau = float(D[a, b])
+    for band in (32, 0):
+        got = run_links(m, None, tau, "bottomk", band)
+        lki.assert_same(got, lki.csr(D, tau), f"N {n} S {s} links at tau {tau!r} band_rows {band}")
+    ptr, idx, ld = got
+    row = idx[int(ptr[a]):int(ptr[a + 1])].tolist()
+    assert row[0] == b and int(ptr[-1]) >= 2, "at the smallest distance of the set a's first link is b"
+    seen["links"] = bits(ld[int(ptr[a])]).item()
+    off = np.unique(D[~np.eye(n, dtype=bool)])
+    mid = float(off[len(off) // 8])
+    lki.assert_same(run_links(m, None, mid, "bottomk", 32), lki.csr(D, mid), f"N {n} S {s} links at tau {mid!r}")
+    (ea, eb, ed), _ = run_dendrogram(m, None, "bottomk", 0)
+    assert (int(ea[0]), int(eb[0])) == (a, b)
+    seen["dendrogram"] = bits(ed[0]).item()
+    for method in lni.METHODS:
+        got, _ = run_linkage(m, None, method, "bottomk")
+        assert_same_merges(got, lni.agglomerate(D, method), f"N {n} S {s} {method} linkage")
+        assert (int(got[0][0]), int(got[1][0])) == (a, b)
+        seen[method] = bits(got[2][0]).item()
+    print(f"S {s}: the closest pair ({a}, {b}) at {D[a, b]!r} as {sorted(seen)}")
+    assert len(set(seen.values())) == 1 and len(seen) == 8, seen
+
+
+def test_lists_of_very_different_density():
+    """a list of S copies of one value, a list of S distinct values, MaxUint64 and 0 S times over, and a ladder of densities between
+    them at S = 1000: the tile's windows advance at very different rates (many short rounds) and stay exact"""
+    from hulk_amd.smash import search
+    n, s = 40, 1000
+    m, D = bi.check_density_set(n, s)
+    assert_matrix(gpu_matrix(m), D, f"N {n} S {s} density set")
+    assert_matrix(gpu_matrix(np.sort(m, axis=1)), D, f"N {n} S {s} density set, ascending")
+    assert_hits(search(m, None, None, None, 33, "bottomk", self_search=True), select(D, 33, no_diagonal=True), f"N {n} S {s} density set, self search")
+    for tau in (0.5, 1.0 - 1.0 / s):
+        assert_same_clusters(run_cluster(m, None, tau, "bottomk"), ci.components(D, tau), f"N {n} S {s} density set, tau {tau!r}")
+
+
+def four_users(s):
     from hulk_amd.smash import search
     m, D = collection(s)
     n = len(m)

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, pack_reads
+from minhash_inputs import U64_MAX, fed_values, khf_merge_reference, khf_reference, kmv_reference, n_reads
 from oracle import pyorc
-from test_minhash_cpu import U64_MAX, khf_merge_reference, khf_reference, kmv_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -25,18 +25,10 @@ def flags_both():
     return _lib.HULK_FLAG_KMV | _lib.HULK_FLAG_KHF
 
 
-def fed_values(bases, offsets, k, w=W):
-    """every AddHash argument of the stream, in read order"""
-    raw = np.ascontiguousarray(bases, dtype=np.uint8).tobytes()
-    off = [int(x) for x in offsets]
-    parts = [pyorc.minimizers(raw[off[i]:off[i + 1]], k, w) for i in range(len(off) - 1)]
-    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
-
-
-def sketcher(k, S, **kw):
+def sketcher(k, S, w=W, **kw):
     import hulk_amd
     kw.setdefault("flags", flags_both())
-    return hulk_amd.GpuSketcher(k, W, S, **kw)
+    return hulk_amd.GpuSketcher(k, w, S, **kw)
 
 
 def assert_minhash(g, vals, S, what=""):
@@ -86,19 +78,6 @@ def test_fewer_values_than_slots_and_an_empty_context(fq_reads):
     kmv, _ = assert_minhash(g, vals, 512)
     assert len(kmv) == len(vals) < 512
     g.close()
-
-
-def n_reads(seed, n, lo, hi, n_frac=0.0):
-    """n random reads of lo..hi bases; a fraction of them carries N (code 4) and lower-case bases"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        s = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=int(rng.integers(lo, hi + 1)))].copy()
-        if rng.random() < n_frac:
-            s[rng.integers(0, len(s), size=3)] = ord("N")
-            s[rng.integers(0, len(s), size=5)] |= 32
-        out.append(s.tobytes())
-    return out
 
 
 @pytest.mark.parametrize("k", [21, 31])

@@ -2,8 +2,8 @@
 
 The yardstick throughout is oracle.pyorc.smash_matrix over the stack [queries; database], as in tests/test_gpu_panel.py: block
 [:m, m:] for role "row", [m:, :m].T for role "column"; then the selection in numpy — mask NaN and the values above max_distance,
-np.lexsort((index, distance)), the first K.  Indices are compared exactly, distances on the uint64 view, and behind count[i] the
-entries must be 0xFFFFFFFF / NaN."""
+np.lexsort((index, distance)), the first K (tests/search_inputs.py).  Indices are compared exactly, distances on the uint64 view,
+and behind count[i] the entries must be 0xFFFFFFFF / NaN."""
 import functools
 import os
 import subprocess
@@ -11,43 +11,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import search_inputs as si
 from conftest import ROOT
-from oracle import pyorc
+from search_inputs import NONE, bits, blocks, select          # (the yardstick: one definition, the tests of other modules import it from here)
 from test_gpu_panel import make_sketches
 
 pytestmark = pytest.mark.gpu
 
 VARIANTS = [("jaccard", "row"), ("jaccard", "column"), ("weightedjaccard", "row"), ("weightedjaccard", "column")]
 MS, PS, KS = (1, 31, 32, 33, 65), (1, 63, 64, 65, 257), (1, 5, 64)
-NONE = 0xFFFFFFFF
 MAXF = 1.7976931348623157e308
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def blocks(qm, qw, dm, dw, metric):
-    """one call of the yardstick over [queries; database] -> {"row": [m][P], "column": [m][P]}"""
-    m = len(qm)
-    full = pyorc.smash_matrix(np.vstack([qm, dm]), np.vstack([qw, dw]), metric)
-    return {"row": np.ascontiguousarray(full[:m, m:]), "column": np.ascontiguousarray(full[m:, :m].T)}
-
-
-def select(D, k, max_distance=None, no_diagonal=False):
-    """the hit lists of the issue's rule, from the distances [m][P]"""
-    m, P = D.shape
-    index = np.full((m, k), NONE, dtype=np.uint32); dist = np.full((m, k), np.nan); count = np.zeros(m, dtype=np.uint32)
-    for i in range(m):
-        ok = ~np.isnan(D[i])
-        if max_distance is not None and 0 <= max_distance <= 1:
-            ok &= D[i] <= max_distance
-        if no_diagonal:
-            ok[i] = False
-        cand = np.nonzero(ok)[0]
-        order = cand[np.lexsort((cand, D[i][cand]))][:k]
-        count[i] = len(order); index[i, :len(order)] = order; dist[i, :len(order)] = D[i][order]
-    return index, dist, count
 
 
 def assert_hits(got, want, what):
@@ -234,6 +207,81 @@ def test_self_search():
             assert (plain[0][diag_ok, 0] == np.nonzero(diag_ok)[0]).all(), "without the flag the diagonal is hit 0 wherever it is not NaN"
             if metric == "weightedjaccard":
                 assert not diag_ok[7] or role == "column"
+
+
+# ---- 5b. beyond one pass of the selection -------------------------------------------------------------------------------------------
+# k_search_select reads a strip's row 512 distances a pass.  Five queries against up to 1100 sketches: tests/search_inputs.py has the
+# inputs and the conditions that make them a test (they run without a GPU in tests/test_search_cpu.py)
+@pytest.mark.parametrize("p", si.LONG_PS)
+@pytest.mark.parametrize("s,metric", si.LONG_CASES)
+def test_one_strip_longer_than_one_pass(s, metric, p):
+    """one strip of 511, 512, 513 (a second pass of one candidate, and that one a hit), 1023, 1024, 1025 and 1100 sketches (a third
+    pass with a tail); K = 1, 2, 33, 63, 64 thinned over the strip lengths and the two roles (tests/search_inputs.py: thinned)"""
+    from hulk_amd.smash import search
+    qm, qw, dm, dw = si.long_inputs(s)
+    ran = 0
+    for role in si.ROLES:
+        D = si.long_blocks(s, metric)[role]
+        for k in [k for pp, k in si.thinned(role) if pp == p]:
+            st = {}
+            got = search(qm, qw, dm[:p], dw[:p], k, metric, role, stats=st)
+            assert (st["strips"], st["query_blocks"]) == (1, 1), st
+            assert_hits(got, select(D[:, :p], k), f"P {p} S {s} K {k} {metric} {role}")
+            ran += 1
+    assert ran == len(si.LONG_KS), "every K meets this P, under one role or the other"
+
+
+@pytest.mark.parametrize("s,metric", si.LONG_CASES)
+def test_two_strips_longer_than_one_pass(s, metric):
+    """1100 sketches in strips of 576 and 524: the second strip starts at pbase = 576 and has a second pass with a tail of its own"""
+    from hulk_amd.smash import search
+    si.check_long_strips(s, metric)
+    qm, qw, dm, dw = si.long_inputs(s)
+    for role in si.ROLES:
+        D = si.long_blocks(s, metric)[role]
+        for k in si.LONG_KS:
+            st = {}
+            got = search(qm, qw, dm, dw, k, metric, role, scratch_bytes=si.strip_scratch(s), stats=st)
+            assert st["strips"] == 2, st
+            assert_hits(got, select(D, k), f"P {si.LONG_P} S {s} K {k} {metric} {role} in strips of {si.STRIP}")
+
+
+@pytest.mark.parametrize("order", si.ORDERS)
+@pytest.mark.parametrize("s,metric", si.LONG_CASES)
+def test_database_orders_made_for_the_selection(s, metric, order):
+    """P = 1100, K = 64.  descending by the distance to query 0: candidate after candidate enters at rank 0 and the tail moves up;
+    ascending: nothing enters after the first K; 1100 identical sketches: every key ties and the index alone decides; copies of query
+    0's nearest sketch at 509 .. 515: a run of equal distances across the border of the first pass"""
+    from hulk_amd.smash import search
+    qm, qw, _, _ = si.long_inputs(s)
+    for role in si.ROLES:
+        entered = si.check_orders(s, metric, role)[order]
+        dm, dw, D = si.ordered_database(s, metric, role, order)
+        print(f"S {s} {metric} {role} {order}: {entered} of {si.LONG_P} candidates enter query 0's list")
+        want = select(D, si.LONG_K)
+        for scratch in (0, si.strip_scratch(s)):
+            got = search(qm, qw, dm, dw, si.LONG_K, metric, role, scratch_bytes=scratch)
+            assert_hits(got, want, f"P {si.LONG_P} S {s} {metric} {role} database {order} scratch {scratch}")
+        if order == "identical":
+            assert (got[0] == np.arange(si.LONG_K, dtype=np.uint32)[None, :]).all() and (bits(got[1]) == bits(got[1])[:, :1]).all()
+
+
+@pytest.mark.parametrize("s,metric", si.LONG_CASES)
+def test_self_search_and_a_limit_beyond_one_pass(s, metric):
+    """N = 1100 sketches among themselves: the diagonal lies in every pass, and a max_distance that leaves many queries fewer than K
+    hits rejects and accepts candidates of the second and the third pass"""
+    from hulk_amd.smash import search
+    _, _, dm, dw = si.long_inputs(s)
+    n = si.pass_length()
+    for role in si.ROLES:
+        lim, want, free = si.check_self_search(s, metric, role)
+        got = search(dm, dw, None, None, si.LONG_K, metric, role, max_distance=lim, self_search=True)
+        assert_hits(got, want, f"self N {si.LONG_P} S {s} {metric} {role} max_distance {lim!r}")
+        index, _, count = got
+        held = np.arange(si.LONG_K)[None, :] < count[:, None]
+        assert (held & (index < n)).any() and (held & (index >= n) & (index < 2 * n)).any() and (held & (index >= 2 * n)).any(), "hits on both sides of every pass border"
+        assert not (index == np.arange(si.LONG_P, dtype=np.uint32)[:, None]).any(), "a sketch is its own hit"
+        assert_hits(search(dm, dw, None, None, si.LONG_K, metric, role, self_search=True), free, f"self N {si.LONG_P} S {s} {metric} {role}")
 
 
 # ---- 6. the directory form and the CLI ------------------------------------------------------------------------------------------------

@@ -1,38 +1,19 @@
 """The MinHash side of the ABI without a GPU: the header and the binding agree on the two flags and the two entry points, the
 numpy restatement of minhash.KMVsketch / KHFsketch (src/minhash/kmv.go:39-71, khf.go:34-45) that tests/test_gpu_minhash.py
 compares the GPU with behaves as the reference does on hand cases, and a HULKdata with real kmv + khf signatures round-trips
-through both loaders."""
+through both loaders; and the inputs of tests/test_gpu_minhash_sizes.py exercise what they claim (the check_* functions of
+tests/minhash_inputs.py, on the reference alone)."""
 import ctypes
 import os
 import re
 
 import numpy as np
+import pytest
 
+# the reference, restated, lives in tests/minhash_inputs.py (the GPU test modules import that ONE definition, from here or there)
+import minhash_inputs as mi
 from conftest import ROOT
-
-U64_MAX = (1 << 64) - 1
-
-
-# ---- the reference, restated (kept here so that the GPU test module imports ONE definition)
-def kmv_reference(vals, sketch_size):
-    """KMVsketch.AddHash over `vals` + GetSketch: a max-heap of sketch_size entries WITHOUT de-duplication (kmv.go:39-71), so the
-    min(sketch_size, len(vals)) smallest values of the multiset, ascending (kmv.go:161-169)."""
-    return np.sort(np.asarray(vals, dtype=np.uint64), kind="stable")[:sketch_size]
-
-
-def khf_reference(vals, sketch_size, chunk=1 << 14):
-    """KHFsketch.AddHash over `vals`: slot i = min over x of (x + i * x) mod 2^64, MaxUint64 to begin with (khf.go:20-45)."""
-    vals = np.asarray(vals, dtype=np.uint64)
-    mult = np.arange(1, sketch_size + 1, dtype=np.uint64)[None, :]
-    out = np.full(sketch_size, U64_MAX, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        for lo in range(0, len(vals), chunk):
-            out = np.minimum(out, (vals[lo:lo + chunk, None] * mult).min(axis=0))
-    return out
-
-
-def khf_merge_reference(a, b):
-    return np.minimum(np.asarray(a, dtype=np.uint64), np.asarray(b, dtype=np.uint64))      # khf.go:49-55
+from minhash_inputs import U64_MAX, khf_merge_reference, khf_reference, kmv_reference  # noqa: F401
 
 
 def test_header_and_binding_agree_on_the_minhash_abi():
@@ -130,3 +111,32 @@ def test_minhash_signatures_round_trip_through_both_loaders(tmp_path):
         order, mins, weights, _ = smash_mod.load_sketches(files, 27, algo)
         assert order == sorted(files) and mins.shape == (3, 32)
         assert np.array_equal(mins, np.stack(want)) and not weights.any()
+
+
+# ---- the inputs of tests/test_gpu_minhash_sizes.py are a test (conditions on the reference alone) -----------------------------------
+@pytest.mark.parametrize("k", [21, 31])
+def test_the_path_inputs_feed_every_path_and_fill_the_largest_sketch(k):
+    mi.check_path_inputs(k)
+
+
+def test_at_k_31_the_wrap_decides_more_than_half_of_the_slots_of_every_size():
+    mi.check_wrap_decides(31)
+    mi.check_no_wrap(21)
+    assert set(mi.DISPATCH_SIZES) >= {64 * ns + d for ns in (1, 2, 4, 8, 16, 32) for d in (0, 1)} | {4095, 4096}
+
+
+@pytest.mark.parametrize("k", [21, 31])
+def test_kmv_streams_at_the_cap_and_the_bound_between_two_copies(k):
+    mi.check_cap_streams(k)
+
+
+@pytest.mark.parametrize("k", [21, 31])
+def test_descending_reads_make_the_bound_fall_in_half_of_the_reads(k):
+    mi.check_orders(k)
+
+
+@pytest.mark.parametrize("k", sorted(mi.BOUNDARY_S_LO))
+def test_the_inputs_show_the_line_between_the_two_khf_feeds(k):
+    wrapped = mi.check_boundary(k)
+    print(f"k {k}: S_lo {mi.BOUNDARY_S_LO[k]}, seed {mi.BOUNDARY_SEEDS[k]}, {wrapped} slots above S_lo wrap at 2 * S_lo; sizes {mi.boundary_sizes(k)}")
+    assert 2 * k + 8 + (mi.BOUNDARY_S_LO[k] - 1).bit_length() == 64 and mi.BOUNDARY_S_LO[k] in mi.boundary_sizes(k)

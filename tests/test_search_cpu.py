@@ -12,6 +12,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import search_inputs as si
 from conftest import ROOT
 
 ENTRY_POINTS = ("hulk_search", "hulk_search_files")
@@ -183,6 +184,36 @@ def test_cli_refuses_a_bad_top_and_an_unknown_metric(tmp_path):
         assert rc == 1
         assert "ERROR---> " + text in buf.getvalue(), buf.getvalue()
         assert sorted(os.listdir(tmp_path)) == ["db"], "nothing is written"
+
+
+# ---- the inputs that take the selection beyond one pass are a test (tests/search_inputs.py, on the yardstick alone) -------------------
+@pytest.mark.parametrize("s,metric", si.LONG_CASES)
+def test_the_long_strips_are_what_they_claim(s, metric):
+    si.check_long_strips(s, metric)
+    # the scratch that makes two strips of 576 + 524 sketches, by search_plan's own rule (Mb = 32 for five queries)
+    per_sketch = 32 * s + 8 * 32
+    assert si.strip_scratch(s) // per_sketch // 64 * 64 == si.STRIP == 576 and -(-si.LONG_P // si.STRIP) == 2
+    text = open(os.path.join(ROOT, "hulk_amd", "csrc", "hulk_search.hip")).read()
+    assert "Pb = budget / ((uint64_t)S * 32 + Mb * 8) / 64 * 64;" in text, "search_plan moved: look at strip_scratch"
+
+
+@pytest.mark.parametrize("s,metric", si.LONG_CASES)
+def test_the_database_orders_and_the_self_search_limit_are_what_they_claim(s, metric):
+    for role in si.ROLES:
+        entered = si.check_orders(s, metric, role)
+        print(f"S {s} {metric} {role}: candidates that enter query 0's list of {si.LONG_K}: {entered}")
+        assert entered["ascending"] == entered["identical"] == si.LONG_K < entered["copies"] < entered["descending"]
+        lim, cut, free = si.check_self_search(s, metric, role)
+        print(f"S {s} {metric} {role}: max_distance {lim!r} leaves {cut[2].mean():.1f} hits a query")
+
+
+def test_the_replay_of_the_selection_counts_insertions():
+    assert si.insertions(np.array([0.5, 0.4, 0.3, 0.2]), 2) == 4            # descending: every candidate enters
+    assert si.insertions(np.array([0.2, 0.3, 0.4, 0.5]), 2) == 2            # ascending: the first K
+    assert si.insertions(np.array([0.3, 0.3, 0.3, 0.3]), 2) == 2            # ties: a later index never beats an earlier one
+    assert si.insertions(np.array([0.3, np.nan, 0.1, 0.3, 0.2]), 2) == 3    # NaN is no candidate
+    D = np.array([[0.3, np.nan, 0.1, 0.3, 0.2]])
+    assert si.select(D, 2)[0].tolist() == [[2, 4]] and si.select(D, 4)[2].tolist() == [4]
 
 
 def test_cpp_search_driver_compiles_and_links(tmp_path):
