@@ -356,7 +356,8 @@ struct DevRun {
     // The host's whole job is read() into pinned memory and one PCIe copy per block, so its best settings are not the
     // parser's: 16 MiB blocks read in 16 pieces side by side moved 46 GB/s of a page-cached file (1.5e8 reads/s of 150 bp
     // FASTQ: the PCIe link), 4 pieces 33; 8 MiB blocks 28 (profiles/r05_devparse.txt).  A caller's figures are taken as they are
-    // (the line index holds (porch + block) / 8 lines in 8 K workgroups of 1 K: blocks of up to 32 MiB).
+    // (the line index holds (porch + block) / 8 + 1024 lines in workgroups of 256 — 8,708 of them at 16 MiB —, which the one-workgroup
+    // scans walk in trips of 2,048: blocks of up to 32 MiB).
     bool begin(const char *const *paths, uint32_t n_paths, const IngestCfg &cfg_in, bool fasta) {
         if (n_paths && !paths) return err.set(HULK_ERR_ARG, "NULL path list");
         cfg = cfg_in;
