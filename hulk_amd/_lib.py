@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "hulk_dendrogram", "hulk_dendrogram_files", "hulk_linkage", "hulk_linkage_files",
     "hulk_links", "hulk_links_files", "hulk_link_list_info", "hulk_link_list_row_start", "hulk_link_list_cols",
     "hulk_link_list_distances", "hulk_link_list_free",
+    "hulk_index_build", "hulk_index_search", "hulk_index_info", "hulk_index_free", "hulk_index_set_names", "hulk_index_name",
+    "hulk_index_save", "hulk_index_load", "hulk_index_build_files", "hulk_index_search_files",
 )
 # test hooks: exported by the profiling build only (make -C hulk_amd/csrc EXPERIMENTS=1; HULK_LIB=exp)
 EXPERIMENT_SYMBOLS = ("hulk_debug_inject", "hulk_debug_read")
@@ -127,6 +129,24 @@ class SearchOpts(ctypes.Structure):
 class SearchStats(ctypes.Structure):
     _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_dist", ctypes.c_double), ("kernel_ms_select", ctypes.c_double),
                 ("strips", ctypes.c_uint32), ("query_blocks", ctypes.c_uint32)]
+
+
+class IndexOpts(ctypes.Structure):
+    """hulk_index_opts (include/hulk_hip.h)."""
+    _fields_ = [("max_distance", ctypes.c_double), ("bands", ctypes.c_uint32), ("metric", ctypes.c_int), ("flags", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 4)]
+
+
+class IndexSearchOpts(ctypes.Structure):
+    """hulk_index_search_opts (include/hulk_hip.h)."""
+    _fields_ = [("k", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("max_distance", ctypes.c_double), ("scratch_bytes", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 4)]
+
+
+class IndexSearchStats(ctypes.Structure):
+    _fields_ = [("seconds_total", ctypes.c_double), ("kernel_ms_keys", ctypes.c_double), ("kernel_ms_probe", ctypes.c_double),
+                ("kernel_ms_verify", ctypes.c_double), ("kernel_ms_select", ctypes.c_double), ("candidates", ctypes.c_uint64),
+                ("within", ctypes.c_uint64), ("query_blocks", ctypes.c_uint32), ("pieces", ctypes.c_uint32)]
 
 
 class ClusterOpts(ctypes.Structure):
@@ -391,6 +411,23 @@ def load():
     L.hulk_linkage_files.restype = ctypes.c_int
     L.hulk_linkage_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, u32, ctypes.c_char_p, dbl,
                                      ctypes.c_char_p, vp, vp, vp, vp, vp, ctypes.POINTER(LinkageStats), ctypes.c_char_p, u64]
+    L.hulk_index_build.restype = ctypes.c_int
+    L.hulk_index_build.argtypes = [ctypes.c_int, vp, u32, u32, ctypes.POINTER(IndexOpts), ctypes.POINTER(vp)]
+    L.hulk_index_search.restype = ctypes.c_int
+    L.hulk_index_search.argtypes = [vp, vp, u32, ctypes.POINTER(IndexSearchOpts), vp, vp, vp, ctypes.POINTER(IndexSearchStats)]
+    L.hulk_index_info.restype = ctypes.c_int
+    L.hulk_index_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(dbl), ctypes.POINTER(u64)]
+    L.hulk_index_free.restype = None; L.hulk_index_free.argtypes = [vp]
+    L.hulk_index_set_names.restype = ctypes.c_int; L.hulk_index_set_names.argtypes = [vp, cpp, u32]
+    L.hulk_index_name.restype = ctypes.c_char_p; L.hulk_index_name.argtypes = [vp, u32]
+    L.hulk_index_save.restype = ctypes.c_int; L.hulk_index_save.argtypes = [vp, ctypes.c_char_p]
+    L.hulk_index_load.restype = ctypes.c_int; L.hulk_index_load.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(vp)]
+    L.hulk_index_build_files.restype = ctypes.c_int
+    L.hulk_index_build_files.argtypes = [ctypes.c_int, cpp, u32, u32, ctypes.c_char_p, u32, ctypes.POINTER(IndexOpts), ctypes.POINTER(vp),
+                                         ctypes.c_char_p, u64]
+    L.hulk_index_search_files.restype = ctypes.c_int
+    L.hulk_index_search_files.argtypes = [vp, cpp, u32, u32, ctypes.c_char_p, u32, ctypes.POINTER(IndexSearchOpts), ctypes.c_char_p, vp, vp, vp,
+                                          ctypes.POINTER(IndexSearchStats), ctypes.c_char_p, u64]
     _lib = L
     return L
 

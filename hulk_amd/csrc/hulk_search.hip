@@ -13,12 +13,13 @@
 //   k_search_select a wave owns a query: lane l < K holds entry l of its list, sorted by the 96-bit key (distance bits, database
 //                   index) — a non-negative, non-NaN double orders like its uint64 bits.  It reads the strip's row 64 values at
 //                   a time (coalesced, eight such loads in flight), rejects against the K-th key (after the first strip nearly everything fails this one
-//                   compare), takes the survivors of a ballot in lane order and inserts each: its rank in the list is a ballot's
-//                   population count, the tail moves up one lane.  The compare is the full key, so the list is a function of the
-//                   set of pairs alone: no atomics, no appends, no dependence on strips, blocks or scheduling
+//                   compare), takes the survivors of a ballot in lane order and inserts each (select_insert, hulk_select.h: its rank
+//                   in the list is a ballot's population count, the tail moves up one lane).  The compare is the full key, so the
+//                   list is a function of the set of pairs alone: no atomics, no appends, no dependence on strips, blocks or scheduling
 #include "hulk_oneshot.h"
 #include "hulk_pairtile.h"
 #include "hulk_bottomk_tile.h"
+#include "hulk_select.h"
 
 #include <algorithm>
 #include <cmath>
@@ -91,23 +92,8 @@ __global__ __launch_bounds__(256) void k_search_select(const double *__restrict_
             const double d = dv[u];
             const unsigned long long bits = (unsigned long long)__double_as_longlong(d);
             // (d <= lim is false for a NaN; distances are in [0, 1], so the bits order as the values do)
-            const bool ok = c < np && d >= 0.0 && d <= lim && !(self && gi == q) && (bits < td || (bits == td && gi < ti));
-            unsigned long long mask = __ballot(ok);
-            while (mask) {                                          // survivors in lane order = ascending index
-                const int src = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const unsigned long long cd = __shfl(bits, src);
-                const uint32_t ci = __shfl(gi, src);
-                if (!(cd < td || (cd == td && ci < ti))) continue;  // (the K-th key has moved since the ballot)
-                const bool less = lane < K && (kd < cd || (kd == cd && ki < ci));
-                const uint32_t pos = (uint32_t)__popcll(__ballot(less));            // < K: the candidate beats the K-th key
-                const unsigned long long ud = __shfl_up(kd, 1);
-                const uint32_t ui = __shfl_up(ki, 1);
-                if (lane > pos) { kd = ud; ki = ui; }
-                else if (lane == pos) { kd = cd; ki = ci; }
-                td = __shfl(kd, (int)K - 1);
-                ti = __shfl(ki, (int)K - 1);
-            }
+            const bool ok = c < np && d >= 0.0 && d <= lim && !(self && gi == q) && select_beats(bits, gi, td, ti);
+            select_insert(__ballot(ok), bits, gi, lane, K, kd, ki, td, ti);      // survivors in lane order = ascending index
         }
     }
     if (lane < K) { lkey[(size_t)q * K + lane] = kd; lidx[(size_t)q * K + lane] = ki; }

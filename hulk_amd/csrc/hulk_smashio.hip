@@ -719,6 +719,77 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
     return HULK_OK;
 }
 
+int hulk_index_build_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, uint32_t threads,
+                           const hulk_index_opts *opts, hulk_index **index, char *errbuf, uint64_t errbuf_len) {
+    if (index) *index = nullptr;
+    if (!algo || !opts || !index) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    const std::string algo_s = algo;
+    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    hulk_sketch_set *set = nullptr;
+    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
+    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
+    const uint32_t n = (uint32_t)set->files.size();
+    hulk_index *ix = nullptr;
+    { const int rc = hulk_index_build(device, set->mins.data(), n, set->size, opts, &ix); if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr)); }
+    std::vector<const char *> names(n);
+    for (uint32_t i = 0; i < n; i++) names[i] = set->files[i].path.c_str();
+    { const int rc = hulk_index_set_names(ix, names.data(), n); if (rc != HULK_OK) { hulk_index_free(ix); return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr)); } }
+    *index = ix;
+    return HULK_OK;
+}
+
+int hulk_index_search_files(hulk_index *index, const char *const *query_paths, uint32_t n_q, uint32_t ksize, const char *algo,
+                            uint32_t threads, const hulk_index_search_opts *opts, const char *csv_path, uint32_t *hit_index,
+                            double *hit_distance, uint32_t *hit_count, hulk_index_search_stats *stats, char *errbuf, uint64_t errbuf_len) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!index || !algo || !opts) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    const std::string algo_s = algo;
+    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    const uint32_t k = opts->k;
+    if (k == 0 || k > HULK_SEARCH_MAX_K) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_index_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
+    const bool self = (opts->flags & HULK_SEARCH_SELF) != 0;
+    if (self && (query_paths || n_q)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_index_search: HULK_SEARCH_SELF takes no queries");
+    uint32_t n = 0, S = 0;
+    hulk_index_info(index, &n, &S, nullptr, nullptr, nullptr);
+    hulk_sketch_set *qs = nullptr;
+    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } gq{nullptr};
+    if (!self) {
+        const int rc = load_sketch_set(query_paths, n_q, ksize, algo, threads, false, &qs, errbuf, errbuf_len);
+        if (rc != HULK_OK) return rc;
+        gq.s = qs;
+        if (qs->size != S)                                          // sketchio.go:274-277
+            return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(qs->size) + " vs " + std::to_string(S) + "\n");
+    }
+    const uint32_t m = self ? n : (uint32_t)qs->files.size();
+    std::vector<uint32_t> own_i, own_c; std::vector<double> own_d;
+    if (!hit_index) { own_i.resize((size_t)m * k); hit_index = own_i.data(); }
+    if (!hit_distance) { own_d.resize((size_t)m * k); hit_distance = own_d.data(); }
+    if (!hit_count) { own_c.resize(m); hit_count = own_c.data(); }
+    {
+        const int rc = hulk_index_search(index, self ? nullptr : qs->mins.data(), m, opts, hit_index, hit_distance, hit_count, stats);
+        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
+    }
+    if (csv_path) {
+        std::vector<std::string> rows((size_t)m + 1);
+        rows[0] = "query,rank,hit,similarity\n";
+        parallel_for(m, pick_threads(threads, m), [&](size_t i) {
+            std::string &r = rows[i + 1];
+            const std::string query = self ? std::string(hulk_index_name(index, (uint32_t)i)) : qs->files[i].path;
+            for (uint32_t j = 0; j < hit_count[i]; j++) {
+                csv_field(r, query); r += ','; r += std::to_string(j + 1); r += ',';
+                csv_field(r, hulk_index_name(index, hit_index[i * (size_t)k + j])); r += ',';
+                format_f2(r, 100 - (hit_distance[i * (size_t)k + j] * 100));       // cmd/smash.go:217
+                r += '\n';
+            }
+        });
+        std::string err;
+        if (!write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    }
+    return HULK_OK;
+}
+
 int hulk_cluster_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
                        double max_distance, uint32_t threads, const char *csv_path, uint32_t *label, hulk_cluster_stats *stats,
                        char *errbuf, uint64_t errbuf_len) {

@@ -188,6 +188,175 @@ def search_files(query_files, db_files, k, ksize=21, algo="histosketch", metric=
     return q_order, d_order, index, dist, count[:m]
 
 
+def _index_stats_dict(st):
+    return dict(seconds_total=st.seconds_total, kernel_ms_keys=st.kernel_ms_keys, kernel_ms_probe=st.kernel_ms_probe,
+                kernel_ms_verify=st.kernel_ms_verify, kernel_ms_select=st.kernel_ms_select, candidates=st.candidates, within=st.within,
+                query_blocks=st.query_blocks, pieces=st.pieces)
+
+
+class Index:
+    """A banded index over a sketch collection that stays on the GPU (hulk_index_*): search()'s hit lists under jaccard at a distance
+    threshold, computed over the sketches that share a band with the query.  Built for max_distance D with the default bands
+    (bands=0: u_max + 1) the result is search(metric="jaccard", the same k and max_distance <= D) over the whole collection, bit for
+    bit; with fewer bands it is an LSH filter, faster and incomplete (include/hulk_hip.h states the rule).  One call at a time per
+    index; close() (or the end of a `with` block) frees the device memory."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _opts(max_distance, bands, metric):
+        if metric not in AVAIL_METRICS:
+            raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+        code = {"jaccard": _lib.HULK_METRIC_JACCARD, "weightedjaccard": _lib.HULK_METRIC_WEIGHTED_JACCARD, "bottomk": _lib.HULK_METRIC_BOTTOMK}[metric]
+        bands = int(bands)
+        return _lib.IndexOpts(max_distance=float(max_distance), bands=bands if 0 <= bands < 2 ** 32 else 0xFFFFFFFF, metric=code)
+
+    @classmethod
+    def build(cls, mins, max_distance, bands=0, device=0, names=None, metric="jaccard"):
+        """mins [n][S] uint64 -> Index.  names: n strings (search_files' CSV and .names report them)."""
+        import ctypes
+        m = np.ascontiguousarray(mins, dtype=np.uint64)
+        if m.ndim != 2:
+            raise ValueError("mins must be [n][sketch_size]")
+        o = cls._opts(max_distance, bands, metric)
+        L = _lib.load()
+        h = ctypes.c_void_p()
+        rc = L.hulk_index_build(device, m.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), ctypes.byref(h))
+        if rc != 0:
+            raise HulkError(rc, L.hulk_last_error(None).decode())
+        ix = cls(h)
+        if names is not None:
+            arr, n = _paths(names)
+            rc = L.hulk_index_set_names(h, arr, n)
+            if rc != 0:
+                ix.close()
+                raise HulkError(rc, L.hulk_last_error(None).decode())
+        return ix
+
+    @classmethod
+    def build_files(cls, files, max_distance, bands=0, ksize=21, algo="histosketch", threads=0, device=0):
+        """The sketch files through the native loader (MD5, FindSketch, the reference's error texts); the sorted unique paths are the names."""
+        import ctypes
+        o = cls._opts(max_distance, bands, "jaccard")
+        arr, n = _paths(files)
+        L = _lib.load()
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(4096)
+        rc = L.hulk_index_build_files(device, arr, n, ksize, algo.encode(), threads, ctypes.byref(o), ctypes.byref(h), err, len(err))
+        if rc != 0:
+            raise HulkError(rc, err.value.decode("utf-8", "replace"))
+        return cls(h)
+
+    @classmethod
+    def load(cls, path, device=0):
+        import ctypes
+        L = _lib.load()
+        h = ctypes.c_void_p()
+        rc = L.hulk_index_load(device, os.fsencode(path), ctypes.byref(h))
+        if rc != 0:
+            raise HulkError(rc, L.hulk_last_error(None).decode("utf-8", "replace"))
+        return cls(h)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the index is closed")
+        return self._h
+
+    def save(self, path):
+        L = _lib.load()
+        rc = L.hulk_index_save(self._handle(), os.fsencode(path))
+        if rc != 0:
+            raise HulkError(rc, L.hulk_last_error(None).decode("utf-8", "replace"))
+
+    @property
+    def info(self):
+        """dict(n, sketch_size, bands, max_distance, device_bytes)"""
+        import ctypes
+        n, s, b, d, by = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_double(), ctypes.c_uint64()
+        _lib.load().hulk_index_info(self._handle(), ctypes.byref(n), ctypes.byref(s), ctypes.byref(b), ctypes.byref(d), ctypes.byref(by))
+        return dict(n=n.value, sketch_size=s.value, bands=b.value, max_distance=d.value, device_bytes=by.value)
+
+    @property
+    def names(self):
+        L = _lib.load()
+        return [os.fsdecode(L.hulk_index_name(self._handle(), i)) for i in range(self.info["n"])]
+
+    def _search_opts(self, k, max_distance, self_search, scratch_bytes):
+        k = int(k)
+        o = _lib.IndexSearchOpts(k=k if 0 <= k < 2 ** 32 else 0, flags=_lib.HULK_SEARCH_SELF if self_search else 0,
+                                 max_distance=-1.0 if max_distance is None else float(max_distance), scratch_bytes=int(scratch_bytes))
+        return o, max(min(k, _lib.HULK_SEARCH_MAX_K), 1)
+
+    def search(self, q_mins, k, max_distance=None, self_search=False, scratch_bytes=0, stats=None):
+        """-> (index[m][k] uint32, distance[m][k], count[m]) as search() gives them.  max_distance None: the build's; above the
+        build's: HulkError.  self_search: q_mins is None and the queries are the indexed sketches, (i, i) left out.  stats: a dict
+        that receives candidates, within, the kernel milliseconds per phase, query_blocks, pieces."""
+        import ctypes
+        h = self._handle()
+        if self_search:
+            if q_mins is not None:
+                raise ValueError("self_search takes no queries")
+            qm, m = None, self.info["n"]
+        else:
+            qm = np.ascontiguousarray(q_mins, dtype=np.uint64)
+            if qm.ndim != 2:
+                raise ValueError("mins must be [m][sketch_size]")
+            if qm.shape[1] != self.info["sketch_size"]:
+                raise HulkError(-30, f"sketch length mismatch: {qm.shape[1]} vs {self.info['sketch_size']}\n")
+            m = qm.shape[0]
+        o, kk = self._search_opts(k, max_distance, self_search, scratch_bytes)
+        index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(max(m, 1), dtype=np.uint32)
+        st = _lib.IndexSearchStats()
+        L = _lib.load()
+        rc = L.hulk_index_search(h, None if qm is None else qm.ctypes.data, m, ctypes.byref(o), index.ctypes.data, dist.ctypes.data,
+                                 count.ctypes.data, ctypes.byref(st))
+        if rc != 0:
+            raise HulkError(rc, L.hulk_last_error(None).decode())
+        if stats is not None:
+            stats.update(_index_stats_dict(st))
+        return index, dist, count[:m]
+
+    def search_files(self, query_files, k, max_distance=None, self_search=False, ksize=21, algo="histosketch", csv_path=None, threads=0,
+                     stats=None):
+        """The query files through the native loader; csv_path: search_files' "query,rank,hit,similarity".
+        -> (query ordering, index, distance, count)"""
+        import ctypes
+        h = self._handle()
+        q_order = self.names if self_search else sorted(set(query_files))
+        m = len(q_order)
+        o, kk = self._search_opts(k, max_distance, self_search, 0)
+        index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(max(m, 1), dtype=np.uint32)
+        qa, nq = (None, 0) if self_search else _paths(query_files)
+        st = _lib.IndexSearchStats()
+        err = ctypes.create_string_buffer(4096)
+        L = _lib.load()
+        rc = L.hulk_index_search_files(h, qa, nq, ksize, algo.encode(), threads, ctypes.byref(o), None if csv_path is None else os.fsencode(csv_path),
+                                       index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st), err, len(err))
+        if rc != 0:
+            raise HulkError(rc, err.value.decode("utf-8", "replace"))
+        if stats is not None:
+            stats.update(_index_stats_dict(st))
+        return q_order, index, dist, count[:m]
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().hulk_index_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _cluster_stats_dict(st):
     return dict(seconds_total=st.seconds_total, kernel_ms_link=st.kernel_ms_link, kernel_ms_flatten=st.kernel_ms_flatten,
                 links=st.links, bands=st.bands, clusters=st.clusters)

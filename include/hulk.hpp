@@ -14,6 +14,7 @@
 //   `--stream`: "prints the sketches ... after every interval"            hulk::Boss::EnableSnapshots / CollectSnapshots /
 //       cmd/sketch.go:56 (promised, read nowhere in src/pipeline)           OnSnapshot (recorded inside the batched flush)
 //   (none: the k nearest sketches of a database for every query sketch)   hulk::Search (HULKdata.GetDistance per pair)
+//   (none: the same hits within a distance from a banded index on the GPU)  hulk::Index (Build / BuildFiles / Load / Save / Search / SearchSelf)
 //   (none: the sketches of a collection grouped at a distance threshold)  hulk::Cluster / hulk::ClusterFiles (single linkage)
 //   (none: every threshold at once, the single-linkage dendrogram)         hulk::Dendrogram / hulk::DendrogramFiles
 //   (none: the complete- and average-linkage dendrograms the paper's       hulk::Linkage / hulk::LinkageFiles
@@ -362,6 +363,98 @@ inline std::vector<std::vector<Hit>> Search(const std::vector<HistoSketch> &quer
         for (uint32_t j = 0; j < count[i]; j++) { Hit h; h.Index = index[i * kk + j]; h.Distance = distance[i * kk + j]; out[i].push_back(h); }
     return out;
 }
+
+// A banded index over a collection that stays on the GPU (hulk_index_*): Search's hits under "jaccard" within a distance, computed over
+// the sketches that share a band with the query.  Built for maxDistance with bands = 0 (derived) the result is Search(queries, database,
+// k, "jaccard", true, limit <= maxDistance), bit for bit; fewer bands make it an LSH filter, faster and incomplete (hulk_hip.h states
+// the rule).  The handle is freed with the object; one call at a time per index.
+class Index {
+public:
+    static Index Build(const std::vector<HistoSketch> &sketches, double maxDistance, uint32_t bands = 0, int device = 0) {
+        const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
+        hulk_index_opts o = hulk_index_opts();
+        o.max_distance = maxDistance; o.bands = bands;
+        const std::vector<uint64_t> mins = Pack(sketches, S);
+        hulk_index *h = nullptr;
+        const int rc = hulk_index_build(device, mins.data(), N, S, &o, &h);
+        if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+        return Index(h);
+    }
+    // the files through the library's loader (MD5, FindSketch, the reference's error texts); the sorted unique paths are the names
+    static Index BuildFiles(const std::vector<std::string> &files, double maxDistance, uint32_t bands = 0, uint32_t ksize = 21,
+                            const std::string &algo = "histosketch", uint32_t threads = 0, int device = 0) {
+        hulk_index_opts o = hulk_index_opts();
+        o.max_distance = maxDistance; o.bands = bands;
+        std::vector<const char *> paths;
+        for (const std::string &f : files) paths.push_back(f.c_str());
+        char err[4096] = "";
+        hulk_index *h = nullptr;
+        const int rc = hulk_index_build_files(device, paths.data(), (uint32_t)paths.size(), ksize, algo.c_str(), threads, &o, &h, err, sizeof err);
+        if (rc != HULK_OK) throw Error(rc, err);
+        return Index(h);
+    }
+    static Index Load(const std::string &path, int device = 0) {
+        hulk_index *h = nullptr;
+        const int rc = hulk_index_load(device, path.c_str(), &h);
+        if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+        return Index(h);
+    }
+    Index(Index &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Index &operator=(Index &&o) noexcept { if (this != &o) { hulk_index_free(h_); h_ = o.h_; o.h_ = nullptr; } return *this; }
+    Index(const Index &) = delete;
+    Index &operator=(const Index &) = delete;
+    ~Index() { hulk_index_free(h_); }
+
+    void Save(const std::string &path) const {
+        const int rc = hulk_index_save(h_, path.c_str());
+        if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+    }
+    // maxDistance < 0: the build's.  (An empty `queries` is the library's "m must be positive", not a self-join: SearchSelf is its own call.)
+    std::vector<std::vector<Hit>> Search(const std::vector<HistoSketch> &queries, uint32_t k, double maxDistance = -1.0, uint64_t scratchBytes = 0,
+                                         hulk_index_search_stats *stats = nullptr) const {
+        const std::vector<uint64_t> mins = Pack(queries, SketchSize());
+        return Run(mins.data(), (uint32_t)queries.size(), 0u, k, maxDistance, scratchBytes, stats);
+    }
+    // the indexed sketches among themselves (HULK_SEARCH_SELF): a sketch is not its own hit
+    std::vector<std::vector<Hit>> SearchSelf(uint32_t k, double maxDistance = -1.0, uint64_t scratchBytes = 0,
+                                             hulk_index_search_stats *stats = nullptr) const {
+        return Run(nullptr, Size(), HULK_SEARCH_SELF, k, maxDistance, scratchBytes, stats);
+    }
+    uint32_t Size() const { uint32_t v = 0; hulk_index_info(h_, &v, nullptr, nullptr, nullptr, nullptr); return v; }
+    uint32_t SketchSize() const { uint32_t v = 0; hulk_index_info(h_, nullptr, &v, nullptr, nullptr, nullptr); return v; }
+    uint32_t Bands() const { uint32_t v = 0; hulk_index_info(h_, nullptr, nullptr, &v, nullptr, nullptr); return v; }
+    double MaxDistance() const { double v = 0; hulk_index_info(h_, nullptr, nullptr, nullptr, &v, nullptr); return v; }
+    uint64_t DeviceBytes() const { uint64_t v = 0; hulk_index_info(h_, nullptr, nullptr, nullptr, nullptr, &v); return v; }
+    std::string Name(uint32_t i) const { const char *s = hulk_index_name(h_, i); return s ? s : ""; }
+    hulk_index *Handle() const { return h_; }
+
+private:
+    explicit Index(hulk_index *h) : h_(h) {}
+    std::vector<std::vector<Hit>> Run(const uint64_t *mins, uint32_t M, uint32_t flags, uint32_t k, double maxDistance, uint64_t scratchBytes,
+                                      hulk_index_search_stats *stats) const {
+        hulk_index_search_opts o = hulk_index_search_opts();
+        o.k = k; o.flags = flags; o.max_distance = maxDistance; o.scratch_bytes = scratchBytes;
+        const size_t kk = k ? k : 1;
+        std::vector<uint32_t> index(M * kk + 1), count((size_t)M + 1);
+        std::vector<double> distance(M * kk + 1);
+        const int rc = hulk_index_search(h_, mins, M, &o, index.data(), distance.data(), count.data(), stats);
+        if (rc != HULK_OK) throw Error(rc, hulk_last_error(nullptr));
+        std::vector<std::vector<Hit>> out(M);
+        for (uint32_t i = 0; i < M; i++)
+            for (uint32_t j = 0; j < count[i]; j++) { Hit h; h.Index = index[i * kk + j]; h.Distance = distance[i * kk + j]; out[i].push_back(h); }
+        return out;
+    }
+    static std::vector<uint64_t> Pack(const std::vector<HistoSketch> &set, uint32_t S) {
+        std::vector<uint64_t> mins(set.size() * (size_t)S + 1);
+        for (size_t i = 0; i < set.size(); i++) {
+            if (set[i].Sketch.size() != S)
+                throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(set[i].Sketch.size()) + " vs " + std::to_string(S) + "\n");
+            std::copy(set[i].Sketch.begin(), set[i].Sketch.end(), mins.begin() + i * (size_t)S);
+        }
+        return mins;
+    }
+    hulk_index *h_ = nullptr;
+};
 
 // Single-linkage clusters of a collection at a distance threshold, on the GPU (hulk_cluster): sketches i != j are linked when Smash's
 // entry [i][j] or [j][i] is <= maxDistance (in [0, 1]; a NaN never links, equality does); a cluster is a connected component, the

@@ -836,6 +836,104 @@ int hulk_linkage_files(int device, const char *const *paths, uint32_t n, uint32_
                        const char *cut_csv_path, uint32_t *merge_a, uint32_t *merge_b, double *merge_distance, uint32_t *merge_size,
                        uint32_t *n_merges, hulk_linkage_stats *stats, char *errbuf, uint64_t errbuf_len);
 
+/* ---- a banded index over a sketch collection: hulk_search at a distance threshold against a database that stays on the device ------
+ * The distance is hulk_smash's jaccard and nothing else: mins compared as (double)min, distance = 1.0 - (double)equal / (double)S.
+ * weightedjaccard and bottomk are HULK_ERR_ARG with a text: a weighted distance (or a set similarity) does not bound the number of
+ * unequal slots, so the filter below would not be exact for them.
+ * BANDS.  For the build threshold D = opts->max_distance in [0, 1), u_max is the largest u in [0, S] with
+ * 1.0 - (double)(S - u) / (double)S <= D — the distance expression itself in fp64, so the bound and the kernel cannot disagree about
+ * an edge case.  bands = 0 derives B = u_max + 1; band b covers the slots [floor(b S / B), floor((b + 1) S / B)).  u_max == S (D = 1)
+ * is HULK_ERR_ARG, "every sketch is within this distance: use hulk_search".  bands may be given, 1 .. S; below u_max + 1 the index is
+ * an ordinary LSH filter, faster and incomplete: the result is what RESULT says and nothing more.
+ * KEYS.  key(sketch, b) folds the band's slots in ascending order: h = 0, then h = hash64(h ^ bits((double)min[t]), ~0) with the
+ * minimap2 mix this library hashes k-mers with.  The hash is over the double's bits: two mins that smash calls equal get one key.
+ * CANDIDATES.  Database sketch p is a candidate of query q when key(q, b) == key(p, b) for at least one b.  A 64-bit collision makes
+ * a candidate that a slot-by-slot compare would not; its real distance is computed anyway, so a collision adds work and never changes
+ * a result.
+ * RESULT.  For every query hulk_search's hit list (k <= HULK_SEARCH_MAX_K, ordered by (distance, database index), the entries behind
+ * hit_count 0xFFFFFFFF / NaN) computed over the candidates only, with the limit max_distance of the search (negative or NaN: the
+ * build's D; above the build's D: HULK_ERR_ARG, whatever bands is).  HULK_SEARCH_SELF: q_mins NULL, m ignored, the queries are the
+ * indexed set and (i, i) is left out.  Every distinct candidate pair is verified and counted once, however many bands it shares:
+ * stats->candidates is the number of distinct (q, p) pairs, stats->within how many of them were within the limit before the cut to
+ * k — a caller can see a truncated list.
+ * THEOREM.  With bands >= u_max + 1 (the default) the result is hulk_search(metric jaccard, the same k, the same max_distance) over
+ * the whole database, bit for bit.  (Two sketches within D differ in at most u_max slots; these lie in at most u_max of the
+ * u_max + 1 disjoint bands, so one band is intact and its keys are equal: every pair within the limit is a candidate, and a
+ * candidate's distance is the bits of hulk_search's.)
+ * The index keeps on the device the mins as doubles [n][S], the keys by sketch [n][B] and per band the (key, sketch) pairs sorted by
+ * (key, sketch): 8 S + 20 B bytes a sketch (hulk_index_info's device_bytes); a build that does not fit is HULK_ERR_HIP with the
+ * bytes needed.  A search launches k_index_keys (the queries' keys), k_index_probe twice around k_index_scan (per (query, band) a
+ * binary search for the run of equal keys; count, one synchronisation in which the host reads the candidates per query, then every
+ * candidate to its final slot — no atomics, no sort), k_index_verify and k_index_select (hulk_index.hip).  scratch_bytes (0 = 256 MiB)
+ * holds the candidates, 16 bytes each: the queries are cut into blocks that fit it, a single query above it goes in pieces; neither
+ * can change a byte of the result.  The buffers of a search stay allocated between calls (beside device_bytes).
+ * On the HOST the handle keeps a copy of the raw mins, 8 * n * sketch_size bytes (what hulk_index_save writes), and the names, for its
+ * whole life; a build, load or search that cannot allocate host memory is HULK_ERR_HIP with "out of host memory", not an abort.
+ * LIMITS.  A launch stays below HIP's 2^32 threads whatever the shape: a wave serves a (query, band) of the probe and a candidate of the
+ * verification, so the count pass runs over chunks of 2^25 / bands queries, a block holds at most that many queries and at most 2^25
+ * candidates (a scratch_bytes above 512 MiB changes nothing), and what is left is refused with HULK_ERR_ARG before any HIP call:
+ * n * bands and m * bands (the keys: a thread per sketch and band) must be below 2^32, bands at most 65535 (hulk_index_plan.h).
+ * Every call returns synchronised (the outputs are host arrays) and works on the null stream of the index's device.  One call at a
+ * time per index; hulk_index_free ends its life (NULL is fine).
+ * HULK_ERR_ARG before any HIP call, with a text in hulk_last_error(NULL): NULL pointers; n, m or sketch_size == 0; a metric other than
+ * HULK_METRIC_JACCARD; max_distance outside [0, 1) at a build; bands above sketch_size (or 65535); k == 0 or above HULK_SEARCH_MAX_K;
+ * unknown flags; non-zero reserved; queries together with HULK_SEARCH_SELF or neither; a scratch_bytes below one candidate; the two
+ * products of LIMITS.  The text of a max_distance above the build's prints both doubles as %.17g: -j 0.90 builds for
+ * 0.099999999999999978, which a later --maxDistance 0.1 is above. */
+typedef struct hulk_index hulk_index;
+typedef struct hulk_index_opts {
+    double max_distance;     /* D in [0, 1): the largest distance a search may ask for */
+    uint32_t bands;          /* 0 = u_max + 1 (exact); 1 .. sketch_size */
+    int metric;              /* HULK_METRIC_JACCARD (0) */
+    uint32_t flags;          /* zero */
+    uint32_t pad;            /* zero */
+    uint64_t reserved[4];    /* zero */
+} hulk_index_opts;
+typedef struct hulk_index_search_opts {
+    uint32_t k;              /* hits per query, 1 .. HULK_SEARCH_MAX_K */
+    uint32_t flags;          /* HULK_SEARCH_SELF */
+    double max_distance;     /* in [0, D]; negative or NaN: D */
+    uint64_t scratch_bytes;  /* 0 = default */
+    uint64_t reserved[4];    /* zero */
+} hulk_index_search_opts;
+typedef struct hulk_index_search_stats {
+    double seconds_total;    /* the whole call */
+    double kernel_ms_keys;   /* the queries' upload and k_index_keys (HIP events, as the three below) */
+    double kernel_ms_probe;  /* k_index_probe (count and fill) and k_index_scan */
+    double kernel_ms_verify; /* k_index_verify */
+    double kernel_ms_select; /* k_index_select */
+    uint64_t candidates;     /* distinct (query, sketch) pairs that share a band */
+    uint64_t within;         /* ... of which within the limit, before the cut to k */
+    uint32_t query_blocks, pieces;   /* pieces: the parts of queries whose candidates exceed the scratch (0: none did) */
+} hulk_index_search_stats;
+int hulk_index_build(int device, const uint64_t *mins, uint32_t n, uint32_t sketch_size, const hulk_index_opts *opts, hulk_index **index);
+int hulk_index_search(hulk_index *index, const uint64_t *q_mins, uint32_t m, const hulk_index_search_opts *opts, uint32_t *hit_index,
+                      double *hit_distance, uint32_t *hit_count, hulk_index_search_stats *stats);
+int hulk_index_info(const hulk_index *index, uint32_t *n, uint32_t *sketch_size, uint32_t *bands, double *max_distance,
+                    uint64_t *device_bytes);   /* HULK_ERR_ARG for NULL; any output may be NULL */
+void hulk_index_free(hulk_index *index);
+/* The names of the sketches: empty after hulk_index_build until hulk_index_set_names (n must be the index's), the sorted unique paths
+ * after hulk_index_build_files, what the file held after hulk_index_load.  hulk_index_name: NULL for NULL or i >= n. */
+int hulk_index_set_names(hulk_index *index, const char *const *names, uint32_t n);
+const char *hulk_index_name(const hulk_index *index, uint32_t i);
+/* One binary file, little-endian: the magic "HULKIDX\n", the format version (1), sketch_size, n, bands (uint32 each), the bits of the
+ * threshold, the bytes of the names and of the mins (uint64 each), the names (NUL-terminated), the raw mins [n][sketch_size] and a
+ * CRC-32 over all of it.  Loading checks the lengths against the file's and the checksum, then uploads and rebuilds keys and order
+ * on the device — the code path of a build — so a loaded index answers every search with the bytes of the one that was saved.  A
+ * truncated, corrupt or foreign file is HULK_ERR_IO with a text, before any HIP call: never a crash, never a partly loaded index. */
+int hulk_index_save(const hulk_index *index, const char *path);
+int hulk_index_load(int device, const char *path, hulk_index **index);
+/* The file forms.  hulk_index_build_files: the files go through hulk_load_sketches' loader (MD5, FindSketch, the reference's error
+ * texts; a set of ONE sketch is valid); the sorted unique paths become the names.  hulk_index_search_files: the query files through
+ * the same loader ("sketch length mismatch: %d vs %d\n": the queries', the index's); HULK_SEARCH_SELF in flags: query_paths NULL.
+ * csv_path != NULL: hulk_search_files' file, "query,rank,hit,similarity" with the same strings, the hits named by hulk_index_name.
+ * hit_index / hit_distance [unique query paths][k] and hit_count may be NULL. */
+int hulk_index_build_files(int device, const char *const *paths, uint32_t n, uint32_t ksize, const char *algo, uint32_t threads,
+                           const hulk_index_opts *opts, hulk_index **index, char *errbuf, uint64_t errbuf_len);
+int hulk_index_search_files(hulk_index *index, const char *const *query_paths, uint32_t n_q, uint32_t ksize, const char *algo,
+                            uint32_t threads, const hulk_index_search_opts *opts, const char *csv_path, uint32_t *hit_index,
+                            double *hit_distance, uint32_t *hit_count, hulk_index_search_stats *stats, char *errbuf, uint64_t errbuf_len);
+
 /* Device self-test: the jump hash replaces the fp64 division 2^31/r by a Newton reciprocal; this
  * checks RN(1/r) against IEEE division for EVERY r in [1, 2^31] and returns the mismatch count. */
 int hulk_selftest_reciprocal(hulk_ctx *ctx, uint64_t *mismatches);
