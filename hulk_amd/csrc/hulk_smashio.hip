@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <memory>
 #include <thread>
 
 namespace hulk {
@@ -473,6 +474,103 @@ int put_err(char *errbuf, uint64_t errbuf_len, int code, const std::string &msg)
     fail(nullptr, code, msg);
     return code;
 }
+// a library call returned rc: report its hulk_last_error
+int put_lib_err(char *errbuf, uint64_t errbuf_len, int rc) { return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr)); }
+
+// the names of the *_files entry points in the order cmd/smash.go:60-82 checks them: the metric (NULL: the entry takes none), the
+// algorithm, the linkage method (NULL: none).  HULK_OK or the error reported
+int check_names(char *errbuf, uint64_t errbuf_len, const char *metric, const char *algo, const char *method = nullptr) {
+    auto one_of = [](const std::string &s, std::initializer_list<const char *> names) {
+        for (const char *x : names) if (s == x) return true;
+        return false;
+    };
+    if (metric && !one_of(metric, {"jaccard", "weightedjaccard", "bottomk"}))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, std::string("supplied distance metric is not available: ") + metric +
+                                                         "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
+    if (!one_of(algo, {"histosketch", "kmv", "khf"}))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, std::string("supplied algorithm not available: ") + algo +
+                                                         "\nplease select one of the following: [histosketch kmv khf]");
+    if (method && !one_of(method, {"single", "complete", "average"}))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, std::string("supplied linkage is not available: ") + method +
+                                                         "\nplease select one of the following: [single complete average]");
+    return HULK_OK;
+}
+
+// the metric against the loaded sketches: sketchio.go:287-293, and bottomk is the estimator of a sorted bottom-k list
+// (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
+int check_metric_fits(char *errbuf, uint64_t errbuf_len, const std::string &metric, const std::string &algo, bool histosketch) {
+    if (metric == "weightedjaccard" && !histosketch) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
+    if (metric == "bottomk" && algo != "kmv") return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    return HULK_OK;
+}
+int metric_code(const std::string &m) { return m == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : m == "bottomk" ? HULK_METRIC_BOTTOMK : HULK_METRIC_JACCARD; }
+
+// a caller-optional output array: p, or n elements of `local`
+template <class T> T *own_or(T *p, std::vector<T> &local, size_t n) {
+    if (!p) { local.resize(n); p = local.data(); }
+    return p;
+}
+
+// "<distance as %.17g>,<similarity as smash prints it>" of the links, dendrogram and linkage CSVs
+void distance_fields(std::string &out, double d) {
+    char tmp[40];
+    snprintf(tmp, sizeof tmp, "%.17g", d);
+    out += tmp; out += ',';
+    format_f2(out, 100 - (d * 100));                               // cmd/smash.go:217
+}
+
+// "query,rank,hit,similarity" of hulk_search_files and hulk_index_search_files: one line per hit, the rows formatted in parallel.
+// query_name(i) / hit_name(j): the names of query i and of database sketch j
+template <class Q, class H>
+bool write_hits_csv(const char *csv_path, uint32_t m, uint32_t k, const uint32_t *hit_index, const double *hit_distance, const uint32_t *hit_count,
+                    uint32_t threads, Q query_name, H hit_name, std::string &err) {
+    std::vector<std::string> rows((size_t)m + 1);
+    rows[0] = "query,rank,hit,similarity\n";
+    parallel_for(m, pick_threads(threads, m), [&](size_t i) {
+        std::string &r = rows[i + 1];
+        const auto &query = query_name((uint32_t)i);
+        for (uint32_t j = 0; j < hit_count[i]; j++) {
+            csv_field(r, query); r += ','; r += std::to_string(j + 1); r += ',';
+            csv_field(r, hit_name(hit_index[i * (size_t)k + j])); r += ',';
+            format_f2(r, 100 - (hit_distance[i * (size_t)k + j] * 100));       // cmd/smash.go:217
+            r += '\n';
+        }
+    });
+    return write_all(csv_path, rows, err);
+}
+
+// "merge,sketch_a,sketch_b,distance,similarity,size" of hulk_dendrogram_files and hulk_linkage_files: one line per merge
+bool write_merges_csv(const std::vector<Loaded> &files, const uint32_t *a, const uint32_t *b, const double *d, const uint32_t *size, uint32_t m,
+                      const char *csv_path, std::string &err) {
+    std::vector<std::string> rows((size_t)m + 1);
+    rows[0] = "merge,sketch_a,sketch_b,distance,similarity,size\n";
+    for (uint32_t e = 0; e < m; e++) {
+        std::string &r = rows[(size_t)e + 1];
+        r += std::to_string(e + 1); r += ',';
+        csv_field(r, files[a[e]].path); r += ','; csv_field(r, files[b[e]].path); r += ',';
+        distance_fields(r, d[e]);
+        r += ','; r += std::to_string(size[e]); r += '\n';
+    }
+    return write_all(csv_path, rows, err);
+}
+
+uint32_t uf_root(std::vector<uint32_t> &up, uint32_t x) {
+    while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; }
+    return x;
+}
+// the clusters of the merges with d <= cut, whatever their place in the order (average linkage may step down by a rounding): the
+// smaller root stays, so label[i] is the smallest member of i's cluster
+std::vector<uint32_t> cut_labels(uint32_t n, const uint32_t *a, const uint32_t *b, const double *d, uint32_t m, double cut) {
+    std::vector<uint32_t> up(n);
+    for (uint32_t i = 0; i < n; i++) up[i] = i;
+    for (uint32_t e = 0; e < m; e++) {
+        if (!(d[e] <= cut)) continue;
+        const uint32_t x = uf_root(up, a[e]), y = uf_root(up, b[e]);
+        if (x != y) up[std::max(x, y)] = std::min(x, y);
+    }
+    for (uint32_t i = 0; i < n; i++) up[i] = uf_root(up, i);
+    return up;
+}
 
 }  // namespace
 }  // namespace hulk
@@ -490,15 +588,15 @@ struct hulk_sketch_set {
 // the loader behind hulk_load_sketches and hulk_search_files.  at_least_two: smash's rule (cmd/smash.go:175-177); a search takes a
 // set of one sketch
 static int load_sketch_set(const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, uint32_t threads, bool at_least_two,
-                           hulk_sketch_set **out, char *errbuf, uint64_t errbuf_len) {
-    if (out) *out = nullptr;
-    if (!out || !algo || (n_paths && !paths)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+                           std::unique_ptr<hulk_sketch_set> &out, char *errbuf, uint64_t errbuf_len) {
+    out.reset();
+    if (!algo || (n_paths && !paths)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
     for (uint32_t i = 0; i < n_paths; i++) if (!paths[i]) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL path");
     // cmd/smash.go:175-177 (hSketches is a map keyed by path: a path given twice counts once)
     std::vector<std::string> names(paths, paths + n_paths);
     std::sort(names.begin(), names.end());
     names.erase(std::unique(names.begin(), names.end()), names.end());
-    hulk_sketch_set *set = new hulk_sketch_set;
+    auto set = std::make_unique<hulk_sketch_set>();
     set->files.resize(names.size());
     for (size_t i = 0; i < names.size(); i++) set->files[i].path = names[i];
     const std::string algo_s = algo;
@@ -506,23 +604,17 @@ static int load_sketch_set(const char *const *paths, uint32_t n_paths, uint32_t 
     // the reference loads the files in name order and dies at the first failure (cmd/smash.go:165-172), then wants two sketches
     // (:175-177); FindSketch failures surface in makeMatrix, pair by pair in sorted order: the first file that has one
     for (const Loaded &L : set->files)
-        if (!L.error.empty() && !L.find_stage) { const std::string e = L.error; delete set; return put_err(errbuf, errbuf_len, HULK_ERR_ARG, e); }
-    if (set->files.size() < (at_least_two ? 2u : 1u)) {
-        const std::string e = at_least_two ? std::to_string(set->files.size()) + " sketches found in the supplied directory, HULK needs at least 2 to smash!\n"
-                                           : std::string("no sketch files supplied\n");
-        delete set;
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, e);
-    }
+        if (!L.error.empty() && !L.find_stage) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, L.error);
+    if (set->files.size() < (at_least_two ? 2u : 1u))
+        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, at_least_two ? std::to_string(set->files.size()) + " sketches found in the supplied directory, HULK needs at least 2 to smash!\n"
+                                                                      : std::string("no sketch files supplied\n"));
     for (const Loaded &L : set->files)
-        if (!L.error.empty()) { const std::string e = L.error; delete set; return put_err(errbuf, errbuf_len, HULK_ERR_ARG, e); }
+        if (!L.error.empty()) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, L.error);
     const size_t size = set->files[0].mins.size();
     for (const Loaded &L : set->files)
-        if (L.mins.size() != size) {
-            const std::string e = "sketch length mismatch: " + std::to_string(size) + " vs " + std::to_string(L.mins.size()) + "\n";
-            delete set;
-            return put_err(errbuf, errbuf_len, HULK_ERR_ARG, e);
-        }
-    if (size > 0xffffffffull) { delete set; return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "sketch too long"); }
+        if (L.mins.size() != size)
+            return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(size) + " vs " + std::to_string(L.mins.size()) + "\n");
+    if (size > 0xffffffffull) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "sketch too long");
     set->size = (uint32_t)size;
     set->histosketch = algo_s == "histosketch";
     const size_t n = set->files.size();
@@ -534,16 +626,14 @@ static int load_sketch_set(const char *const *paths, uint32_t n_paths, uint32_t 
         if (set->histosketch) {
             // (a histosketch whose weights array is shorter than its mins: GetWJD indexes the weights by the mins' positions
             // and the reference panics; refused here)
-            if (L.weights.size() != size) {
-                const std::string e = "malformed sketch file (" + std::to_string(L.weights.size()) + " weights for " + std::to_string(size) + " mins): " + L.path + "\n";
-                delete set;
-                return put_err(errbuf, errbuf_len, HULK_ERR_ARG, e);
-            }
+            if (L.weights.size() != size)
+                return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "malformed sketch file (" + std::to_string(L.weights.size()) + " weights for " +
+                                                                 std::to_string(size) + " mins): " + L.path + "\n");
             if (size) memcpy(&set->weights[i * size], L.weights.data(), size * 8);
         }
         std::vector<uint64_t>().swap(L.mins); std::vector<double>().swap(L.weights);
     }
-    *out = set;
+    out = std::move(set);
     return HULK_OK;
 }
 
@@ -569,7 +659,11 @@ extern "C" {
 
 int hulk_load_sketches(const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, uint32_t threads,
                        hulk_sketch_set **out, char *errbuf, uint64_t errbuf_len) {
-    return load_sketch_set(paths, n_paths, ksize, algo, threads, true, out, errbuf, errbuf_len);
+    if (!out) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
+    std::unique_ptr<hulk_sketch_set> set;
+    const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, true, set, errbuf, errbuf_len);
+    *out = set.release();
+    return rc;
 }
 
 void hulk_sketch_set_free(hulk_sketch_set *set) { delete set; }
@@ -586,40 +680,23 @@ const double *hulk_sketch_set_weights(const hulk_sketch_set *set) { return set ?
 const char *hulk_sketch_set_path(const hulk_sketch_set *set, uint32_t i) { return (set && i < set->files.size()) ? set->files[i].path.c_str() : nullptr; }
 const char *hulk_sketch_set_banner(const hulk_sketch_set *set, uint32_t i) { return (set && i < set->files.size()) ? set->files[i].banner.c_str() : nullptr; }
 
-// the metrics of the *_files entry points (cmd/smash.go:30 and this library's bottomk) and their HULK_METRIC_ values
-static bool metric_name_ok(const std::string &m) { return m == "jaccard" || m == "weightedjaccard" || m == "bottomk"; }
-static int metric_code(const std::string &m) { return m == "weightedjaccard" ? HULK_METRIC_WEIGHTED_JACCARD : m == "bottomk" ? HULK_METRIC_BOTTOMK : HULK_METRIC_JACCARD; }
-
 int hulk_smash_files(int device, const char *const *paths, uint32_t n_paths, uint32_t ksize, const char *algo, const char *metric,
                      uint32_t threads, const char *matrix_csv_path, const char *banner_csv_path, double *distances,
                      hulk_smash_stats *stats, char *errbuf, uint64_t errbuf_len) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string metric_s = metric, algo_s = algo;
-    // cmd/smash.go:60-82
-    if (!metric_name_ok(metric_s))
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (const int rc = check_names(errbuf, errbuf_len, metric, algo)) return rc;
     const double t0 = now_s();
-    hulk_sketch_set *set = nullptr;
-    { const int rc = hulk_load_sketches(paths, n_paths, ksize, algo, threads, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
+    std::unique_ptr<hulk_sketch_set> set;
+    if (const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, true, set, errbuf, errbuf_len)) return rc;
     const uint32_t n = (uint32_t)set->files.size(), S = set->size;
-    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
-    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    if (const int rc = check_metric_fits(errbuf, errbuf_len, metric, algo, set->histosketch)) return rc;
     const double t1 = now_s();
     std::vector<double> own;
-    double *dist = distances;
-    if (!dist) { own.resize((size_t)n * n); dist = own.data(); }
+    double *dist = own_or(distances, own, (size_t)n * n);
     double kernel_ms = 0.0;
-    {
-        const int rc = hulk_smash_ex(device, set->mins.data(), set->weights.data(), n, S, metric_code(metric_s),
-                                     dist, &kernel_ms);
-        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
-    }
+    if (const int rc = hulk_smash_ex(device, set->mins.data(), set->weights.data(), n, S, metric_code(metric), dist, &kernel_ms))
+        return put_lib_err(errbuf, errbuf_len, rc);
     const double t2 = now_s();
     if (matrix_csv_path) {
         std::vector<std::string> rows((size_t)n + 1);
@@ -661,61 +738,39 @@ int hulk_search_files(int device, const char *const *query_paths, uint32_t n_q, 
                       hulk_search_stats *stats, char *errbuf, uint64_t errbuf_len) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string metric_s = metric, algo_s = algo;
-    if (!metric_name_ok(metric_s))
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (const int rc = check_names(errbuf, errbuf_len, metric, algo)) return rc;
     if (k == 0 || k > HULK_SEARCH_MAX_K) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
     if (!role_ok(role)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: role");
     if (flags & ~HULK_SEARCH_SELF) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: unknown flags");
     const bool self = (flags & HULK_SEARCH_SELF) != 0;
     if (self && (db_paths || n_db)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: HULK_SEARCH_SELF takes no database");
     if (!self && !db_paths) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_search: no database (and no HULK_SEARCH_SELF)");
-    hulk_sketch_set *qs = nullptr, *ds = nullptr;
-    { const int rc = load_sketch_set(query_paths, n_q, ksize, algo, threads, false, &qs, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } gq{qs}, gd{nullptr};
+    std::unique_ptr<hulk_sketch_set> qs, ds;
+    if (const int rc = load_sketch_set(query_paths, n_q, ksize, algo, threads, false, qs, errbuf, errbuf_len)) return rc;
     if (!self) {
-        const int rc = load_sketch_set(db_paths, n_db, ksize, algo, threads, false, &ds, errbuf, errbuf_len);
-        if (rc != HULK_OK) return rc;
-        gd.s = ds;
+        if (const int rc = load_sketch_set(db_paths, n_db, ksize, algo, threads, false, ds, errbuf, errbuf_len)) return rc;
         if (qs->size != ds->size)                                   // sketchio.go:274-277
             return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(qs->size) + " vs " + std::to_string(ds->size) + "\n");
     }
-    if (metric_s == "weightedjaccard" && !qs->histosketch)          // sketchio.go:287-293
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
-    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
-    const hulk_sketch_set *db = self ? qs : ds;
+    if (const int rc = check_metric_fits(errbuf, errbuf_len, metric, algo, qs->histosketch)) return rc;
+    const hulk_sketch_set *db = self ? qs.get() : ds.get();
     const uint32_t m = (uint32_t)qs->files.size();
     std::vector<uint32_t> own_i, own_c; std::vector<double> own_d;
-    if (!hit_index) { own_i.resize((size_t)m * k); hit_index = own_i.data(); }
-    if (!hit_distance) { own_d.resize((size_t)m * k); hit_distance = own_d.data(); }
-    if (!hit_count) { own_c.resize(m); hit_count = own_c.data(); }
+    hit_index = own_or(hit_index, own_i, (size_t)m * k);
+    hit_distance = own_or(hit_distance, own_d, (size_t)m * k);
+    hit_count = own_or(hit_count, own_c, m);
     hulk_search_opts o;
     memset(&o, 0, sizeof o);
-    o.k = k; o.metric = metric_code(metric_s); o.role = role; o.flags = flags;
+    o.k = k; o.metric = metric_code(metric); o.role = role; o.flags = flags;
     o.max_distance = max_distance;
-    {
-        const int rc = hulk_search(device, qs->mins.data(), qs->weights.data(), m, self ? nullptr : ds->mins.data(), self ? nullptr : ds->weights.data(),
-                                   self ? 0 : (uint32_t)ds->files.size(), qs->size, &o, hit_index, hit_distance, hit_count, stats);
-        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
-    }
-    if (csv_path) {
-        std::vector<std::string> rows((size_t)m + 1);
-        rows[0] = "query,rank,hit,similarity\n";
-        parallel_for(m, pick_threads(threads, m), [&](size_t i) {
-            std::string &r = rows[i + 1];
-            for (uint32_t j = 0; j < hit_count[i]; j++) {
-                csv_field(r, qs->files[i].path); r += ','; r += std::to_string(j + 1); r += ',';
-                csv_field(r, db->files[hit_index[i * (size_t)k + j]].path); r += ',';
-                format_f2(r, 100 - (hit_distance[i * (size_t)k + j] * 100));       // cmd/smash.go:217
-                r += '\n';
-            }
-        });
-        std::string err;
-        if (!write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
-    }
+    if (const int rc = hulk_search(device, qs->mins.data(), qs->weights.data(), m, self ? nullptr : ds->mins.data(), self ? nullptr : ds->weights.data(),
+                                   self ? 0 : (uint32_t)ds->files.size(), qs->size, &o, hit_index, hit_distance, hit_count, stats))
+        return put_lib_err(errbuf, errbuf_len, rc);
+    std::string err;
+    if (csv_path && !write_hits_csv(csv_path, m, k, hit_index, hit_distance, hit_count, threads,
+                                    [&](uint32_t i) -> const std::string & { return qs->files[i].path; },
+                                    [&](uint32_t j) -> const std::string & { return db->files[j].path; }, err))
+        return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     return HULK_OK;
 }
 
@@ -723,18 +778,15 @@ int hulk_index_build_files(int device, const char *const *paths, uint32_t n_path
                            const hulk_index_opts *opts, hulk_index **index, char *errbuf, uint64_t errbuf_len) {
     if (index) *index = nullptr;
     if (!algo || !opts || !index) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string algo_s = algo;
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
-    hulk_sketch_set *set = nullptr;
-    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
+    if (const int rc = check_names(errbuf, errbuf_len, nullptr, algo)) return rc;
+    std::unique_ptr<hulk_sketch_set> set;
+    if (const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, set, errbuf, errbuf_len)) return rc;
     const uint32_t n = (uint32_t)set->files.size();
     hulk_index *ix = nullptr;
-    { const int rc = hulk_index_build(device, set->mins.data(), n, set->size, opts, &ix); if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr)); }
+    if (const int rc = hulk_index_build(device, set->mins.data(), n, set->size, opts, &ix)) return put_lib_err(errbuf, errbuf_len, rc);
     std::vector<const char *> names(n);
     for (uint32_t i = 0; i < n; i++) names[i] = set->files[i].path.c_str();
-    { const int rc = hulk_index_set_names(ix, names.data(), n); if (rc != HULK_OK) { hulk_index_free(ix); return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr)); } }
+    if (const int rc = hulk_index_set_names(ix, names.data(), n)) { hulk_index_free(ix); return put_lib_err(errbuf, errbuf_len, rc); }
     *index = ix;
     return HULK_OK;
 }
@@ -744,49 +796,31 @@ int hulk_index_search_files(hulk_index *index, const char *const *query_paths, u
                             double *hit_distance, uint32_t *hit_count, hulk_index_search_stats *stats, char *errbuf, uint64_t errbuf_len) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (!index || !algo || !opts) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string algo_s = algo;
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (const int rc = check_names(errbuf, errbuf_len, nullptr, algo)) return rc;
     const uint32_t k = opts->k;
     if (k == 0 || k > HULK_SEARCH_MAX_K) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_index_search: k must be 1 .. " + std::to_string(HULK_SEARCH_MAX_K));
     const bool self = (opts->flags & HULK_SEARCH_SELF) != 0;
     if (self && (query_paths || n_q)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_index_search: HULK_SEARCH_SELF takes no queries");
     uint32_t n = 0, S = 0;
     hulk_index_info(index, &n, &S, nullptr, nullptr, nullptr);
-    hulk_sketch_set *qs = nullptr;
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } gq{nullptr};
+    std::unique_ptr<hulk_sketch_set> qs;
     if (!self) {
-        const int rc = load_sketch_set(query_paths, n_q, ksize, algo, threads, false, &qs, errbuf, errbuf_len);
-        if (rc != HULK_OK) return rc;
-        gq.s = qs;
+        if (const int rc = load_sketch_set(query_paths, n_q, ksize, algo, threads, false, qs, errbuf, errbuf_len)) return rc;
         if (qs->size != S)                                          // sketchio.go:274-277
             return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(qs->size) + " vs " + std::to_string(S) + "\n");
     }
     const uint32_t m = self ? n : (uint32_t)qs->files.size();
     std::vector<uint32_t> own_i, own_c; std::vector<double> own_d;
-    if (!hit_index) { own_i.resize((size_t)m * k); hit_index = own_i.data(); }
-    if (!hit_distance) { own_d.resize((size_t)m * k); hit_distance = own_d.data(); }
-    if (!hit_count) { own_c.resize(m); hit_count = own_c.data(); }
-    {
-        const int rc = hulk_index_search(index, self ? nullptr : qs->mins.data(), m, opts, hit_index, hit_distance, hit_count, stats);
-        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
-    }
-    if (csv_path) {
-        std::vector<std::string> rows((size_t)m + 1);
-        rows[0] = "query,rank,hit,similarity\n";
-        parallel_for(m, pick_threads(threads, m), [&](size_t i) {
-            std::string &r = rows[i + 1];
-            const std::string query = self ? std::string(hulk_index_name(index, (uint32_t)i)) : qs->files[i].path;
-            for (uint32_t j = 0; j < hit_count[i]; j++) {
-                csv_field(r, query); r += ','; r += std::to_string(j + 1); r += ',';
-                csv_field(r, hulk_index_name(index, hit_index[i * (size_t)k + j])); r += ',';
-                format_f2(r, 100 - (hit_distance[i * (size_t)k + j] * 100));       // cmd/smash.go:217
-                r += '\n';
-            }
-        });
-        std::string err;
-        if (!write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
-    }
+    hit_index = own_or(hit_index, own_i, (size_t)m * k);
+    hit_distance = own_or(hit_distance, own_d, (size_t)m * k);
+    hit_count = own_or(hit_count, own_c, m);
+    if (const int rc = hulk_index_search(index, self ? nullptr : qs->mins.data(), m, opts, hit_index, hit_distance, hit_count, stats))
+        return put_lib_err(errbuf, errbuf_len, rc);
+    std::string err;
+    if (csv_path && !write_hits_csv(csv_path, m, k, hit_index, hit_distance, hit_count, threads,
+                                    [&](uint32_t i) { return self ? std::string(hulk_index_name(index, i)) : qs->files[i].path; },
+                                    [&](uint32_t j) { return hulk_index_name(index, j); }, err))
+        return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     return HULK_OK;
 }
 
@@ -795,34 +829,21 @@ int hulk_cluster_files(int device, const char *const *paths, uint32_t n_paths, u
                        char *errbuf, uint64_t errbuf_len) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string metric_s = metric, algo_s = algo;
-    if (!metric_name_ok(metric_s))
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (const int rc = check_names(errbuf, errbuf_len, metric, algo)) return rc;
     if (!(max_distance >= 0.0 && max_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_cluster: max_distance must be in [0, 1]");
-    hulk_sketch_set *set = nullptr;
-    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
-    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
-    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    std::unique_ptr<hulk_sketch_set> set;
+    if (const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, set, errbuf, errbuf_len)) return rc;
+    if (const int rc = check_metric_fits(errbuf, errbuf_len, metric, algo, set->histosketch)) return rc;
     const uint32_t n = (uint32_t)set->files.size();
     std::vector<uint32_t> own;
-    if (!label) { own.resize(n); label = own.data(); }
+    label = own_or(label, own, n);
     hulk_cluster_opts o;
     memset(&o, 0, sizeof o);
-    o.metric = metric_code(metric_s);
+    o.metric = metric_code(metric);
     o.max_distance = max_distance;
-    {
-        const int rc = hulk_cluster(device, set->mins.data(), set->weights.data(), n, set->size, &o, label, stats);
-        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
-    }
-    if (csv_path) {
-        std::string err;
-        if (!write_clusters_csv(*set, label, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
-    }
+    if (const int rc = hulk_cluster(device, set->mins.data(), set->weights.data(), n, set->size, &o, label, stats)) return put_lib_err(errbuf, errbuf_len, rc);
+    std::string err;
+    if (csv_path && !write_clusters_csv(*set, label, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     return HULK_OK;
 }
 
@@ -839,11 +860,9 @@ static bool write_links_csv(const hulk_sketch_set &set, const hulk_link_list *li
         std::string subject;
         csv_field(subject, set.files[i].path);
         for (uint64_t e = row_start[i]; e < row_start[i + 1]; e++) {
-            char tmp[40];
-            snprintf(tmp, sizeof tmp, "%.17g", dist[e]);
             r += subject; r += ',';
-            csv_field(r, set.files[col[e]].path); r += ','; r += tmp; r += ',';
-            format_f2(r, 100 - (dist[e] * 100));                    // cmd/smash.go:217
+            csv_field(r, set.files[col[e]].path); r += ',';
+            distance_fields(r, dist[e]);
             r += '\n';
         }
     });
@@ -856,38 +875,25 @@ int hulk_links_files(int device, const char *const *paths, uint32_t n_paths, uin
     if (stats) memset(stats, 0, sizeof *stats);
     if (out) *out = nullptr;
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string metric_s = metric, algo_s = algo;
-    if (!metric_name_ok(metric_s))
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (const int rc = check_names(errbuf, errbuf_len, metric, algo)) return rc;
     if (!(max_distance >= 0.0 && max_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_links: max_distance must be in [0, 1]");
     if (flags & ~HULK_LINKS_UPPER) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_links: unknown flags");
-    hulk_sketch_set *set = nullptr;
-    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
-    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
-    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    std::unique_ptr<hulk_sketch_set> set;
+    if (const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, set, errbuf, errbuf_len)) return rc;
+    if (const int rc = check_metric_fits(errbuf, errbuf_len, metric, algo, set->histosketch)) return rc;
     const uint32_t n = (uint32_t)set->files.size();
     hulk_links_opts o;
     memset(&o, 0, sizeof o);
-    o.metric = metric_code(metric_s);
+    o.metric = metric_code(metric);
     o.max_distance = max_distance;
     o.flags = flags;
     o.max_edges = max_edges;
     hulk_link_list *list = nullptr;
-    {
-        const int rc = hulk_links(device, set->mins.data(), set->weights.data(), n, set->size, &o, &list, stats);
-        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
-    }
-    struct ListGuard { hulk_link_list *l; ~ListGuard() { hulk_link_list_free(l); } } list_guard{list};
-    if (csv_path) {
-        std::string err;
-        if (!write_links_csv(*set, list, threads, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
-    }
-    if (out) { *out = list; list_guard.l = nullptr; }
+    if (const int rc = hulk_links(device, set->mins.data(), set->weights.data(), n, set->size, &o, &list, stats)) return put_lib_err(errbuf, errbuf_len, rc);
+    std::unique_ptr<hulk_link_list, void (*)(hulk_link_list *)> owned(list, hulk_link_list_free);
+    std::string err;
+    if (csv_path && !write_links_csv(*set, list, threads, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    if (out) *out = owned.release();
     return HULK_OK;
 }
 
@@ -898,60 +904,36 @@ int hulk_dendrogram_files(int device, const char *const *paths, uint32_t n_paths
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_edges) *n_edges = 0;
     if (!algo || !metric) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string metric_s = metric, algo_s = algo;
-    if (!metric_name_ok(metric_s))
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
+    if (const int rc = check_names(errbuf, errbuf_len, metric, algo)) return rc;
     const bool cut = cut_distance == cut_distance;                  // NaN: no cut
     if (cut && !(cut_distance >= 0.0 && cut_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_dendrogram: cut_distance must be in [0, 1] (or NaN: no cut)");
     if (cut && !cut_csv_path) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_dendrogram: a cut_distance without a cut_csv_path");
-    hulk_sketch_set *set = nullptr;
-    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
-    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
-    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    std::unique_ptr<hulk_sketch_set> set;
+    if (const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, set, errbuf, errbuf_len)) return rc;
+    if (const int rc = check_metric_fits(errbuf, errbuf_len, metric, algo, set->histosketch)) return rc;
     const uint32_t n = (uint32_t)set->files.size();
     std::vector<uint32_t> own_a, own_b; std::vector<double> own_d;
     uint32_t m = 0;
-    if (!edge_a) { own_a.resize(n); edge_a = own_a.data(); }
-    if (!edge_b) { own_b.resize(n); edge_b = own_b.data(); }
-    if (!edge_distance) { own_d.resize(n); edge_distance = own_d.data(); }
+    edge_a = own_or(edge_a, own_a, n);
+    edge_b = own_or(edge_b, own_b, n);
+    edge_distance = own_or(edge_distance, own_d, n);
     hulk_dendrogram_opts o;
     memset(&o, 0, sizeof o);
-    o.metric = metric_code(metric_s);
-    {
-        const int rc = hulk_dendrogram(device, set->mins.data(), set->weights.data(), n, set->size, &o, edge_a, edge_b, edge_distance, &m, stats);
-        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
-    }
+    o.metric = metric_code(metric);
+    if (const int rc = hulk_dendrogram(device, set->mins.data(), set->weights.data(), n, set->size, &o, edge_a, edge_b, edge_distance, &m, stats))
+        return put_lib_err(errbuf, errbuf_len, rc);
     if (n_edges) *n_edges = m;
-    // the edges ascend by distance: one sequential union-find (the smaller root stays) gives the size of every merge and, stopped
-    // behind the last edge <= cut_distance, the labels of the cut
-    std::vector<uint32_t> up(n), size(n, 1), label;
+    // one sequential union-find over the edges (the smaller root stays) gives the size of every merge
+    std::vector<uint32_t> up(n), members(n, 1), size(m);
     for (uint32_t i = 0; i < n; i++) up[i] = i;
-    auto find = [&](uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; };
-    auto labels_now = [&] { label.resize(n); for (uint32_t i = 0; i < n; i++) label[i] = find(i); };
-    std::vector<std::string> rows((size_t)m + 1);
-    rows[0] = "merge,sketch_a,sketch_b,distance,similarity,size\n";
-    bool cut_taken = false;
     for (uint32_t e = 0; e < m; e++) {
-        if (cut && !cut_taken && !(edge_distance[e] <= cut_distance)) { labels_now(); cut_taken = true; }
-        const uint32_t a = find(edge_a[e]), b = find(edge_b[e]), lo = std::min(a, b), hi = std::max(a, b);
-        up[hi] = lo; size[lo] += size[hi];
-        std::string &r = rows[(size_t)e + 1];
-        char tmp[64];
-        r += std::to_string(e + 1); r += ',';
-        csv_field(r, set->files[edge_a[e]].path); r += ','; csv_field(r, set->files[edge_b[e]].path); r += ',';
-        snprintf(tmp, sizeof tmp, "%.17g", edge_distance[e]); r += tmp; r += ',';
-        format_f2(r, 100 - (edge_distance[e] * 100));               // cmd/smash.go:217
-        r += ','; r += std::to_string(size[lo]); r += '\n';
+        const uint32_t a = uf_root(up, edge_a[e]), b = uf_root(up, edge_b[e]), lo = std::min(a, b), hi = std::max(a, b);
+        up[hi] = lo; members[lo] += members[hi]; size[e] = members[lo];
     }
-    if (cut && !cut_taken) labels_now();
     std::string err;
-    if (csv_path && !write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
-    if (cut && !write_clusters_csv(*set, label.data(), cut_csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    if (csv_path && !write_merges_csv(set->files, edge_a, edge_b, edge_distance, size.data(), m, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    if (cut && !write_clusters_csv(*set, cut_labels(n, edge_a, edge_b, edge_distance, m, cut_distance).data(), cut_csv_path, err))
+        return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     return HULK_OK;
 }
 
@@ -962,65 +944,32 @@ int hulk_linkage_files(int device, const char *const *paths, uint32_t n_paths, u
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_merges) *n_merges = 0;
     if (!algo || !metric || !method) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "NULL");
-    const std::string metric_s = metric, algo_s = algo, method_s = method;
-    if (!metric_name_ok(metric_s))
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied distance metric is not available: " + metric_s + "\nplease select one of the following: [jaccard weightedjaccard bottomk]");
-    if (algo_s != "histosketch" && algo_s != "kmv" && algo_s != "khf")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied algorithm not available: " + algo_s + "\nplease select one of the following: [histosketch kmv khf]");
-    if (method_s != "single" && method_s != "complete" && method_s != "average")
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "supplied linkage is not available: " + method_s + "\nplease select one of the following: [single complete average]");
+    if (const int rc = check_names(errbuf, errbuf_len, metric, algo, method)) return rc;
     const bool cut = cut_distance == cut_distance;                  // NaN: no cut
     if (cut && !(cut_distance >= 0.0 && cut_distance <= 1.0)) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_linkage: cut_distance must be in [0, 1] (or NaN: no cut)");
     if (cut && !cut_csv_path) return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "hulk_linkage: a cut_distance without a cut_csv_path");
-    hulk_sketch_set *set = nullptr;
-    { const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, &set, errbuf, errbuf_len); if (rc != HULK_OK) return rc; }
-    struct Guard { hulk_sketch_set *s; ~Guard() { delete s; } } guard{set};
-    if (metric_s == "weightedjaccard" && !set->histosketch)         // sketchio.go:287-293
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "weighted jaccard is only supported for histosketches");
-    if (metric_s == "bottomk" && algo_s != "kmv")                   // the estimator of a sorted bottom-k list (KMVsketch.GetSimilarity): position i of a khf sketch is hash function i
-        return put_err(errbuf, errbuf_len, HULK_ERR_ARG, "bottomk is only supported for kmv sketches");
+    std::unique_ptr<hulk_sketch_set> set;
+    if (const int rc = load_sketch_set(paths, n_paths, ksize, algo, threads, false, set, errbuf, errbuf_len)) return rc;
+    if (const int rc = check_metric_fits(errbuf, errbuf_len, metric, algo, set->histosketch)) return rc;
     const uint32_t n = (uint32_t)set->files.size();
     std::vector<uint32_t> own_a, own_b, own_s; std::vector<double> own_d;
     uint32_t m = 0;
-    if (!merge_a) { own_a.resize(n); merge_a = own_a.data(); }
-    if (!merge_b) { own_b.resize(n); merge_b = own_b.data(); }
-    if (!merge_distance) { own_d.resize(n); merge_distance = own_d.data(); }
-    if (!merge_size) { own_s.resize(n); merge_size = own_s.data(); }
+    merge_a = own_or(merge_a, own_a, n);
+    merge_b = own_or(merge_b, own_b, n);
+    merge_distance = own_or(merge_distance, own_d, n);
+    merge_size = own_or(merge_size, own_s, n);
     hulk_linkage_opts o;
     memset(&o, 0, sizeof o);
-    o.metric = metric_code(metric_s);
+    o.metric = metric_code(metric);
+    const std::string method_s = method;
     o.method = method_s == "complete" ? HULK_LINKAGE_COMPLETE : method_s == "average" ? HULK_LINKAGE_AVERAGE : HULK_LINKAGE_SINGLE;
-    {
-        const int rc = hulk_linkage(device, set->mins.data(), set->weights.data(), n, set->size, &o, merge_a, merge_b, merge_distance, merge_size, &m, stats);
-        if (rc != HULK_OK) return put_err(errbuf, errbuf_len, rc, hulk_last_error(nullptr));
-    }
+    if (const int rc = hulk_linkage(device, set->mins.data(), set->weights.data(), n, set->size, &o, merge_a, merge_b, merge_distance, merge_size, &m, stats))
+        return put_lib_err(errbuf, errbuf_len, rc);
     if (n_merges) *n_merges = m;
-    std::vector<std::string> rows((size_t)m + 1);
-    rows[0] = "merge,sketch_a,sketch_b,distance,similarity,size\n";
-    for (uint32_t e = 0; e < m; e++) {
-        std::string &r = rows[(size_t)e + 1];
-        char tmp[64];
-        r += std::to_string(e + 1); r += ',';
-        csv_field(r, set->files[merge_a[e]].path); r += ','; csv_field(r, set->files[merge_b[e]].path); r += ',';
-        snprintf(tmp, sizeof tmp, "%.17g", merge_distance[e]); r += tmp; r += ',';
-        format_f2(r, 100 - (merge_distance[e] * 100));              // cmd/smash.go:217
-        r += ','; r += std::to_string(merge_size[e]); r += '\n';
-    }
     std::string err;
-    if (csv_path && !write_all(csv_path, rows, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
-    if (cut) {
-        // the merges at or below the cut, whatever their place in the order (average linkage may step down by a rounding)
-        std::vector<uint32_t> up(n), label(n);
-        for (uint32_t i = 0; i < n; i++) up[i] = i;
-        auto find = [&](uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; };
-        for (uint32_t e = 0; e < m; e++) {
-            if (!(merge_distance[e] <= cut_distance)) continue;
-            const uint32_t a = find(merge_a[e]), b = find(merge_b[e]);
-            if (a != b) up[std::max(a, b)] = std::min(a, b);
-        }
-        for (uint32_t i = 0; i < n; i++) label[i] = find(i);
-        if (!write_clusters_csv(*set, label.data(), cut_csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
-    }
+    if (csv_path && !write_merges_csv(set->files, merge_a, merge_b, merge_distance, merge_size, m, csv_path, err)) return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
+    if (cut && !write_clusters_csv(*set, cut_labels(n, merge_a, merge_b, merge_distance, m, cut_distance).data(), cut_csv_path, err))
+        return put_err(errbuf, errbuf_len, HULK_ERR_IO, err);
     return HULK_OK;
 }
 

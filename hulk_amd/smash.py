@@ -12,6 +12,7 @@ hulk_dendrogram_files); cut_dendrogram and linkage_matrix read it on the host.
 linkage / linkage_files: the single-, complete- or average-linkage dendrogram by agglomeration over the N x N matrix, which stays on the
 device (hulk_linkage, hulk_linkage_files); cut_dendrogram and linkage_matrix read its merges too.
 """
+import ctypes
 import fnmatch
 import glob
 import os
@@ -28,6 +29,79 @@ AVAIL_METRICS = ["jaccard", "weightedjaccard", "bottomk"]
 PANEL_METRICS = ["jaccard", "weightedjaccard"]          # panels score histosketch snapshots
 _METRIC_CODE = {"jaccard": _lib.HULK_METRIC_JACCARD, "weightedjaccard": _lib.HULK_METRIC_WEIGHTED_JACCARD, "bottomk": _lib.HULK_METRIC_BOTTOMK}
 AVAIL_ALGORITHMS = ["histosketch", "kmv", "khf"]        # sketchio.go:17
+AVAIL_LINKAGES = ["single", "complete", "average"]
+_LINKAGE_CODE = {"single": _lib.HULK_LINKAGE_SINGLE, "complete": _lib.HULK_LINKAGE_COMPLETE, "average": _lib.HULK_LINKAGE_AVERAGE}
+
+
+def _check_metric(metric, avail=AVAIL_METRICS):
+    if metric not in avail:
+        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {avail}")
+
+
+def _check_algo(algo):
+    if algo not in AVAIL_ALGORITHMS:
+        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+
+
+def _check_linkage(method):
+    if method not in AVAIL_LINKAGES:
+        raise HulkError(-30, f"supplied linkage is not available: {method}\nplease select one of the following: {AVAIL_LINKAGES}")
+
+
+def _sketch_arrays(mins, weights, metric):
+    """(mins as contiguous uint64, weights as _weights_for gives them), both [n][sketch_size]"""
+    m = np.ascontiguousarray(mins, dtype=np.uint64)
+    w = _weights_for(metric, m, weights)
+    if m.ndim != 2 or (w is not None and m.shape != w.shape):
+        raise ValueError("mins/weights must be [n][sketch_size]")
+    return m, w
+
+
+def _band_rows(band_rows):
+    band_rows = int(band_rows)
+    if not 0 <= band_rows < 2 ** 32:
+        raise ValueError("band_rows must be a multiple of 32 (0 = default)")
+    return band_rows
+
+
+def _u32_or_zero(x):
+    """x as a uint32 argument; out of range: 0, which the library refuses"""
+    return x if 0 <= x < 2 ** 32 else 0
+
+
+def _fs(path):
+    return None if path is None else os.fsencode(path)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _call(fn, *args):
+    """a direct call into the library: HulkError with hulk_last_error's text when it fails"""
+    rc = fn(*args)
+    if rc != 0:
+        raise HulkError(rc, _lib.load().hulk_last_error(None).decode("utf-8", "replace"))
+
+
+def _call_files(fn, *args):
+    """a *_files call: the library writes its text into the 4096-byte error buffer appended to args"""
+    err = ctypes.create_string_buffer(4096)
+    rc = fn(*args, err, len(err))
+    if rc != 0:
+        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+
+
+def _stats(st):
+    """a stats struct as a dict, one key per field"""
+    return {name: getattr(st, name) for name, _ in st._fields_}
+
+
+def _make_parent_dir(path):
+    """the directory of an output file, created (0700) when it does not exist"""
+    od = os.path.dirname(path)
+    if od and od != "." and not os.path.exists(od):
+        os.makedirs(od, mode=0o700)
 
 
 def collect_jsons(sketch_dir, recursive=False):
@@ -56,16 +130,13 @@ def distance_matrix(mins, weights, metric="jaccard", device=0, timing=None):
         raise ValueError("mins/weights must be [n_sketches][sketch_size]")
     n, s = mins.shape
     out = np.zeros((n, n), dtype=np.float64)
-    L = _lib.load()
-    import ctypes
     kms = ctypes.c_double(0.0)
-    rc = L.hulk_smash_ex(device, mins.ctypes.data, None if weights is None else weights.ctypes.data, n, s,
-                         _METRIC_CODE.get(metric, _lib.HULK_METRIC_JACCARD), out.ctypes.data,
-                         ctypes.byref(kms) if timing is not None else None)
-    if timing is not None:
-        timing["kernel_ms"] = kms.value
-    if rc != 0:
-        raise HulkError(rc, L.hulk_last_error(None).decode())
+    try:
+        _call(_lib.load().hulk_smash_ex, device, mins.ctypes.data, _ptr(weights), n, s, _METRIC_CODE.get(metric, _lib.HULK_METRIC_JACCARD),
+              out.ctypes.data, ctypes.byref(kms) if timing is not None else None)
+    finally:
+        if timing is not None:
+            timing["kernel_ms"] = kms.value
     return out
 
 
@@ -80,9 +151,7 @@ def panel_distances(snap_mins, snap_weights, panel_mins, panel_weights, metric="
     """distances[i, p] between sketch i of snap_* [m][S] and sketch p of panel_* [n_panel][S], on the GPU with the kernel that
     scores sketch snapshots against a panel (hulk_panel_distances): role "row" = sketch i is the subject (the block
     distance_matrix([snap; panel])[:m, m:]), "column" = panel sketch p is (the block [m:, :m] transposed).  One against many."""
-    import ctypes
-    if metric not in PANEL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {PANEL_METRICS}")
+    _check_metric(metric, PANEL_METRICS)
     if role not in ("row", "column"):
         raise ValueError("role must be 'row' or 'column'")
     sm = np.ascontiguousarray(snap_mins, dtype=np.uint64); sw = np.ascontiguousarray(snap_weights, dtype=np.float64)
@@ -92,27 +161,17 @@ def panel_distances(snap_mins, snap_weights, panel_mins, panel_weights, metric="
     if sm.shape[1] != pm.shape[1]:
         raise HulkError(-30, f"sketch length mismatch: {sm.shape[1]} vs {pm.shape[1]}\n")
     out = np.zeros((sm.shape[0], pm.shape[0]), dtype=np.float64)
-    L = _lib.load()
-    rc = L.hulk_panel_distances(device, sm.ctypes.data, sw.ctypes.data, sm.shape[0], pm.ctypes.data, pw.ctypes.data, pm.shape[0],
-                                sm.shape[1], _lib.HULK_METRIC_WEIGHTED_JACCARD if metric == "weightedjaccard" else _lib.HULK_METRIC_JACCARD,
-                                _lib.HULK_PANEL_COLUMN if role == "column" else _lib.HULK_PANEL_ROW, out.ctypes.data)
-    if rc != 0:
-        raise HulkError(rc, L.hulk_last_error(None).decode())
+    _call(_lib.load().hulk_panel_distances, device, sm.ctypes.data, sw.ctypes.data, sm.shape[0], pm.ctypes.data, pw.ctypes.data, pm.shape[0],
+          sm.shape[1], _METRIC_CODE[metric], _lib.HULK_PANEL_COLUMN if role == "column" else _lib.HULK_PANEL_ROW, out.ctypes.data)
     return out
 
 
 def _search_consts(metric, role):
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
+    _check_metric(metric)
     if role not in ("row", "column"):
         raise ValueError("role must be 'row' or 'column'")
     return (_METRIC_CODE[metric],
             _lib.HULK_PANEL_COLUMN if role == "column" else _lib.HULK_PANEL_ROW)
-
-
-def _stats_dict(st):
-    return dict(seconds_total=st.seconds_total, kernel_ms_dist=st.kernel_ms_dist, kernel_ms_select=st.kernel_ms_select,
-                strips=st.strips, query_blocks=st.query_blocks)
 
 
 def search(q_mins, q_weights, db_mins, db_weights, k, metric="jaccard", role="row", max_distance=None, self_search=False,
@@ -124,35 +183,26 @@ def search(q_mins, q_weights, db_mins, db_weights, k, metric="jaccard", role="ro
     db_weights are None, the queries are searched among themselves and the pair (i, i) is left out.  The database streams through
     the device in strips sized by scratch_bytes (0 = 1 GiB): no m x n_db array exists.  stats: a dict that receives
     seconds_total, kernel_ms_dist, kernel_ms_select, strips, query_blocks."""
-    import ctypes
     metric_c, role_c = _search_consts(metric, role)
-    qm = np.ascontiguousarray(q_mins, dtype=np.uint64); qw = _weights_for(metric, qm, q_weights)
-    if qm.ndim != 2 or (qw is not None and qm.shape != qw.shape):
-        raise ValueError("mins/weights must be [n][sketch_size]")
+    qm, qw = _sketch_arrays(q_mins, q_weights, metric)
     if self_search:
         if db_mins is not None or db_weights is not None:
             raise ValueError("self_search takes no database")
         dm = dw = None
     else:
-        dm = np.ascontiguousarray(db_mins, dtype=np.uint64); dw = _weights_for(metric, dm, db_weights)
-        if dm.ndim != 2 or (dw is not None and dm.shape != dw.shape):
-            raise ValueError("mins/weights must be [n][sketch_size]")
+        dm, dw = _sketch_arrays(db_mins, db_weights, metric)
         if qm.shape[1] != dm.shape[1]:
             raise HulkError(-30, f"sketch length mismatch: {qm.shape[1]} vs {dm.shape[1]}\n")
     m, k = qm.shape[0], int(k)
-    o = _lib.SearchOpts(k=k if 0 <= k < 2 ** 32 else 0, metric=metric_c, role=role_c, flags=_lib.HULK_SEARCH_SELF if self_search else 0,
+    o = _lib.SearchOpts(k=_u32_or_zero(k), metric=metric_c, role=role_c, flags=_lib.HULK_SEARCH_SELF if self_search else 0,
                         max_distance=-1.0 if max_distance is None else float(max_distance), scratch_bytes=int(scratch_bytes))
     kk = max(min(k, _lib.HULK_SEARCH_MAX_K), 1)
     index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(m, dtype=np.uint32)
     st = _lib.SearchStats()
-    L = _lib.load()
-    rc = L.hulk_search(device, qm.ctypes.data, None if qw is None else qw.ctypes.data, m, None if dm is None else dm.ctypes.data, None if dw is None else dw.ctypes.data,
-                       0 if dm is None else dm.shape[0], qm.shape[1], ctypes.byref(o), index.ctypes.data, dist.ctypes.data, count.ctypes.data,
-                       ctypes.byref(st))
-    if rc != 0:
-        raise HulkError(rc, L.hulk_last_error(None).decode())
+    _call(_lib.load().hulk_search, device, qm.ctypes.data, _ptr(qw), m, _ptr(dm), _ptr(dw), 0 if dm is None else dm.shape[0], qm.shape[1],
+          ctypes.byref(o), index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st))
     if stats is not None:
-        stats.update(_stats_dict(st))
+        stats.update(_stats(st))
     return index, dist, count
 
 
@@ -162,10 +212,8 @@ def search_files(query_files, db_files, k, ksize=21, algo="histosketch", metric=
     query file is fine), the search runs on the GPU and, csv_path given, the library writes "query,rank,hit,similarity" — one line
     per hit, the similarity the string `smash` prints for that pair.  -> (query ordering, database ordering, index, distance, count);
     the orderings are the sorted unique paths, index counts the database's."""
-    import ctypes
     _search_consts(metric, role)
-    if algo not in AVAIL_ALGORITHMS:
-        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    _check_algo(algo)
     q_order = sorted(set(query_files))
     d_order = q_order if self_search else sorted(set(db_files))
     k = int(k)
@@ -175,23 +223,12 @@ def search_files(query_files, db_files, k, ksize=21, algo="histosketch", metric=
     qa, nq = _paths(query_files)
     da, nd = (None, 0) if self_search else _paths(db_files)
     st = _lib.SearchStats()
-    err = ctypes.create_string_buffer(4096)
-    L = _lib.load()
-    rc = L.hulk_search_files(device, qa, nq, da, nd, ksize, algo.encode(), metric.encode(), 1 if role == "column" else 0,
-                             k if 0 <= k < 2 ** 32 else 0, -1.0 if max_distance is None else float(max_distance),
-                             _lib.HULK_SEARCH_SELF if self_search else 0, threads, None if csv_path is None else os.fsencode(csv_path),
-                             index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st), err, len(err))
-    if rc != 0:
-        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    _call_files(_lib.load().hulk_search_files, device, qa, nq, da, nd, ksize, algo.encode(), metric.encode(), 1 if role == "column" else 0,
+                _u32_or_zero(k), -1.0 if max_distance is None else float(max_distance), _lib.HULK_SEARCH_SELF if self_search else 0, threads,
+                _fs(csv_path), index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st))
     if stats is not None:
-        stats.update(_stats_dict(st))
+        stats.update(_stats(st))
     return q_order, d_order, index, dist, count[:m]
-
-
-def _index_stats_dict(st):
-    return dict(seconds_total=st.seconds_total, kernel_ms_keys=st.kernel_ms_keys, kernel_ms_probe=st.kernel_ms_probe,
-                kernel_ms_verify=st.kernel_ms_verify, kernel_ms_select=st.kernel_ms_select, candidates=st.candidates, within=st.within,
-                query_blocks=st.query_blocks, pieces=st.pieces)
 
 
 class Index:
@@ -206,56 +243,42 @@ class Index:
 
     @staticmethod
     def _opts(max_distance, bands, metric):
-        if metric not in AVAIL_METRICS:
-            raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-        code = {"jaccard": _lib.HULK_METRIC_JACCARD, "weightedjaccard": _lib.HULK_METRIC_WEIGHTED_JACCARD, "bottomk": _lib.HULK_METRIC_BOTTOMK}[metric]
+        _check_metric(metric)
         bands = int(bands)
-        return _lib.IndexOpts(max_distance=float(max_distance), bands=bands if 0 <= bands < 2 ** 32 else 0xFFFFFFFF, metric=code)
+        return _lib.IndexOpts(max_distance=float(max_distance), bands=bands if 0 <= bands < 2 ** 32 else 0xFFFFFFFF, metric=_METRIC_CODE[metric])
 
     @classmethod
     def build(cls, mins, max_distance, bands=0, device=0, names=None, metric="jaccard"):
         """mins [n][S] uint64 -> Index.  names: n strings (search_files' CSV and .names report them)."""
-        import ctypes
         m = np.ascontiguousarray(mins, dtype=np.uint64)
         if m.ndim != 2:
             raise ValueError("mins must be [n][sketch_size]")
         o = cls._opts(max_distance, bands, metric)
         L = _lib.load()
         h = ctypes.c_void_p()
-        rc = L.hulk_index_build(device, m.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), ctypes.byref(h))
-        if rc != 0:
-            raise HulkError(rc, L.hulk_last_error(None).decode())
+        _call(L.hulk_index_build, device, m.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), ctypes.byref(h))
         ix = cls(h)
         if names is not None:
-            arr, n = _paths(names)
-            rc = L.hulk_index_set_names(h, arr, n)
-            if rc != 0:
+            try:
+                _call(L.hulk_index_set_names, h, *_paths(names))
+            except HulkError:
                 ix.close()
-                raise HulkError(rc, L.hulk_last_error(None).decode())
+                raise
         return ix
 
     @classmethod
     def build_files(cls, files, max_distance, bands=0, ksize=21, algo="histosketch", threads=0, device=0):
         """The sketch files through the native loader (MD5, FindSketch, the reference's error texts); the sorted unique paths are the names."""
-        import ctypes
         o = cls._opts(max_distance, bands, "jaccard")
         arr, n = _paths(files)
-        L = _lib.load()
         h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(4096)
-        rc = L.hulk_index_build_files(device, arr, n, ksize, algo.encode(), threads, ctypes.byref(o), ctypes.byref(h), err, len(err))
-        if rc != 0:
-            raise HulkError(rc, err.value.decode("utf-8", "replace"))
+        _call_files(_lib.load().hulk_index_build_files, device, arr, n, ksize, algo.encode(), threads, ctypes.byref(o), ctypes.byref(h))
         return cls(h)
 
     @classmethod
     def load(cls, path, device=0):
-        import ctypes
-        L = _lib.load()
         h = ctypes.c_void_p()
-        rc = L.hulk_index_load(device, os.fsencode(path), ctypes.byref(h))
-        if rc != 0:
-            raise HulkError(rc, L.hulk_last_error(None).decode("utf-8", "replace"))
+        _call(_lib.load().hulk_index_load, device, os.fsencode(path), ctypes.byref(h))
         return cls(h)
 
     def _handle(self):
@@ -264,15 +287,11 @@ class Index:
         return self._h
 
     def save(self, path):
-        L = _lib.load()
-        rc = L.hulk_index_save(self._handle(), os.fsencode(path))
-        if rc != 0:
-            raise HulkError(rc, L.hulk_last_error(None).decode("utf-8", "replace"))
+        _call(_lib.load().hulk_index_save, self._handle(), os.fsencode(path))
 
     @property
     def info(self):
         """dict(n, sketch_size, bands, max_distance, device_bytes)"""
-        import ctypes
         n, s, b, d, by = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_double(), ctypes.c_uint64()
         _lib.load().hulk_index_info(self._handle(), ctypes.byref(n), ctypes.byref(s), ctypes.byref(b), ctypes.byref(d), ctypes.byref(by))
         return dict(n=n.value, sketch_size=s.value, bands=b.value, max_distance=d.value, device_bytes=by.value)
@@ -284,7 +303,7 @@ class Index:
 
     def _search_opts(self, k, max_distance, self_search, scratch_bytes):
         k = int(k)
-        o = _lib.IndexSearchOpts(k=k if 0 <= k < 2 ** 32 else 0, flags=_lib.HULK_SEARCH_SELF if self_search else 0,
+        o = _lib.IndexSearchOpts(k=_u32_or_zero(k), flags=_lib.HULK_SEARCH_SELF if self_search else 0,
                                  max_distance=-1.0 if max_distance is None else float(max_distance), scratch_bytes=int(scratch_bytes))
         return o, max(min(k, _lib.HULK_SEARCH_MAX_K), 1)
 
@@ -292,7 +311,6 @@ class Index:
         """-> (index[m][k] uint32, distance[m][k], count[m]) as search() gives them.  max_distance None: the build's; above the
         build's: HulkError.  self_search: q_mins is None and the queries are the indexed sketches, (i, i) left out.  stats: a dict
         that receives candidates, within, the kernel milliseconds per phase, query_blocks, pieces."""
-        import ctypes
         h = self._handle()
         if self_search:
             if q_mins is not None:
@@ -308,20 +326,15 @@ class Index:
         o, kk = self._search_opts(k, max_distance, self_search, scratch_bytes)
         index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(max(m, 1), dtype=np.uint32)
         st = _lib.IndexSearchStats()
-        L = _lib.load()
-        rc = L.hulk_index_search(h, None if qm is None else qm.ctypes.data, m, ctypes.byref(o), index.ctypes.data, dist.ctypes.data,
-                                 count.ctypes.data, ctypes.byref(st))
-        if rc != 0:
-            raise HulkError(rc, L.hulk_last_error(None).decode())
+        _call(_lib.load().hulk_index_search, h, _ptr(qm), m, ctypes.byref(o), index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st))
         if stats is not None:
-            stats.update(_index_stats_dict(st))
+            stats.update(_stats(st))
         return index, dist, count[:m]
 
     def search_files(self, query_files, k, max_distance=None, self_search=False, ksize=21, algo="histosketch", csv_path=None, threads=0,
                      stats=None):
         """The query files through the native loader; csv_path: search_files' "query,rank,hit,similarity".
         -> (query ordering, index, distance, count)"""
-        import ctypes
         h = self._handle()
         q_order = self.names if self_search else sorted(set(query_files))
         m = len(q_order)
@@ -329,14 +342,10 @@ class Index:
         index = np.zeros((m, kk), dtype=np.uint32); dist = np.zeros((m, kk), dtype=np.float64); count = np.zeros(max(m, 1), dtype=np.uint32)
         qa, nq = (None, 0) if self_search else _paths(query_files)
         st = _lib.IndexSearchStats()
-        err = ctypes.create_string_buffer(4096)
-        L = _lib.load()
-        rc = L.hulk_index_search_files(h, qa, nq, ksize, algo.encode(), threads, ctypes.byref(o), None if csv_path is None else os.fsencode(csv_path),
-                                       index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st), err, len(err))
-        if rc != 0:
-            raise HulkError(rc, err.value.decode("utf-8", "replace"))
+        _call_files(_lib.load().hulk_index_search_files, h, qa, nq, ksize, algo.encode(), threads, ctypes.byref(o), _fs(csv_path),
+                    index.ctypes.data, dist.ctypes.data, count.ctypes.data, ctypes.byref(st))
         if stats is not None:
-            stats.update(_index_stats_dict(st))
+            stats.update(_stats(st))
         return q_order, index, dist, count[:m]
 
     def close(self):
@@ -357,11 +366,6 @@ class Index:
             pass
 
 
-def _cluster_stats_dict(st):
-    return dict(seconds_total=st.seconds_total, kernel_ms_link=st.kernel_ms_link, kernel_ms_flatten=st.kernel_ms_flatten,
-                links=st.links, bands=st.bands, clusters=st.clusters)
-
-
 def cluster(mins, weights, max_distance, metric="jaccard", band_rows=0, device=0, stats=None):
     """Single-linkage clusters of a sketch collection at a distance threshold, on the GPU (hulk_cluster): -> (labels uint32[N],
     n_clusters).  With D = distance_matrix(mins, weights, metric), sketches i != j are linked when D[i, j] <= max_distance or
@@ -369,25 +373,15 @@ def cluster(mins, weights, max_distance, metric="jaccard", band_rows=0, device=0
     member.  max_distance must be in [0, 1]; band_rows (a multiple of 32, 0 = 2048): the subject rows one kernel launch takes —
     it cannot change the result.  stats: a dict that receives seconds_total, kernel_ms_link, kernel_ms_flatten, links (the
     ordered pairs i != j with D[i, j] <= max_distance), bands, clusters."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
-    if m.ndim != 2 or (w is not None and m.shape != w.shape):
-        raise ValueError("mins/weights must be [n][sketch_size]")
-    band_rows = int(band_rows)
-    if not 0 <= band_rows < 2 ** 32:
-        raise ValueError("band_rows must be a multiple of 32 (0 = default)")
-    o = _lib.ClusterOpts(metric=_METRIC_CODE[metric],
-                         max_distance=float(max_distance), band_rows=band_rows)
+    _check_metric(metric)
+    m, w = _sketch_arrays(mins, weights, metric)
+    band_rows = _band_rows(band_rows)
+    o = _lib.ClusterOpts(metric=_METRIC_CODE[metric], max_distance=float(max_distance), band_rows=band_rows)
     labels = np.zeros(max(m.shape[0], 1), dtype=np.uint32)
     st = _lib.ClusterStats()
-    L = _lib.load()
-    rc = L.hulk_cluster(device, m.ctypes.data, None if w is None else w.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), labels.ctypes.data, ctypes.byref(st))
-    if rc != 0:
-        raise HulkError(rc, L.hulk_last_error(None).decode())
+    _call(_lib.load().hulk_cluster, device, m.ctypes.data, _ptr(w), m.shape[0], m.shape[1], ctypes.byref(o), labels.ctypes.data, ctypes.byref(st))
     if stats is not None:
-        stats.update(_cluster_stats_dict(st))
+        stats.update(_stats(st))
     return labels[:m.shape[0]], int(st.clusters)
 
 
@@ -396,34 +390,21 @@ def cluster_files(files, max_distance, ksize=21, algo="histosketch", metric="jac
     fine), the clustering runs on the GPU and, csv_path given, the library writes "sketch,cluster,size,representative" — one line
     per sketch in sorted path order: the 1-based ordinal of its cluster (ordered by smallest member), the cluster's size and the
     path of its smallest member.  -> (ordering, labels, n_clusters); ordering = the sorted unique paths, labels index it."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    if algo not in AVAIL_ALGORITHMS:
-        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    _check_metric(metric)
+    _check_algo(algo)
     ordering = sorted(set(files))
     labels = np.zeros(max(len(ordering), 1), dtype=np.uint32)
     arr, n = _paths(files)
     st = _lib.ClusterStats()
-    err = ctypes.create_string_buffer(4096)
-    L = _lib.load()
-    rc = L.hulk_cluster_files(device, arr, n, ksize, algo.encode(), metric.encode(), float(max_distance), threads,
-                              None if csv_path is None else os.fsencode(csv_path), labels.ctypes.data, ctypes.byref(st), err, len(err))
-    if rc != 0:
-        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    _call_files(_lib.load().hulk_cluster_files, device, arr, n, ksize, algo.encode(), metric.encode(), float(max_distance), threads, _fs(csv_path),
+                labels.ctypes.data, ctypes.byref(st))
     if stats is not None:
-        stats.update(_cluster_stats_dict(st))
+        stats.update(_stats(st))
     return ordering, labels[:len(ordering)], int(st.clusters)
-
-
-def _links_stats_dict(st):
-    return dict(seconds_total=st.seconds_total, kernel_ms_count=st.kernel_ms_count, kernel_ms_fill=st.kernel_ms_fill,
-                edges=st.edges, bands=st.bands, max_degree=st.max_degree)
 
 
 def _take_link_list(L, handle):
     """numpy copies of a hulk_link_list; the list is freed"""
-    import ctypes
     try:
         n, edges = ctypes.c_uint32(), ctypes.c_uint64()
         L.hulk_link_list_info(handle, ctypes.byref(n), ctypes.byref(edges))
@@ -447,15 +428,9 @@ def links(mins, weights, max_distance, metric="jaccard", upper=False, max_edges=
     and the count reached (stats["edges"] has the count so far).  band_rows as in cluster(): it cannot change the result.
     scipy.sparse.csr_matrix((distances, indices, indptr), shape=(N, N)) takes the three arrays as they are.  stats: a dict that
     receives seconds_total, kernel_ms_count, kernel_ms_fill, edges, bands, max_degree."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
-    if m.ndim != 2 or (w is not None and m.shape != w.shape):
-        raise ValueError("mins/weights must be [n][sketch_size]")
-    band_rows, max_edges = int(band_rows), int(max_edges)
-    if not 0 <= band_rows < 2 ** 32:
-        raise ValueError("band_rows must be a multiple of 32 (0 = default)")
+    _check_metric(metric)
+    m, w = _sketch_arrays(mins, weights, metric)
+    band_rows, max_edges = _band_rows(band_rows), int(max_edges)
     if not 0 <= max_edges < 2 ** 64:
         raise ValueError("max_edges must be non-negative (0 = no cap)")
     o = _lib.LinksOpts(metric=_METRIC_CODE[metric], max_distance=float(max_distance), band_rows=band_rows,
@@ -463,11 +438,11 @@ def links(mins, weights, max_distance, metric="jaccard", upper=False, max_edges=
     st = _lib.LinksStats()
     handle = ctypes.c_void_p()
     L = _lib.load()
-    rc = L.hulk_links(device, m.ctypes.data, None if w is None else w.ctypes.data, m.shape[0], m.shape[1], ctypes.byref(o), ctypes.byref(handle), ctypes.byref(st))
-    if stats is not None:
-        stats.update(_links_stats_dict(st))
-    if rc != 0:
-        raise HulkError(rc, L.hulk_last_error(None).decode())
+    try:
+        _call(L.hulk_links, device, m.ctypes.data, _ptr(w), m.shape[0], m.shape[1], ctypes.byref(o), ctypes.byref(handle), ctypes.byref(st))
+    finally:                                                        # (also on failure: the max_edges error leaves the count so far)
+        if stats is not None:
+            stats.update(_stats(st))
     return _take_link_list(L, handle)
 
 
@@ -477,30 +452,20 @@ def links_files(files, max_distance, ksize=21, algo="histosketch", metric="jacca
     the links are listed on the GPU and, csv_path given, the library writes "sketch,neighbour,distance,similarity" — one line per
     edge in CSR order: the two paths, the distance as %.17g and the similarity string `smash` prints for the pair.
     -> (ordering, indptr, indices, distances); ordering = the sorted unique paths, which the rows and indices count."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    if algo not in AVAIL_ALGORITHMS:
-        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    _check_metric(metric)
+    _check_algo(algo)
     ordering = sorted(set(files))
     arr, n = _paths(files)
     st = _lib.LinksStats()
-    err = ctypes.create_string_buffer(4096)
     handle = ctypes.c_void_p()
     L = _lib.load()
-    rc = L.hulk_links_files(device, arr, n, ksize, algo.encode(), metric.encode(), float(max_distance), _lib.HULK_LINKS_UPPER if upper else 0,
-                            int(max_edges), threads, None if csv_path is None else os.fsencode(csv_path), ctypes.byref(handle), ctypes.byref(st),
-                            err, len(err))
-    if stats is not None:
-        stats.update(_links_stats_dict(st))
-    if rc != 0:
-        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    try:
+        _call_files(L.hulk_links_files, device, arr, n, ksize, algo.encode(), metric.encode(), float(max_distance), _lib.HULK_LINKS_UPPER if upper else 0,
+                    int(max_edges), threads, _fs(csv_path), ctypes.byref(handle), ctypes.byref(st))
+    finally:
+        if stats is not None:
+            stats.update(_stats(st))
     return (ordering,) + _take_link_list(L, handle)
-
-
-def _dendrogram_stats_dict(st):
-    return dict(seconds_total=st.seconds_total, kernel_ms_offer=st.kernel_ms_offer, kernel_ms_fold=st.kernel_ms_fold,
-                rounds=st.rounds, bands=st.bands, edges=st.edges, components=st.components)
 
 
 def dendrogram(mins, weights, metric="jaccard", band_rows=0, device=0, stats=None):
@@ -510,28 +475,17 @@ def dendrogram(mins, weights, metric="jaccard", band_rows=0, device=0, stats=Non
     is what Kruskal gives on that order: E = N - (components of the non-NaN graph), and cut_dendrogram(N, a, b, d, tau) is
     cluster(mins, weights, tau, metric) for every tau.  band_rows (a multiple of 32, 0 = 2048) cannot change the result.  stats: a
     dict that receives seconds_total, kernel_ms_offer, kernel_ms_fold, rounds, bands (per round), edges, components."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
-    if m.ndim != 2 or (w is not None and m.shape != w.shape):
-        raise ValueError("mins/weights must be [n][sketch_size]")
-    band_rows = int(band_rows)
-    if not 0 <= band_rows < 2 ** 32:
-        raise ValueError("band_rows must be a multiple of 32 (0 = default)")
-    o = _lib.DendrogramOpts(metric=_METRIC_CODE[metric],
-                            band_rows=band_rows)
+    _check_metric(metric)
+    m, w = _sketch_arrays(mins, weights, metric)
+    o = _lib.DendrogramOpts(metric=_METRIC_CODE[metric], band_rows=_band_rows(band_rows))
     n = m.shape[0]
     a = np.zeros(max(n, 1), dtype=np.uint32); b = np.zeros(max(n, 1), dtype=np.uint32); d = np.zeros(max(n, 1), dtype=np.float64)
     ne = ctypes.c_uint32(0)
     st = _lib.DendrogramStats()
-    L = _lib.load()
-    rc = L.hulk_dendrogram(device, m.ctypes.data, None if w is None else w.ctypes.data, n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data, d.ctypes.data,
-                           ctypes.byref(ne), ctypes.byref(st))
-    if rc != 0:
-        raise HulkError(rc, L.hulk_last_error(None).decode())
+    _call(_lib.load().hulk_dendrogram, device, m.ctypes.data, _ptr(w), n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data, d.ctypes.data,
+          ctypes.byref(ne), ctypes.byref(st))
     if stats is not None:
-        stats.update(_dendrogram_stats_dict(st))
+        stats.update(_stats(st))
     return a[:ne.value], b[:ne.value], d[:ne.value]
 
 
@@ -542,38 +496,20 @@ def dendrogram_files(files, ksize=21, algo="histosketch", metric="jaccard", csv_
     similarity,size" — one line per merge: its 1-based ordinal, the two paths, the distance as %.17g, the similarity as `smash`
     prints it, the size of the cluster the merge creates.  cut_distance (in [0, 1]) with cut_csv_path: the file cluster_files
     writes at that max_distance, byte for byte.  -> (ordering, a, b, d); ordering = the sorted unique paths, a and b index it."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    if algo not in AVAIL_ALGORITHMS:
-        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    _check_metric(metric)
+    _check_algo(algo)
     ordering = sorted(set(files))
     n = max(len(ordering), 1)
     a = np.zeros(n, dtype=np.uint32); b = np.zeros(n, dtype=np.uint32); d = np.zeros(n, dtype=np.float64)
     ne = ctypes.c_uint32(0)
     arr, n_paths = _paths(files)
     st = _lib.DendrogramStats()
-    err = ctypes.create_string_buffer(4096)
-    L = _lib.load()
-    rc = L.hulk_dendrogram_files(device, arr, n_paths, ksize, algo.encode(), metric.encode(), threads,
-                                 None if csv_path is None else os.fsencode(csv_path),
-                                 float("nan") if cut_distance is None else float(cut_distance),
-                                 None if cut_csv_path is None else os.fsencode(cut_csv_path),
-                                 a.ctypes.data, b.ctypes.data, d.ctypes.data, ctypes.byref(ne), ctypes.byref(st), err, len(err))
-    if rc != 0:
-        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    _call_files(_lib.load().hulk_dendrogram_files, device, arr, n_paths, ksize, algo.encode(), metric.encode(), threads, _fs(csv_path),
+                float("nan") if cut_distance is None else float(cut_distance), _fs(cut_csv_path),
+                a.ctypes.data, b.ctypes.data, d.ctypes.data, ctypes.byref(ne), ctypes.byref(st))
     if stats is not None:
-        stats.update(_dendrogram_stats_dict(st))
+        stats.update(_stats(st))
     return ordering, a[:ne.value], b[:ne.value], d[:ne.value]
-
-
-AVAIL_LINKAGES = ["single", "complete", "average"]
-_LINKAGE_CODE = {"single": _lib.HULK_LINKAGE_SINGLE, "complete": _lib.HULK_LINKAGE_COMPLETE, "average": _lib.HULK_LINKAGE_AVERAGE}
-
-
-def _linkage_stats_dict(st):
-    return dict(seconds_total=st.seconds_total, kernel_ms_matrix=st.kernel_ms_matrix, kernel_ms_merge=st.kernel_ms_merge,
-                merges=st.merges, components=st.components, rows_rescanned=st.rows_rescanned)
 
 
 def linkage(mins, weights, method, metric="jaccard", device=0, stats=None):
@@ -585,27 +521,19 @@ def linkage(mins, weights, method, metric="jaccard", device=0, stats=None):
     the finite graph).  a and b are members of the merged clusters: cut_dendrogram(N, a, b, d, tau) and linkage_matrix(N, a, b, d)
     read the result as they read dendrogram()'s.  The N x N matrix stays on the device (8 * N * N bytes, N at most 65,536).
     stats: a dict that receives seconds_total, kernel_ms_matrix, kernel_ms_merge, merges, components, rows_rescanned."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    if method not in AVAIL_LINKAGES:
-        raise HulkError(-30, f"supplied linkage is not available: {method}\nplease select one of the following: {AVAIL_LINKAGES}")
-    m = np.ascontiguousarray(mins, dtype=np.uint64); w = _weights_for(metric, m, weights)
-    if m.ndim != 2 or (w is not None and m.shape != w.shape):
-        raise ValueError("mins/weights must be [n][sketch_size]")
+    _check_metric(metric)
+    _check_linkage(method)
+    m, w = _sketch_arrays(mins, weights, metric)
     o = _lib.LinkageOpts(metric=_METRIC_CODE[metric], method=_LINKAGE_CODE[method])
     n = m.shape[0]
     a = np.zeros(max(n, 1), dtype=np.uint32); b = np.zeros(max(n, 1), dtype=np.uint32); d = np.zeros(max(n, 1), dtype=np.float64)
     size = np.zeros(max(n, 1), dtype=np.uint32)
     nm = ctypes.c_uint32(0)
     st = _lib.LinkageStats()
-    L = _lib.load()
-    rc = L.hulk_linkage(device, m.ctypes.data, None if w is None else w.ctypes.data, n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data,
-                        d.ctypes.data, size.ctypes.data, ctypes.byref(nm), ctypes.byref(st))
-    if rc != 0:
-        raise HulkError(rc, L.hulk_last_error(None).decode())
+    _call(_lib.load().hulk_linkage, device, m.ctypes.data, _ptr(w), n, m.shape[1], ctypes.byref(o), a.ctypes.data, b.ctypes.data,
+          d.ctypes.data, size.ctypes.data, ctypes.byref(nm), ctypes.byref(st))
     if stats is not None:
-        stats.update(_linkage_stats_dict(st))
+        stats.update(_stats(st))
     return a[:nm.value], b[:nm.value], d[:nm.value], size[:nm.value]
 
 
@@ -614,30 +542,20 @@ def linkage_files(files, method, ksize=21, algo="histosketch", metric="jaccard",
     """The directory form (hulk_linkage_files): dendrogram_files' loader, CSV ("merge,sketch_a,sketch_b,distance,similarity,size", one
     line per merge in the order performed) and cut (the clusters file of the merges with distance <= cut_distance: what
     cut_dendrogram gives), under the linkage `method`.  -> (ordering, a, b, d, size); ordering = the sorted unique paths."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    if algo not in AVAIL_ALGORITHMS:
-        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
-    if method not in AVAIL_LINKAGES:
-        raise HulkError(-30, f"supplied linkage is not available: {method}\nplease select one of the following: {AVAIL_LINKAGES}")
+    _check_metric(metric)
+    _check_algo(algo)
+    _check_linkage(method)
     ordering = sorted(set(files))
     n = max(len(ordering), 1)
     a = np.zeros(n, dtype=np.uint32); b = np.zeros(n, dtype=np.uint32); d = np.zeros(n, dtype=np.float64); size = np.zeros(n, dtype=np.uint32)
     nm = ctypes.c_uint32(0)
     arr, n_paths = _paths(files)
     st = _lib.LinkageStats()
-    err = ctypes.create_string_buffer(4096)
-    L = _lib.load()
-    rc = L.hulk_linkage_files(device, arr, n_paths, ksize, algo.encode(), metric.encode(), method.encode(), threads,
-                              None if csv_path is None else os.fsencode(csv_path),
-                              float("nan") if cut_distance is None else float(cut_distance),
-                              None if cut_csv_path is None else os.fsencode(cut_csv_path),
-                              a.ctypes.data, b.ctypes.data, d.ctypes.data, size.ctypes.data, ctypes.byref(nm), ctypes.byref(st), err, len(err))
-    if rc != 0:
-        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    _call_files(_lib.load().hulk_linkage_files, device, arr, n_paths, ksize, algo.encode(), metric.encode(), method.encode(), threads, _fs(csv_path),
+                float("nan") if cut_distance is None else float(cut_distance), _fs(cut_csv_path),
+                a.ctypes.data, b.ctypes.data, d.ctypes.data, size.ctypes.data, ctypes.byref(nm), ctypes.byref(st))
     if stats is not None:
-        stats.update(_linkage_stats_dict(st))
+        stats.update(_stats(st))
     return ordering, a[:nm.value], b[:nm.value], d[:nm.value], size[:nm.value]
 
 
@@ -727,7 +645,6 @@ def find_sketch(data, ksize, algo, path):
 
 
 def _paths(files):
-    import ctypes
     enc = [os.fsencode(f) for f in files]
     return (ctypes.c_char_p * max(len(enc), 1))(*enc), len(enc)
 
@@ -735,14 +652,10 @@ def _paths(files):
 def load_sketches(files, ksize=21, algo="histosketch", threads=0):
     """LoadHULKdata + FindSketch for every file, in native code on `threads` host threads (hulk_load_sketches; no GPU needed):
     -> (ordering, mins[n][S], weights[n][S], banner labels), ordering = the sorted paths.  Raises HulkError with the reference's text."""
-    import ctypes
     L = _lib.load()
     arr, n = _paths(files)
     h = ctypes.c_void_p()
-    err = ctypes.create_string_buffer(4096)
-    rc = L.hulk_load_sketches(arr, n, ksize, algo.encode(), threads, ctypes.byref(h), err, len(err))
-    if rc != 0:
-        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    _call_files(L.hulk_load_sketches, arr, n, ksize, algo.encode(), threads, ctypes.byref(h))
     try:
         cn, cs = ctypes.c_uint32(), ctypes.c_uint32()
         L.hulk_sketch_set_info(h, ctypes.byref(cn), ctypes.byref(cs))
@@ -763,26 +676,17 @@ def smash(sketch_dir, out_file, ksize=21, algo="histosketch", metric="jaccard", 
     Writes <out_file>.hulk-matrix.csv (and, banner_matrix, <out_file>.banner-matrix.csv: makeBannerMatrix, cmd/smash.go:229-261 —
     the reference iterates a Go map, here the sorted file order is used) and returns (ordering, distances).
     stages: a dict that receives the seconds of "load" (JSON + MD5 check), "matrix", "csv" and "kernel_ms"."""
-    import ctypes
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    if algo not in AVAIL_ALGORITHMS:
-        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    _check_metric(metric)
+    _check_algo(algo)
     files = collect_jsons(sketch_dir, recursive)
-    od = os.path.dirname(out_file)
-    if od and od != "." and not os.path.exists(od):
-        os.makedirs(od, mode=0o700)
+    _make_parent_dir(out_file)
     L = _lib.load()
     arr, n = _paths(files)
     n_unique = len(set(files))
     dist = np.zeros((n_unique, n_unique), dtype=np.float64)
     st = _lib.SmashStats()
-    err = ctypes.create_string_buffer(4096)
-    rc = L.hulk_smash_files(device, arr, n, ksize, algo.encode(), metric.encode(), threads, os.fsencode(out_file + ".hulk-matrix.csv"),
-                            os.fsencode(out_file + ".banner-matrix.csv") if banner_matrix else None, dist.ctypes.data,
-                            ctypes.byref(st), err, len(err))
-    if rc != 0:
-        raise HulkError(rc, err.value.decode("utf-8", "replace"))
+    _call_files(L.hulk_smash_files, device, arr, n, ksize, algo.encode(), metric.encode(), threads, os.fsencode(out_file + ".hulk-matrix.csv"),
+                os.fsencode(out_file + ".banner-matrix.csv") if banner_matrix else None, dist.ctypes.data, ctypes.byref(st))
     if stages is not None:
         stages.update(load=st.seconds_load, matrix=st.seconds_matrix, csv=st.seconds_csv, kernel_ms=st.kernel_ms)
     return sorted(set(files)), dist
@@ -797,10 +701,8 @@ def smash_python(sketch_dir, out_file, ksize=21, algo="histosketch", metric="jac
     sorted file order is used.  stages: a dict that receives the seconds of "load" (JSON + MD5 check), "matrix", "csv"."""
     import time
     t_start = time.perf_counter()
-    if metric not in AVAIL_METRICS:
-        raise HulkError(-30, f"supplied distance metric is not available: {metric}\nplease select one of the following: {AVAIL_METRICS}")
-    if algo not in AVAIL_ALGORITHMS:
-        raise HulkError(-30, f"supplied algorithm not available: {algo}\nplease select one of the following: {AVAIL_ALGORITHMS}")
+    _check_metric(metric)
+    _check_algo(algo)
     files = collect_jsons(sketch_dir, recursive)
     loaded = {}
     for f in files:
@@ -830,9 +732,7 @@ def smash_python(sketch_dir, out_file, ksize=21, algo="histosketch", metric="jac
     t_loaded = time.perf_counter()
     dist = distance_matrix(mins, weights, metric, device)
     t_matrix = time.perf_counter()
-    od = os.path.dirname(out_file)
-    if od and od != "." and not os.path.exists(od):
-        os.makedirs(od, mode=0o700)
+    _make_parent_dir(out_file)
     with open(out_file + ".hulk-matrix.csv", "w", encoding="utf-8", newline="") as fh:
         fh.write(",".join(go_csv_field(f) for f in ordering) + "\n")
         for row in dist:

@@ -311,6 +311,33 @@ inline int MetricCode(const std::string &metric) {
     throw Error(HULK_ERR_ARG, "supplied distance metric is not available: " + metric);
 }
 
+namespace detail {
+// the Sketch and SketchWeights of a collection as [N][S] arrays (one element more: never empty), S = the first sketch's SketchSize
+inline void Pack(const std::vector<HistoSketch> &sketches, std::vector<uint64_t> &mins, std::vector<double> &weights) {
+    const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
+    mins.assign((size_t)N * S + 1, 0);
+    weights.assign((size_t)N * S + 1, 0.0);
+    for (uint32_t i = 0; i < N; i++) {
+        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
+            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
+        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
+        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
+    }
+}
+// the C strings of the *_files entry points' paths
+inline std::vector<const char *> CPaths(const std::vector<std::string> &files) {
+    std::vector<const char *> ptr;
+    for (const auto &f : files) ptr.push_back(f.c_str());
+    return ptr;
+}
+// the order the library's loader gives the files (a path given twice counts once)
+inline std::vector<std::string> SortedUnique(std::vector<std::string> files) {
+    std::sort(files.begin(), files.end());
+    files.erase(std::unique(files.begin(), files.end()), files.end());
+    return files;
+}
+}  // namespace detail
+
 // sketchio's pairwise distances over loaded sketches (cmd/smash.go:183-226): distances[s*N+q]
 inline std::vector<double> Smash(const std::vector<HistoSketch> &sketches, const std::string &metric, int device = 0) {
     const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
@@ -385,8 +412,7 @@ public:
                             const std::string &algo = "histosketch", uint32_t threads = 0, int device = 0) {
         hulk_index_opts o = hulk_index_opts();
         o.max_distance = maxDistance; o.bands = bands;
-        std::vector<const char *> paths;
-        for (const std::string &f : files) paths.push_back(f.c_str());
+        const std::vector<const char *> paths = detail::CPaths(files);
         char err[4096] = "";
         hulk_index *h = nullptr;
         const int rc = hulk_index_build_files(device, paths.data(), (uint32_t)paths.size(), ksize, algo.c_str(), threads, &o, &h, err, sizeof err);
@@ -462,14 +488,9 @@ private:
 inline std::vector<uint32_t> Cluster(const std::vector<HistoSketch> &sketches, double maxDistance, const std::string &metric,
                                      uint32_t bandRows = 0, int device = 0, hulk_cluster_stats *stats = nullptr) {
     const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
-    std::vector<uint64_t> mins((size_t)N * S + 1);
-    std::vector<double> weights((size_t)N * S + 1);
-    for (uint32_t i = 0; i < N; i++) {
-        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
-            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
-        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
-        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
-    }
+    std::vector<uint64_t> mins;
+    std::vector<double> weights;
+    detail::Pack(sketches, mins, weights);
     hulk_cluster_opts o = hulk_cluster_opts();
     o.max_distance = maxDistance; o.band_rows = bandRows;
     o.metric = MetricCode(metric);
@@ -485,11 +506,8 @@ inline std::vector<uint32_t> Cluster(const std::vector<HistoSketch> &sketches, d
 inline std::vector<uint32_t> ClusterFiles(const std::vector<std::string> &jsonFiles, uint32_t kSize, const std::string &algo,
                                           const std::string &metric, double maxDistance, const std::string &clustersCSV = std::string(),
                                           hulk_cluster_stats *stats = nullptr, int device = 0, uint32_t threads = 0) {
-    std::vector<const char *> ptr;
-    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
-    std::vector<std::string> uniq(jsonFiles);
-    std::sort(uniq.begin(), uniq.end());
-    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    const std::vector<const char *> ptr = detail::CPaths(jsonFiles);
+    const std::vector<std::string> uniq = detail::SortedUnique(jsonFiles);
     std::vector<uint32_t> label(uniq.size() + 1);
     char err[4096] = {0};
     const int rc = hulk_cluster_files(device, ptr.data(), (uint32_t)ptr.size(), kSize, algo.c_str(), metric.c_str(), maxDistance, threads,
@@ -534,14 +552,9 @@ struct LinkList {
 inline LinkList Links(const std::vector<HistoSketch> &sketches, double maxDistance, const std::string &metric, bool upper = false,
                       uint64_t maxEdges = 0, uint32_t bandRows = 0, int device = 0, hulk_links_stats *stats = nullptr) {
     const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
-    std::vector<uint64_t> mins((size_t)N * S + 1);
-    std::vector<double> weights((size_t)N * S + 1);
-    for (uint32_t i = 0; i < N; i++) {
-        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
-            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
-        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
-        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
-    }
+    std::vector<uint64_t> mins;
+    std::vector<double> weights;
+    detail::Pack(sketches, mins, weights);
     hulk_links_opts o = hulk_links_opts();
     o.max_distance = maxDistance; o.band_rows = bandRows; o.flags = upper ? HULK_LINKS_UPPER : 0u; o.max_edges = maxEdges;
     o.metric = MetricCode(metric);
@@ -556,8 +569,7 @@ inline LinkList Links(const std::vector<HistoSketch> &sketches, double maxDistan
 inline LinkList LinksFiles(const std::vector<std::string> &jsonFiles, uint32_t kSize, const std::string &algo, const std::string &metric,
                            double maxDistance, bool upper = false, uint64_t maxEdges = 0, const std::string &linksCSV = std::string(),
                            hulk_links_stats *stats = nullptr, int device = 0, uint32_t threads = 0) {
-    std::vector<const char *> ptr;
-    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
+    const std::vector<const char *> ptr = detail::CPaths(jsonFiles);
     char err[4096] = {0};
     hulk_link_list *list = nullptr;
     const int rc = hulk_links_files(device, ptr.data(), (uint32_t)ptr.size(), kSize, algo.c_str(), metric.c_str(), maxDistance,
@@ -574,14 +586,9 @@ struct DendrogramEdge { uint32_t A = 0, B = 0; double Distance = 0; };
 inline std::vector<DendrogramEdge> Dendrogram(const std::vector<HistoSketch> &sketches, const std::string &metric, uint32_t bandRows = 0,
                                               int device = 0, hulk_dendrogram_stats *stats = nullptr) {
     const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
-    std::vector<uint64_t> mins((size_t)N * S + 1);
-    std::vector<double> weights((size_t)N * S + 1);
-    for (uint32_t i = 0; i < N; i++) {
-        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
-            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
-        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
-        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
-    }
+    std::vector<uint64_t> mins;
+    std::vector<double> weights;
+    detail::Pack(sketches, mins, weights);
     hulk_dendrogram_opts o = hulk_dendrogram_opts();
     o.band_rows = bandRows;
     o.metric = MetricCode(metric);
@@ -603,8 +610,7 @@ inline std::vector<DendrogramEdge> DendrogramFiles(const std::vector<std::string
                                                    double cutDistance = std::numeric_limits<double>::quiet_NaN(),
                                                    const std::string &clustersCSV = std::string(), hulk_dendrogram_stats *stats = nullptr,
                                                    int device = 0, uint32_t threads = 0) {
-    std::vector<const char *> ptr;
-    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
+    const std::vector<const char *> ptr = detail::CPaths(jsonFiles);
     const size_t n = jsonFiles.size() + 1;
     std::vector<uint32_t> a(n), b(n);
     std::vector<double> d(n);
@@ -632,14 +638,9 @@ inline int LinkageCode(const std::string &method) {
 inline std::vector<LinkageMerge> Linkage(const std::vector<HistoSketch> &sketches, const std::string &method, const std::string &metric,
                                          int device = 0, hulk_linkage_stats *stats = nullptr) {
     const uint32_t N = (uint32_t)sketches.size(), S = N ? sketches[0].SketchSize : 0;
-    std::vector<uint64_t> mins((size_t)N * S + 1);
-    std::vector<double> weights((size_t)N * S + 1);
-    for (uint32_t i = 0; i < N; i++) {
-        if (sketches[i].Sketch.size() != S || sketches[i].SketchWeights.size() != S)
-            throw Error(HULK_ERR_ARG, "sketch length mismatch: " + std::to_string(S) + " vs " + std::to_string(sketches[i].Sketch.size()) + "\n");
-        std::copy(sketches[i].Sketch.begin(), sketches[i].Sketch.end(), mins.begin() + i * (size_t)S);
-        std::copy(sketches[i].SketchWeights.begin(), sketches[i].SketchWeights.end(), weights.begin() + i * (size_t)S);
-    }
+    std::vector<uint64_t> mins;
+    std::vector<double> weights;
+    detail::Pack(sketches, mins, weights);
     hulk_linkage_opts o = hulk_linkage_opts();
     o.method = LinkageCode(method);
     o.metric = MetricCode(metric);
@@ -659,8 +660,7 @@ inline std::vector<LinkageMerge> LinkageFiles(const std::vector<std::string> &js
                                               double cutDistance = std::numeric_limits<double>::quiet_NaN(),
                                               const std::string &clustersCSV = std::string(), hulk_linkage_stats *stats = nullptr,
                                               int device = 0, uint32_t threads = 0) {
-    std::vector<const char *> ptr;
-    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
+    const std::vector<const char *> ptr = detail::CPaths(jsonFiles);
     const size_t n = jsonFiles.size() + 1;
     std::vector<uint32_t> a(n), b(n), s(n);
     std::vector<double> d(n);
@@ -682,11 +682,8 @@ struct SmashStats { double SecondsLoad = 0, SecondsMatrix = 0, SecondsCSV = 0, K
 inline std::vector<double> SmashFiles(const std::vector<std::string> &jsonFiles, uint32_t kSize, const std::string &algo,
                                       const std::string &metric, const std::string &matrixCSV, const std::string &bannerCSV = std::string(),
                                       SmashStats *stats = nullptr, int device = 0, uint32_t threads = 0) {
-    std::vector<const char *> ptr;
-    for (const auto &f : jsonFiles) ptr.push_back(f.c_str());
-    std::vector<std::string> uniq(jsonFiles);
-    std::sort(uniq.begin(), uniq.end());
-    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    const std::vector<const char *> ptr = detail::CPaths(jsonFiles);
+    const std::vector<std::string> uniq = detail::SortedUnique(jsonFiles);
     std::vector<double> out(uniq.size() * uniq.size());
     hulk_smash_stats st;
     char err[4096] = {0};
