@@ -9,7 +9,7 @@
 //                     below N is stored (the full square: the tile is symmetric, the matrix is written whole)
 //   k_bottomk_global  the obvious fallback, kept as the yardstick of tools/profile_bottomk.py: a thread a pair, bottomk_merge over the
 //                     prepared lists where they lie in global memory.  The profiling build runs it with HULK_BOTTOMK_GLOBAL
-// k_search_dist_bottomk, k_cluster_link_bottomk and k_dendro_offer_bottomk are the tile under those kernels' own epilogues, in their units.
+// k_search_dist, k_cluster_link, k_links_count, k_links_fill and k_dendro_offer run the tile as their BottomkSet instances, in their units.
 #include "../../include/hulk_hip.h"
 #include "hulk_device.h"
 #include "hulk_bottomk_tile.h"
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void k_bottomk_global(const BottomkSet set, ui
 
 }  // namespace
 
-// N sketches of d_mins [N][S] -> the prepared form in d_mT / d_wT (bottomk_view over smash_padded_n(N) rows).  S <= 4096: the caller checks
+// N sketches of d_mins [N][S] -> the prepared form in d_mT / d_wT (BottomkSet::view over smash_padded_n(N) rows).  S <= 4096: the caller checks
 hipError_t launch_bottomk_prep(hipStream_t s, const unsigned long long *d_mins, uint32_t N, uint32_t S, double *d_mT, double *d_wT) {
     if (N == 0 || S == 0 || S > BK_MAX_S) return N == 0 || S == 0 ? hipSuccess : hipErrorInvalidValue;
     const uint32_t rows = smash_padded_n(N);
@@ -104,7 +104,7 @@ hipError_t launch_bottomk_smash(hipStream_t s, const unsigned long long *d_mins,
     const uint32_t rows = smash_padded_n(N);
     hipError_t e = launch_bottomk_prep(s, d_mins, N, S, d_mT, d_wT);
     if (e != hipSuccess) return e;
-    const BottomkSet set = bottomk_view(d_mT, d_wT, rows, S);
+    const BottomkSet set = BottomkSet::view(d_mT, d_wT, rows, S);
     // experiment (tools/profile_bottomk.py, the profiling build only): 1 = the merge from global memory, 2 = the preparation alone
     const char *exp = HULK_EXP_ENV("HULK_BOTTOMK_GLOBAL");
     const int mode = exp ? atoi(exp) : 0;

@@ -1,14 +1,15 @@
 // hulk_bottomk_tile.h — the tile of the bottom-k metric (HULK_METRIC_BOTTOMK, include/hulk_hip.h): the multiset intersection of
 // KMVsketch.GetSimilarity (kmv.go:119-159) for 32 subject sketches against 64 other sketches.  It hands the calling thread cnt[4][4]
 // in pair_tile's thread-to-pair mapping (hulk_pairtile.h: 128 threads, thread t the subjects 4 * (t / 16) + i and the others
-// 4 * (t % 16) + j), so the epilogues of k_search_dist, k_cluster_link and k_dendro_offer run on it unchanged, with
-// pair_distance<0>: the distance is 1.0 - (double)cnt / (double)S, jaccard's expression over another count.
+// 4 * (t % 16) + j), so k_search_dist, k_cluster_link, k_links_count, k_links_fill and k_dendro_offer run it as BottomkSet::tile
+// under their one epilogue, with pair_distance<0>: the distance is 1.0 - (double)cnt / (double)S, jaccard's expression over another
+// count.
 //
 // Layout (k_bottomk_prep, hulk_bottomk.hip, once per set or strip).  SKETCH-major, run-length form (hulk_bottomk_merge.h): val[row][S]
 // the row's distinct values strictly ascending, mult[row][S] their multiplicities, len[row] how many there are (<= S; what lies
 // behind is never read).  Values are uint64 and are compared as such: 2^60 and 2^60 + 1 differ.  The arrays hold the padded
 // number of rows (smash_padded_n, a multiple of 64); a row behind the last sketch has len 0 and intersects nothing.  The three
-// arrays live in the two buffers of 8 * S * rows bytes the other metrics keep their slot-major doubles in: bottomk_view.
+// arrays live in the two buffers of 8 * S * rows bytes the other metrics keep their slot-major doubles in: BottomkSet::view.
 //
 // The tile.  96 lists of S = 512 values are 393 KB, the LDS holds 160 KiB: the lists go through it in WINDOWS between shared pivots,
 // which the count allows because it is additive over disjoint ranges of values.  Every list has a cursor, 0 at the start.  A round
@@ -46,15 +47,23 @@ namespace hulk {
 
 constexpr int BK_W = 32, BK_PITCH = BK_W + 1, BK_LISTS = PAIR_TS + PAIR_TQ;
 
-struct BottomkSet { const uint64_t *val; const uint32_t *mult; const uint32_t *len; };
+// a prepared set as the kernels take it, PairSet's counterpart (hulk_pairtile.h): tile() is bottomk_tile below and leaves acc / uni
+// as they are; METRIC 0, because pair_distance<0> is the distance and the count is symmetric as jaccard's is
+struct BottomkSet {
+    static constexpr int METRIC = 0;
+    const uint64_t *val; const uint32_t *mult; const uint32_t *len;
+    static __host__ __device__ BottomkSet view(const double *d_mT, const double *d_wT, uint32_t rows, uint32_t S);
+    __device__ __forceinline__ void tile(uint32_t a_first, const BottomkSet &other, uint32_t b_first, uint32_t S, double (&)[4][4],
+                                         double (&)[4], uint32_t (&cnt)[4][4]) const;
+};
 
 // the prepared form inside the two buffers of rows * S doubles each that the other metrics call mT and wT (rows = smash_padded_n(n)):
 // val fills the first, mult the first half of the second, len stands behind mult (4 * rows bytes of the other half: S >= 1)
 inline uint64_t *bottomk_val(double *d_mT) { return (uint64_t *)d_mT; }
 inline uint32_t *bottomk_mult(double *d_wT) { return (uint32_t *)d_wT; }
 inline uint32_t *bottomk_len(double *d_wT, uint32_t rows, uint32_t S) { return (uint32_t *)d_wT + (size_t)rows * S; }
-inline BottomkSet bottomk_view(double *d_mT, double *d_wT, uint32_t rows, uint32_t S) {
-    return BottomkSet{bottomk_val(d_mT), bottomk_mult(d_wT), bottomk_len(d_wT, rows, S)};
+inline __host__ __device__ BottomkSet BottomkSet::view(const double *d_mT, const double *d_wT, uint32_t rows, uint32_t S) {
+    return BottomkSet{(const uint64_t *)d_mT, (const uint32_t *)d_wT, (const uint32_t *)d_wT + (size_t)rows * S};
 }
 
 // Sets cnt of this thread's 4 x 4 pairs: rows a_first + 4 * (t / 16) + i of A against rows b_first + 4 * (t % 16) + j of B
@@ -133,6 +142,11 @@ __device__ __forceinline__ void bottomk_tile(const BottomkSet A, uint32_t a_firs
         __syncthreads();                                            // the windows and s_n are free
         if (!again) break;
     }
+}
+
+__device__ __forceinline__ void BottomkSet::tile(uint32_t a_first, const BottomkSet &other, uint32_t b_first, uint32_t S, double (&)[4][4],
+                                                 double (&)[4], uint32_t (&cnt)[4][4]) const {
+    bottomk_tile(*this, a_first, other, b_first, S, cnt);
 }
 
 }  // namespace hulk

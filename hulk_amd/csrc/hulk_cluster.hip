@@ -15,7 +15,8 @@
 //                     shared tile was measured to cost against a loop of the kernel's own: DESIGN 4d
 //                     jaccard: d(s, q) and d(q, s) are the same bits — tiles wholly below the diagonal are not launched or leave
 //                     at once, inside the others only s < q is taken and counts twice.  weighted jaccard: the full square, every
-//                     ordered pair once, as subject
+//                     ordered pair once, as subject.  One template over the set type (PairSet<0>, PairSet<1>, BottomkSet: symmetric,
+//                     taken as jaccard is)
 //   k_cluster_flatten parent[i] = root(i), once behind the last band: its output is `label`.  (Behind EVERY band it would keep the next
 //                     band's finds one step deep and show the filter whole components; measured, the link kernel is no faster
 //                     for it — path halving and hooking under the smaller root keep the trees shallow — and it costs a launch a
@@ -25,8 +26,6 @@
 // filter's plain loads may be stale too: parent[s] == parent[q] with either value old still says that both have that common ancestor.
 // What the labels need to be exact is the kernel boundary between the last k_cluster_link and the last k_cluster_flatten.
 #include "hulk_oneshot.h"
-#include "hulk_pairtile.h"
-#include "hulk_bottomk_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,21 +43,21 @@ constexpr uint32_t CLUSTER_MAX_BAND = 1u << 20;                     // (band_row
 constexpr uint32_t CLUSTER_MAX_N = HULK_CLUSTER_MAX_N;              // N rounded up to 64, over 32, is grid.y of k_smash_prep (at most 65,535)
 static_assert(CLUSTER_MAX_N % 64 == 0 && CLUSTER_MAX_N / 32 <= 65535, "k_smash_prep's grid");
 
-// mT / wT: the prepared set [S][NP].  Subjects b0 + 32 * blockIdx.y .. (below N), others 64 * (qt0 + blockIdx.x) .. (below N).
+// set: the prepared set (NP rows).  Subjects b0 + 32 * blockIdx.y .. (below N), others 64 * (qt0 + blockIdx.x) .. (below N).
 // filter: skip a pair whose two parents are equal already (plain loads; it pays where links are dense: DESIGN 4e).
-// links: the ordered pairs s != q with d(s, q) <= tau
-// cluster_link_tile is the kernel's text around the tile: tile(s0, q0, acc, uni, cnt) fills the sums of the tile at rows s0, columns q0
-template <int METRIC, class TILE>
-__device__ __forceinline__ void cluster_link_tile(uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t filter,
-                                                  uint32_t *parent, unsigned long long *links, uint32_t *err, TILE tile) {
+// links: the ordered pairs s != q with d(s, q) <= tau.  METRIC 0 (jaccard, bottomk) is symmetric: the triangle, a link counts twice
+// cluster_link is the kernel's text, a function under k_cluster_link: as the kernel's own body hipcc compiles it to other code (k_dendro_offer, hulk_dendrogram.hip)
+template <class SET>
+__device__ __forceinline__ void cluster_link(const SET set, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t filter,
+                                             uint32_t *parent, unsigned long long *links, uint32_t *err) {
     const uint32_t s0 = b0 + blockIdx.y * PAIR_TS, q0 = (qt0 + blockIdx.x) * PAIR_TQ;
-    if (METRIC == 0 && s0 >= q0 + PAIR_TQ - 1) return;              // jaccard: every pair of the tile has s >= q (the whole workgroup leaves)
+    if (SET::METRIC == 0 && s0 >= q0 + PAIR_TQ - 1) return;         // jaccard: every pair of the tile has s >= q (the whole workgroup leaves)
     __shared__ uint32_t wg_links;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;     // other quad, subject quad inside the tile
     if (tid == 0) wg_links = 0;                                     // (ordered before its use by the tile's barriers)
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    tile(s0, q0, acc, uni, cnt);
+    set.tile(s0, set, q0, S, acc, uni, cnt);
     // the epilogue.  First the 16 compares into one word — the accumulators are dead behind it, the unions run on a handful of registers
     uint32_t mask = 0;
 #pragma unroll
@@ -67,12 +66,12 @@ __device__ __forceinline__ void cluster_link_tile(uint32_t N, uint32_t b0, uint3
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t q = q0 + 4 * tx + j;
-            const double d = pair_distance<METRIC>(acc[i][j], uni[i], cnt[i][j], S);
-            const bool pair = METRIC == 1 ? s != q : s < q;         // (jaccard: (q, s) is this pair again, bit for bit)
+            const double d = pair_distance<SET::METRIC>(acc[i][j], uni[i], cnt[i][j], S);
+            const bool pair = SET::METRIC == 1 ? s != q : s < q;    // (jaccard: (q, s) is this pair again, bit for bit)
             if (s < N && q < N && pair && d <= tau) mask |= 1u << (4 * i + j);         // (a NaN compares false)
         }
     }
-    uint32_t mine = (uint32_t)__popc(mask) * (METRIC == 1 ? 1u : 2u);
+    uint32_t mine = (uint32_t)__popc(mask) * (SET::METRIC == 1 ? 1u : 2u);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
     if ((tid & 63) == 0 && mine) atomicAdd(&wg_links, mine);        // (at most 2 x 2048 a workgroup)
@@ -87,23 +86,12 @@ __device__ __forceinline__ void cluster_link_tile(uint32_t N, uint32_t b0, uint3
     if (tid == 0 && wg_links) atomicAdd(links, (unsigned long long)wg_links);
 }
 
-template <int METRIC>
+// (mT, wT, NP and not the set: k_dendro_offer, hulk_dendrogram.hip)
+template <class SET>
 __global__ __launch_bounds__(128) void k_cluster_link(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t N,
                                                       uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t filter,
                                                       uint32_t *parent, unsigned long long *links, uint32_t *err) {
-    cluster_link_tile<METRIC>(N, b0, qt0, S, tau, filter, parent, links, err,
-                              [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
-        pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
-    });
-}
-
-// HULK_METRIC_BOTTOMK: the same text over bottomk_tile's count (hulk_bottomk_tile.h), symmetric as jaccard is — the triangle, a link counts twice
-__global__ __launch_bounds__(128) void k_cluster_link_bottomk(const BottomkSet set, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau,
-                                                              uint32_t filter, uint32_t *parent, unsigned long long *links, uint32_t *err) {
-    cluster_link_tile<0>(N, b0, qt0, S, tau, filter, parent, links, err,
-                         [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
-        bottomk_tile(set, s0, set, q0, S, cnt);
-    });
+    cluster_link(SET::view(mT, wT, NP, S), N, b0, qt0, S, tau, filter, parent, links, err);
 }
 
 // parent[i] = root(i).  No hook runs beside this kernel, so the roots stand still and every store writes the value the node ends with
@@ -128,17 +116,10 @@ using namespace hulk;
 extern "C" int hulk_cluster(int device, const uint64_t *mins, const double *weights, uint32_t n, uint32_t sketch_size,
                             const hulk_cluster_opts *opts, uint32_t *label, hulk_cluster_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
-    // (HULK_METRIC_BOTTOMK reads no weights: they may be NULL)
-    const bool bottomk = opts && opts->metric == HULK_METRIC_BOTTOMK;
-    if (!mins || (!weights && !bottomk) || !opts || !label) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: NULL");
-    if (n == 0 || sketch_size == 0) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: n and sketch_size must be positive");
-    if (n > CLUSTER_MAX_N) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: n must be at most " + std::to_string(CLUSTER_MAX_N));
-    if (!pair_metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: metric");
-    if (!bottomk_size_ok(opts->metric, sketch_size)) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
+    if (const int rc = collection_args("hulk_cluster", mins, weights, opts, label != nullptr, n, sketch_size, CLUSTER_MAX_N)) return rc;
     if (!(opts->max_distance >= 0.0 && opts->max_distance <= 1.0)) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: max_distance must be in [0, 1]");
     if (opts->band_rows % 32) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: band_rows must be a multiple of 32");
-    if (opts->flags) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: unknown flags");
-    for (uint64_t x : opts->reserved) if (x) return fail(nullptr, HULK_ERR_ARG, "hulk_cluster: reserved fields must be zero");
+    if (const int rc = collection_flags("hulk_cluster", opts, 0)) return rc;
     const double t0 = now_s();
     if (const int rc = oneshot_device(device)) return rc;
     const uint32_t N = n, S = sketch_size, NP = smash_padded_n(N), band = opts->band_rows ? std::min(opts->band_rows, CLUSTER_MAX_BAND) : CLUSTER_DEFAULT_BAND;
@@ -147,19 +128,13 @@ extern "C" int hulk_cluster(int device, const uint64_t *mins, const double *weig
     // experiments (tools/cluster_cost.py, the profiling build only): what the filter and a flatten behind every band are worth
     const uint32_t filter = HULK_EXP_ENV("HULK_CLUSTER_NO_FILTER") ? 0u : 1u;
     const bool band_flatten = HULK_EXP_ENV("HULK_CLUSTER_BAND_FLATTEN") != nullptr;
-    const size_t NS = (size_t)N * S, NT = (size_t)NP * S;
     OneShot own;                                                    // events per band: before the link kernel, behind it, behind the flatten (if one ran)
-    unsigned long long *d_raw_m = nullptr, *d_links = nullptr; double *d_raw_w = nullptr, *d_mT = nullptr, *d_wT = nullptr;
+    unsigned long long *d_links = nullptr; double *d_mT = nullptr, *d_wT = nullptr;
     uint32_t *d_parent = nullptr, *d_err = nullptr;
-    ONESHOT_CHK(own.alloc(&d_mT, NT)); ONESHOT_CHK(own.alloc(&d_wT, NT));
-    ONESHOT_CHK(own.alloc(&d_raw_m, NS)); ONESHOT_CHK(own.alloc(&d_raw_w, NS));
     ONESHOT_CHK(own.alloc(&d_parent, N)); ONESHOT_CHK(own.alloc(&d_links, 1)); ONESHOT_CHK(own.alloc(&d_err, 1));
-    // bottomk: the same buffers hold the sorted run-length form (bottomk_view)
-    if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, mins, N, S, d_raw_m, d_mT, d_wT));
-    else ONESHOT_CHK(upload_prepared(nullptr, mins, weights, N, S, d_raw_m, d_raw_w, d_mT, d_wT));
-    ONESHOT_CHK(hipDeviceSynchronize());
-    ONESHOT_CHK(own.release(d_raw_m));                              // (the peak of device memory: the header comment)
-    ONESHOT_CHK(own.release(d_raw_w));
+    // (the peak of device memory: the header comment — these three and the set with its staging, whichever is allocated first.
+    // bottomk: the same buffers hold the sorted run-length form, BottomkSet::view)
+    if (const int rc = prepare_set(own, metric, mins, weights, N, S, d_mT, d_wT)) return rc;
     {   // the identity (label doubles as the host staging)
         for (uint32_t i = 0; i < N; i++) label[i] = i;
         ONESHOT_CHK(hipMemcpy(d_parent, label, (size_t)N * 4, hipMemcpyHostToDevice));
@@ -183,12 +158,9 @@ extern "C" int hulk_cluster(int device, const uint64_t *mins, const double *weig
         const dim3 g(NP / PAIR_TQ - qt0, (rows + PAIR_TS - 1) / PAIR_TS);
         const bool last = b0 + band >= N;
         ONESHOT_CHK(mark());
-        if (bottomk)
-            hipLaunchKernelGGL(k_cluster_link_bottomk, g, dim3(128), 0, nullptr, bottomk_view(d_mT, d_wT, NP, S), N, (uint32_t)b0, qt0, S, tau, filter, d_parent, d_links, d_err);
-        else if (metric == HULK_METRIC_WEIGHTED_JACCARD)
-            hipLaunchKernelGGL(k_cluster_link<1>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, filter, d_parent, d_links, d_err);
-        else
-            hipLaunchKernelGGL(k_cluster_link<0>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, filter, d_parent, d_links, d_err);
+        with_set(metric, d_mT, d_wT, NP, S, [&](auto set) {
+            hipLaunchKernelGGL(k_cluster_link<decltype(set)>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, filter, d_parent, d_links, d_err);
+        });
         ONESHOT_CHK(hipGetLastError());
         ONESHOT_CHK(mark());
         flattened.push_back(band_flatten || last);

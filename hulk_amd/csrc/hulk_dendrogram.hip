@@ -8,7 +8,7 @@
 //                     preparation, so the PEAK of device memory is 32 * S * N bytes, or the resident set plus the scratch below,
 //                     whichever is larger.  The limit on N is hulk_cluster's (HULK_CLUSTER_MAX_N)
 //   comp[NP]          uint32, the identity at the start: the smallest member of a sketch's component, uploaded before every round
-//   k_dendro_offer    pair_tile over one set with k_cluster_link's index arithmetic (jaccard: the tiles on and above the diagonal,
+//   k_dendro_offer    SET::tile over one set with k_cluster_link's index arithmetic (jaccard, bottomk: the tiles on and above the diagonal,
 //                     inside them s < q; weighted jaccard: the full square, s != q), once per band of band_rows subject rows.  The
 //                     epilogue forms d with pair_distance; a pair inside the set, of two components, whose d is not NaN OFFERS
 //                     (d, q) to s and (d, s) to q.  A sketch's best offer is the lexicographic minimum of (d bits, partner).  The
@@ -26,8 +26,6 @@
 //                     uploads comp (4 * N bytes); stops when one component is left or a round delivered no offer
 // The output does not depend on bands, launch shape or the number of rounds: every minimum is over a total order.
 #include "hulk_oneshot.h"
-#include "hulk_pairtile.h"
-#include "hulk_bottomk_tile.h"
 #include "hulk_boruvka.h"
 
 #include <algorithm>
@@ -48,17 +46,19 @@ __device__ __forceinline__ void offer_min(uint64_t &d, uint32_t &p, uint64_t od,
     p = take ? op : p;
 }
 
-// mT / wT: the prepared set [S][NP].  Subjects b0 + 32 * blockIdx.y .., others 64 * (qt0 + blockIdx.x) ..; CT = NP / 64, RT = the
-// pitch of the column scratch (the band's planned row tiles).  Every launched workgroup writes its 32 row and 64 column entries
-// dendro_offer_tile is the kernel's text around the tile: tile(s0, q0, acc, uni, cnt) fills the sums of the tile at rows s0, columns q0
-template <int METRIC, class TILE>
-__device__ __forceinline__ void dendro_offer_tile(uint32_t NP, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, const uint32_t *__restrict__ comp,
-                                                  uint32_t RT, uint64_t *__restrict__ row_d, uint32_t *__restrict__ row_p,
-                                                  uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p, TILE tile) {
+// set: the prepared set [NP rows] (mT / wT: its two buffers, SET::view).  Subjects b0 + 32 * blockIdx.y .., others 64 * (qt0 + blockIdx.x) ..; CT = NP / 64, RT = the
+// pitch of the column scratch (the band's planned row tiles).  Every launched workgroup writes its 32 row and 64 column entries.
+// METRIC 0 (jaccard, bottomk) is symmetric: the tiles on and above the diagonal.
+// dendro_offer is the kernel's text.  It stays a function under k_dendro_offer because hipcc compiles it differently as the kernel's
+// own body: the epilogue's selects become branches, 7 % more instructions
+template <class SET>
+__device__ __forceinline__ void dendro_offer(const SET set, uint32_t NP, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S,
+                                             const uint32_t *__restrict__ comp, uint32_t RT, uint64_t *__restrict__ row_d,
+                                             uint32_t *__restrict__ row_p, uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p) {
     const uint32_t ct = qt0 + blockIdx.x, CT = NP / PAIR_TQ;
     const uint32_t s0 = b0 + blockIdx.y * PAIR_TS, q0 = ct * PAIR_TQ;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;     // other quad, subject quad inside the tile
-    if (METRIC == 0 && s0 >= q0 + PAIR_TQ - 1) {                    // jaccard: every pair of the tile has s >= q — nothing to offer
+    if (SET::METRIC == 0 && s0 >= q0 + PAIR_TQ - 1) {               // jaccard: every pair of the tile has s >= q — nothing to offer
         if (tid < PAIR_TS) {
             const size_t at = (size_t)(s0 - b0 + (uint32_t)tid) * CT + ct;
             row_d[at] = BORUVKA_NONE; row_p[at] = NO_PARTNER;
@@ -72,7 +72,7 @@ __device__ __forceinline__ void dendro_offer_tile(uint32_t NP, uint32_t N, uint3
     __shared__ uint32_t x_p[PAIR_TQ];
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    tile(s0, q0, acc, uni, cnt);
+    set.tile(s0, set, q0, S, acc, uni, cnt);
     // the epilogue: the accumulators die pair by pair into 4 row and 4 column minima
     uint32_t cs[4], cq[4];
 #pragma unroll
@@ -87,8 +87,8 @@ __device__ __forceinline__ void dendro_offer_tile(uint32_t NP, uint32_t N, uint3
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t q = q0 + 4 * tx + j;
-            const double d = pair_distance<METRIC>(acc[i][j], uni[i], cnt[i][j], S);
-            const bool pair = METRIC == 1 ? s != q : s < q;         // (jaccard: (q, s) is this pair again, bit for bit)
+            const double d = pair_distance<SET::METRIC>(acc[i][j], uni[i], cnt[i][j], S);
+            const bool pair = SET::METRIC == 1 ? s != q : s < q;    // (jaccard: (q, s) is this pair again, bit for bit)
             const bool ok = s < N && q < N && pair && cs[i] != cq[j] && d == d;
             const uint64_t bits = ok ? (uint64_t)__double_as_longlong(d) : BORUVKA_NONE;
             // q ascends with j and s with i: a strict compare keeps the smaller partner at equal d ("no offer" is never below)
@@ -140,25 +140,14 @@ __device__ __forceinline__ void dendro_offer_tile(uint32_t NP, uint32_t N, uint3
     }
 }
 
-template <int METRIC>
+// The kernel takes mT, wT and the pitch as the dense kernels always did and builds the set here: passed as a struct the argument
+// loads split and the weighted kernels measured 1 - 3.5 % slower (profiles/pairset.txt)
+template <class SET>
 __global__ __launch_bounds__(128) void k_dendro_offer(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t N,
-                                                      uint32_t b0, uint32_t qt0, uint32_t S, const uint32_t *__restrict__ comp, uint32_t RT,
-                                                      uint64_t *__restrict__ row_d, uint32_t *__restrict__ row_p,
-                                                      uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p) {
-    dendro_offer_tile<METRIC>(NP, N, b0, qt0, S, comp, RT, row_d, row_p, col_d, col_p,
-                              [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
-        pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
-    });
-}
-
-// HULK_METRIC_BOTTOMK: the same text over bottomk_tile's count (hulk_bottomk_tile.h), symmetric as jaccard is — the tiles on and above the diagonal
-__global__ __launch_bounds__(128) void k_dendro_offer_bottomk(const BottomkSet set, uint32_t NP, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S,
-                                                              const uint32_t *__restrict__ comp, uint32_t RT, uint64_t *__restrict__ row_d,
-                                                              uint32_t *__restrict__ row_p, uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p) {
-    dendro_offer_tile<0>(NP, N, b0, qt0, S, comp, RT, row_d, row_p, col_d, col_p,
-                         [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
-        bottomk_tile(set, s0, set, q0, S, cnt);
-    });
+                                                      uint32_t b0, uint32_t qt0, uint32_t S,
+                                                      const uint32_t *__restrict__ comp, uint32_t RT, uint64_t *__restrict__ row_d,
+                                                      uint32_t *__restrict__ row_p, uint64_t *__restrict__ col_d, uint32_t *__restrict__ col_p) {
+    dendro_offer(SET::view(mT, wT, NP, S), NP, N, b0, qt0, S, comp, RT, row_d, row_p, col_d, col_p);
 }
 
 // one wave a sketch: best[i] = min(best[i] (fresh: no offer), the band's row partials of i (if the band holds row i: the column tiles
@@ -193,16 +182,10 @@ extern "C" int hulk_dendrogram(int device, const uint64_t *mins, const double *w
                                uint32_t *n_edges, hulk_dendrogram_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_edges) *n_edges = 0;
-    // (HULK_METRIC_BOTTOMK reads no weights: they may be NULL)
-    const bool bottomk = opts && opts->metric == HULK_METRIC_BOTTOMK;
-    if (!mins || (!weights && !bottomk) || !opts || !edge_a || !edge_b || !edge_distance || !n_edges) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: NULL");
-    if (n == 0 || sketch_size == 0) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: n and sketch_size must be positive");
-    if (n > DENDRO_MAX_N) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: n must be at most " + std::to_string(DENDRO_MAX_N));
-    if (!pair_metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: metric");
-    if (!bottomk_size_ok(opts->metric, sketch_size)) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
+    if (const int rc = collection_args("hulk_dendrogram", mins, weights, opts, edge_a && edge_b && edge_distance && n_edges, n, sketch_size, DENDRO_MAX_N))
+        return rc;
     if (opts->band_rows % 32) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: band_rows must be a multiple of 32");
-    if (opts->flags) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: unknown flags");
-    for (uint64_t x : opts->reserved) if (x) return fail(nullptr, HULK_ERR_ARG, "hulk_dendrogram: reserved fields must be zero");
+    if (const int rc = collection_flags("hulk_dendrogram", opts, 0)) return rc;
     const double t0 = now_s();
     if (const int rc = oneshot_device(device)) return rc;
     const uint32_t N = n, S = sketch_size, NP = smash_padded_n(N), CT = NP / PAIR_TQ;
@@ -217,19 +200,13 @@ extern "C" int hulk_dendrogram(int device, const uint64_t *mins, const double *w
     uint32_t rounds = 0;
     double ms_offer = 0.0, ms_fold = 0.0;
     if (N > 1) {
-        const size_t NS = (size_t)N * S, NT = (size_t)NP * S, n_row = (size_t)band_alloc * CT, n_col = (size_t)NP * RT;
+        const size_t n_row = (size_t)band_alloc * CT, n_col = (size_t)NP * RT;
         OneShot own;                                                // events per band: before the offer kernel, behind it, behind the fold
-        unsigned long long *d_raw_m = nullptr; double *d_raw_w = nullptr, *d_mT = nullptr, *d_wT = nullptr;
+        double *d_mT = nullptr, *d_wT = nullptr;
         uint32_t *d_comp = nullptr, *d_row_p = nullptr, *d_col_p = nullptr, *d_best_p = nullptr;
         uint64_t *d_row_d = nullptr, *d_col_d = nullptr, *d_best_d = nullptr;
-        ONESHOT_CHK(own.alloc(&d_mT, NT)); ONESHOT_CHK(own.alloc(&d_wT, NT));
-        ONESHOT_CHK(own.alloc(&d_raw_m, NS)); ONESHOT_CHK(own.alloc(&d_raw_w, NS));
-        // bottomk: the same buffers hold the sorted run-length form (bottomk_view)
-        if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, mins, N, S, d_raw_m, d_mT, d_wT));
-        else ONESHOT_CHK(upload_prepared(nullptr, mins, weights, N, S, d_raw_m, d_raw_w, d_mT, d_wT));
-        ONESHOT_CHK(hipDeviceSynchronize());
-        ONESHOT_CHK(own.release(d_raw_m));                          // (the peak of device memory: the header comment)
-        ONESHOT_CHK(own.release(d_raw_w));
+        // (the peak of device memory: the header comment.  bottomk: the same buffers hold the sorted run-length form, BottomkSet::view)
+        if (const int rc = prepare_set(own, metric, mins, weights, N, S, d_mT, d_wT)) return rc;
         ONESHOT_CHK(own.alloc(&d_comp, NP));
         ONESHOT_CHK(own.alloc(&d_row_d, n_row)); ONESHOT_CHK(own.alloc(&d_row_p, n_row));
         ONESHOT_CHK(own.alloc(&d_col_d, n_col)); ONESHOT_CHK(own.alloc(&d_col_p, n_col));
@@ -250,12 +227,9 @@ extern "C" int hulk_dendrogram(int device, const uint64_t *mins, const double *w
                 const uint32_t qt0 = metric == HULK_METRIC_WEIGHTED_JACCARD ? 0u : (uint32_t)b0 / PAIR_TQ;
                 const dim3 g(CT - qt0, rt);
                 ONESHOT_CHK(hipEventRecord(ev[3 * b], nullptr));
-                if (bottomk)
-                    hipLaunchKernelGGL(k_dendro_offer_bottomk, g, dim3(128), 0, nullptr, bottomk_view(d_mT, d_wT, NP, S), NP, N, (uint32_t)b0, qt0, S, d_comp, RT, d_row_d, d_row_p, d_col_d, d_col_p);
-                else if (metric == HULK_METRIC_WEIGHTED_JACCARD)
-                    hipLaunchKernelGGL(k_dendro_offer<1>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, d_comp, RT, d_row_d, d_row_p, d_col_d, d_col_p);
-                else
-                    hipLaunchKernelGGL(k_dendro_offer<0>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, d_comp, RT, d_row_d, d_row_p, d_col_d, d_col_p);
+                with_set(metric, d_mT, d_wT, NP, S, [&](auto set) {
+                    hipLaunchKernelGGL(k_dendro_offer<decltype(set)>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, d_comp, RT, d_row_d, d_row_p, d_col_d, d_col_p);
+                });
                 ONESHOT_CHK(hipGetLastError());
                 ONESHOT_CHK(hipEventRecord(ev[3 * b + 1], nullptr));
                 hipLaunchKernelGGL(k_dendro_fold, fg, dim3(256), 0, nullptr, N, NP, (uint32_t)b0, rows, qt0, RT, rt, b0 == 0 ? 1u : 0u,

@@ -209,7 +209,7 @@ hipError_t launch_smash(hipStream_t s, const unsigned long long *d_mins, const d
                         int metric, double *d_out, double *d_mT, double *d_wT);     // d_mT, d_wT: scratch [S][smash_padded_n(N)]
 uint32_t smash_padded_n(uint32_t N);
 // HULK_METRIC_BOTTOMK (hulk_bottomk.hip): d_mins [N][S], S <= HULK_MINHASH_MAX_SKETCH, sorted and run-length coded on the device into
-// the two buffers of smash_padded_n(N) * S doubles the other metrics keep their slot-major arrays in (bottomk_view, hulk_bottomk_tile.h)
+// the two buffers of smash_padded_n(N) * S doubles the other metrics keep their slot-major arrays in (BottomkSet::view, hulk_bottomk_tile.h)
 hipError_t launch_bottomk_prep(hipStream_t s, const unsigned long long *d_mins, uint32_t N, uint32_t S, double *d_mT, double *d_wT);
 hipError_t launch_bottomk_smash(hipStream_t s, const unsigned long long *d_mins, uint32_t N, uint32_t S, double *d_out, double *d_mT,
                                 double *d_wT);

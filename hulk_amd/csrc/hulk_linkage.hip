@@ -201,21 +201,17 @@ extern "C" int hulk_linkage(int device, const uint64_t *mins, const double *weig
                             uint32_t *merge_size, uint32_t *n_merges, hulk_linkage_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_merges) *n_merges = 0;
-    const bool bottomk = opts && opts->metric == HULK_METRIC_BOTTOMK;   // (reads no weights: they may be NULL)
-    if (!mins || (!weights && !bottomk) || !opts || !merge_a || !merge_b || !merge_distance || !merge_size || !n_merges)
-        return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: NULL");
-    if (n == 0 || sketch_size == 0) return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: n and sketch_size must be positive");
-    if (n > LINK_MAX_N) return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: n must be at most " + std::to_string(LINK_MAX_N));
-    if (!pair_metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: metric");
-    if (!bottomk_size_ok(opts->metric, sketch_size)) return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
+    if (const int rc = collection_args("hulk_linkage", mins, weights, opts, merge_a && merge_b && merge_distance && merge_size && n_merges, n,
+                                       sketch_size, LINK_MAX_N))
+        return rc;
     if (opts->method != HULK_LINKAGE_SINGLE && opts->method != HULK_LINKAGE_COMPLETE && opts->method != HULK_LINKAGE_AVERAGE)
         return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: method");
-    if (opts->flags) return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: unknown flags");
-    for (uint64_t x : opts->reserved) if (x) return fail(nullptr, HULK_ERR_ARG, "hulk_linkage: reserved fields must be zero");
+    if (const int rc = collection_flags("hulk_linkage", opts, 0)) return rc;
     const double t0 = now_s();
     if (const int rc = oneshot_device(device)) return rc;
     const uint32_t N = n, S = sketch_size, NP = smash_padded_n(N);
     const int metric = opts->metric, method = opts->method;
+    const bool bottomk = metric == HULK_METRIC_BOTTOMK;             // (reads no weights: they may be NULL)
     uint32_t merges = 0;
     uint64_t rescans = 0;
     double ms_matrix = 0.0, ms_merge = 0.0;

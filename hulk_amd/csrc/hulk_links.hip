@@ -4,8 +4,8 @@
 //   the set           prepared once and resident exactly as in hulk_cluster (hulk_cluster.hip: the same buffers, the same peak of
 //                     32 * S * N bytes)
 // Per band of band_rows subject rows, with NT = NP / 64 column tiles:
-//   k_links_count     the pair tile (pair_tile / bottomk_tile, called the way k_cluster_link calls them) and an epilogue: the 16
-//                     compares of a thread as in cluster_link_tile, then the four nibbles of a row's 16 neighbouring lanes combined
+//   k_links_count     the pair tile (SET::tile, called the way k_cluster_link calls it) and an epilogue: the 16
+//                     compares of a thread as in k_cluster_link, then the four nibbles of a row's 16 neighbouring lanes combined
 //                     into the row's 64-bit mask by shuffles inside those lanes (no LDS, no atomics), one plain 8-byte store per
 //                     (row, tile), zeros included: mask[tile][row of the band] — the 32 rows of a workgroup are 256 contiguous bytes.
 //                     HULK_LINKS_UPPER: the tiles in front of the band's first row are not launched and never read, those below
@@ -30,8 +30,6 @@
 // Determinism: a mask bit is a function of the pair; the offsets are functions of the masks; the slot is a function of both.
 // Bands, tile shape, list order and scheduling cannot move an edge.
 #include "hulk_oneshot.h"
-#include "hulk_pairtile.h"
-#include "hulk_bottomk_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -58,9 +56,10 @@ constexpr int LINKS_SEGS = 16, LINKS_SCAN_THREADS = 1024;
 struct LinksHead { unsigned long long total; uint32_t tiles, max_degree; };
 
 // subjects b0 + 32 * blockIdx.y .., column tile qt0 + blockIdx.x; mask[tile * band + row of the band]
-template <int METRIC, class TILE>
-__device__ __forceinline__ void links_count_tile(uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t upper, uint32_t band,
-                                                 unsigned long long *mask_out, TILE tile) {
+// links_count is the kernel's text, a function under k_links_count: as the kernel's own body hipcc compiles it to other code (k_dendro_offer, hulk_dendrogram.hip)
+template <class SET>
+__device__ __forceinline__ void links_count(const SET set, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t upper,
+                                            uint32_t band, unsigned long long *mask_out) {
     const uint32_t t = qt0 + blockIdx.x, s0 = b0 + blockIdx.y * PAIR_TS, q0 = t * PAIR_TQ;
     unsigned long long *out = mask_out + (size_t)t * band + blockIdx.y * PAIR_TS;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;     // other quad, subject quad inside the tile
@@ -70,15 +69,15 @@ __device__ __forceinline__ void links_count_tile(uint32_t N, uint32_t b0, uint32
     }
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    tile(s0, q0, acc, uni, cnt);
-    uint32_t mask = 0;                                              // bit 4 * i + j, as in cluster_link_tile
+    set.tile(s0, set, q0, S, acc, uni, cnt);
+    uint32_t mask = 0;                                              // bit 4 * i + j, as in k_cluster_link
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t s = s0 + 4 * ty + i;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t q = q0 + 4 * tx + j;
-            const double d = pair_distance<METRIC>(acc[i][j], uni[i], cnt[i][j], S);
+            const double d = pair_distance<SET::METRIC>(acc[i][j], uni[i], cnt[i][j], S);
             const bool pair = upper ? s < q : s != q;
             if (s < N && q < N && pair && d <= tau) mask |= 1u << (4 * i + j);         // (a NaN compares false)
         }
@@ -95,22 +94,12 @@ __device__ __forceinline__ void links_count_tile(uint32_t N, uint32_t b0, uint32
     if (tx < 4) out[4 * ty + tx] = word;                            // lane k of the first quad: row 4 * ty + k
 }
 
-template <int METRIC>
+// (mT, wT, NP and not the set: k_dendro_offer, hulk_dendrogram.hip)
+template <class SET>
 __global__ __launch_bounds__(128) void k_links_count(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t N,
-                                                     uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t upper, uint32_t band,
-                                                     unsigned long long *mask_out) {
-    links_count_tile<METRIC>(N, b0, qt0, S, tau, upper, band, mask_out,
-                             [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
-        pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
-    });
-}
-
-__global__ __launch_bounds__(128) void k_links_count_bottomk(const BottomkSet set, uint32_t N, uint32_t b0, uint32_t qt0, uint32_t S, double tau,
-                                                             uint32_t upper, uint32_t band, unsigned long long *mask_out) {
-    links_count_tile<0>(N, b0, qt0, S, tau, upper, band, mask_out,
-                        [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
-        bottomk_tile(set, s0, set, q0, S, cnt);
-    });
+                                                     uint32_t b0, uint32_t qt0, uint32_t S, double tau, uint32_t upper,
+                                                     uint32_t band, unsigned long long *mask_out) {
+    links_count(SET::view(mT, wT, NP, S), N, b0, qt0, S, tau, upper, band, mask_out);
 }
 
 // rows32: the band's rows rounded up to 32 (the rows k_links_count stored masks for); tiles qt0 .. NT - 1.
@@ -164,17 +153,17 @@ __global__ __launch_bounds__(LINKS_SCAN_THREADS) void k_links_scan(const uint32_
 }
 
 // workgroup e fills the tile list[e] = (32-row block of the band) << 32 | column tile
-template <int METRIC, class TILE>
-__device__ __forceinline__ void links_fill_tile(uint32_t b0, uint32_t S, uint32_t band, const unsigned long long *__restrict__ list,
-                                                const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ offset,
-                                                const unsigned long long *__restrict__ row_start, uint32_t *__restrict__ col, double *__restrict__ dist,
-                                                TILE tile) {
+// (links_fill: a function under its kernel as links_count is)
+template <class SET>
+__device__ __forceinline__ void links_fill(const SET set, uint32_t b0, uint32_t S, uint32_t band, const unsigned long long *__restrict__ list,
+                                           const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ offset,
+                                           const unsigned long long *__restrict__ row_start, uint32_t *__restrict__ col, double *__restrict__ dist) {
     const unsigned long long entry = list[blockIdx.x];
     const uint32_t by = (uint32_t)(entry >> 32), t = (uint32_t)entry, s0 = b0 + by * PAIR_TS, q0 = t * PAIR_TQ;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    tile(s0, q0, acc, uni, cnt);
+    set.tile(s0, set, q0, S, acc, uni, cnt);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t r = by * PAIR_TS + 4 * ty + i;
@@ -188,30 +177,17 @@ __device__ __forceinline__ void links_fill_tile(uint32_t b0, uint32_t S, uint32_
             if (!((m >> bit) & 1ull)) continue;
             const unsigned long long slot = links_slot(start, off, m, bit);
             col[slot] = q0 + bit;
-            dist[slot] = pair_distance<METRIC>(acc[i][j], uni[i], cnt[i][j], S);
+            dist[slot] = pair_distance<SET::METRIC>(acc[i][j], uni[i], cnt[i][j], S);
         }
     }
 }
 
-template <int METRIC>
-__global__ __launch_bounds__(128) void k_links_fill(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t b0, uint32_t S,
-                                                    uint32_t band, const unsigned long long *__restrict__ list, const unsigned long long *__restrict__ mask,
-                                                    const uint32_t *__restrict__ offset, const unsigned long long *__restrict__ row_start,
-                                                    uint32_t *__restrict__ col, double *__restrict__ dist) {
-    links_fill_tile<METRIC>(b0, S, band, list, mask, offset, row_start, col, dist,
-                            [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
-        pair_tile<METRIC>(mT, wT, NP, s0, mT, NP, q0, S, acc, uni, cnt);
-    });
-}
-
-__global__ __launch_bounds__(128) void k_links_fill_bottomk(const BottomkSet set, uint32_t b0, uint32_t S, uint32_t band,
-                                                            const unsigned long long *__restrict__ list, const unsigned long long *__restrict__ mask,
-                                                            const uint32_t *__restrict__ offset, const unsigned long long *__restrict__ row_start,
-                                                            uint32_t *__restrict__ col, double *__restrict__ dist) {
-    links_fill_tile<0>(b0, S, band, list, mask, offset, row_start, col, dist,
-                       [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
-        bottomk_tile(set, s0, set, q0, S, cnt);
-    });
+template <class SET>
+__global__ __launch_bounds__(128) void k_links_fill(const double *__restrict__ mT, const double *__restrict__ wT, uint32_t NP, uint32_t b0,
+                                                    uint32_t S, uint32_t band, const unsigned long long *__restrict__ list,
+                                                    const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ offset,
+                                                    const unsigned long long *__restrict__ row_start, uint32_t *__restrict__ col, double *__restrict__ dist) {
+    links_fill(SET::view(mT, wT, NP, S), b0, S, band, list, mask, offset, row_start, col, dist);
 }
 
 }  // namespace
@@ -223,16 +199,10 @@ extern "C" int hulk_links(int device, const uint64_t *mins, const double *weight
                           const hulk_links_opts *opts, hulk_link_list **out, hulk_links_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (out) *out = nullptr;
-    const bool bottomk = opts && opts->metric == HULK_METRIC_BOTTOMK;   // (reads no weights: they may be NULL)
-    if (!mins || (!weights && !bottomk) || !opts || !out) return fail(nullptr, HULK_ERR_ARG, "hulk_links: NULL");
-    if (n == 0 || sketch_size == 0) return fail(nullptr, HULK_ERR_ARG, "hulk_links: n and sketch_size must be positive");
-    if (n > LINKS_MAX_N) return fail(nullptr, HULK_ERR_ARG, "hulk_links: n must be at most " + std::to_string(LINKS_MAX_N));
-    if (!pair_metric_ok(opts->metric)) return fail(nullptr, HULK_ERR_ARG, "hulk_links: metric");
-    if (!bottomk_size_ok(opts->metric, sketch_size)) return fail(nullptr, HULK_ERR_ARG, "hulk_links: bottomk takes a sketch_size of at most " + std::to_string(HULK_MINHASH_MAX_SKETCH));
+    if (const int rc = collection_args("hulk_links", mins, weights, opts, out != nullptr, n, sketch_size, LINKS_MAX_N)) return rc;
     if (!(opts->max_distance >= 0.0 && opts->max_distance <= 1.0)) return fail(nullptr, HULK_ERR_ARG, "hulk_links: max_distance must be in [0, 1]");
     if (opts->band_rows % 32) return fail(nullptr, HULK_ERR_ARG, "hulk_links: band_rows must be a multiple of 32");
-    if (opts->flags & ~HULK_LINKS_UPPER) return fail(nullptr, HULK_ERR_ARG, "hulk_links: unknown flags");
-    for (uint64_t x : opts->reserved) if (x) return fail(nullptr, HULK_ERR_ARG, "hulk_links: reserved fields must be zero");
+    if (const int rc = collection_flags("hulk_links", opts, HULK_LINKS_UPPER)) return rc;
     const double t0 = now_s();
     if (const int rc = oneshot_device(device)) return rc;
     const uint32_t N = n, S = sketch_size, NP = smash_padded_n(N), NT = NP / PAIR_TQ;
@@ -240,16 +210,9 @@ extern "C" int hulk_links(int device, const uint64_t *mins, const double *weight
     const double tau = opts->max_distance;
     const uint32_t upper = (opts->flags & HULK_LINKS_UPPER) ? 1u : 0u;
     const uint64_t cap = opts->max_edges;
-    const size_t NS = (size_t)N * S, NPS = (size_t)NP * S;
     OneShot own;
-    unsigned long long *d_raw_m = nullptr; double *d_raw_w = nullptr, *d_mT = nullptr, *d_wT = nullptr;
-    ONESHOT_CHK(own.alloc(&d_mT, NPS)); ONESHOT_CHK(own.alloc(&d_wT, NPS));
-    ONESHOT_CHK(own.alloc(&d_raw_m, NS)); ONESHOT_CHK(own.alloc(&d_raw_w, NS));
-    if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, mins, N, S, d_raw_m, d_mT, d_wT));
-    else ONESHOT_CHK(upload_prepared(nullptr, mins, weights, N, S, d_raw_m, d_raw_w, d_mT, d_wT));
-    ONESHOT_CHK(hipDeviceSynchronize());
-    ONESHOT_CHK(own.release(d_raw_m));                              // (the peak of device memory: hulk_cluster.hip's header comment)
-    ONESHOT_CHK(own.release(d_raw_w));
+    double *d_mT = nullptr, *d_wT = nullptr;
+    if (const int rc = prepare_set(own, metric, mins, weights, N, S, d_mT, d_wT)) return rc;      // (the peak: hulk_cluster.hip's header comment)
     // the band: the caller's, capped as in hulk_cluster, no longer than the set, and short enough for its tables (the header comment)
     uint32_t band = opts->band_rows ? std::min(opts->band_rows, LINKS_MAX_BAND) : LINKS_DEFAULT_BAND;
     band = std::min(band, (N + 31) / 32 * 32);
@@ -285,12 +248,9 @@ extern "C" int hulk_links(int device, const uint64_t *mins, const double *weight
             const dim3 g(NT - qt0, rows32 / PAIR_TS);
             ONESHOT_CHK(hipMemsetAsync(d_head, 0, sizeof(LinksHead), nullptr));
             ONESHOT_CHK(hipEventRecord(ev[0], nullptr));
-            if (bottomk)
-                hipLaunchKernelGGL(k_links_count_bottomk, g, dim3(128), 0, nullptr, bottomk_view(d_mT, d_wT, NP, S), N, (uint32_t)b0, qt0, S, tau, upper, band, d_mask);
-            else if (metric == HULK_METRIC_WEIGHTED_JACCARD)
-                hipLaunchKernelGGL(k_links_count<1>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, upper, band, d_mask);
-            else
-                hipLaunchKernelGGL(k_links_count<0>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, upper, band, d_mask);
+            with_set(metric, d_mT, d_wT, NP, S, [&](auto set) {
+                hipLaunchKernelGGL(k_links_count<decltype(set)>, g, dim3(128), 0, nullptr, d_mT, d_wT, NP, N, (uint32_t)b0, qt0, S, tau, upper, band, d_mask);
+            });
             ONESHOT_CHK(hipGetLastError());
             ONESHOT_CHK(hipEventRecord(ev[1], nullptr));
             hipLaunchKernelGGL(k_links_rows, dim3((rows32 + 63) / 64), dim3(64, LINKS_SEGS), 0, nullptr, d_mask, band, rows32, qt0, NT, d_offset, d_degree, d_list, d_head);
@@ -319,12 +279,9 @@ extern "C" int hulk_links(int device, const uint64_t *mins, const double *weight
                 }
                 ONESHOT_CHK(hipEventRecord(ev[2], nullptr));
                 const dim3 fg(head.tiles);
-                if (bottomk)
-                    hipLaunchKernelGGL(k_links_fill_bottomk, fg, dim3(128), 0, nullptr, bottomk_view(d_mT, d_wT, NP, S), (uint32_t)b0, S, band, d_list, d_mask, d_offset, d_row_start, d_col, d_dist);
-                else if (metric == HULK_METRIC_WEIGHTED_JACCARD)
-                    hipLaunchKernelGGL(k_links_fill<1>, fg, dim3(128), 0, nullptr, d_mT, d_wT, NP, (uint32_t)b0, S, band, d_list, d_mask, d_offset, d_row_start, d_col, d_dist);
-                else
-                    hipLaunchKernelGGL(k_links_fill<0>, fg, dim3(128), 0, nullptr, d_mT, d_wT, NP, (uint32_t)b0, S, band, d_list, d_mask, d_offset, d_row_start, d_col, d_dist);
+                with_set(metric, d_mT, d_wT, NP, S, [&](auto set) {
+                    hipLaunchKernelGGL(k_links_fill<decltype(set)>, fg, dim3(128), 0, nullptr, d_mT, d_wT, NP, (uint32_t)b0, S, band, d_list, d_mask, d_offset, d_row_start, d_col, d_dist);
+                });
                 ONESHOT_CHK(hipGetLastError());
                 ONESHOT_CHK(hipEventRecord(ev[3], nullptr));
                 const size_t at = list->col.size();

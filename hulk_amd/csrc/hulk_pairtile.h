@@ -2,8 +2,10 @@
 // sketches against 64 other sketches, summed over the S slots in ascending order.  One text for
 //   k_search_dist   (hulk_search.hip)    a block of queries against a strip of the database, either side the subject
 //   k_cluster_link  (hulk_cluster.hip)   one set against itself in bands of subject rows; the distances go no further than a compare
+//   k_links_count, k_links_fill (hulk_links.hip) the same bands; the distances go into a mask, then into the edges
 //   k_dendro_offer  (hulk_dendrogram.hip) the same bands; the distances go into per-sketch minima
-// each of which is its index arithmetic, one call of pair_tile and its own epilogue over pair_distance.
+// each of which is a kernel template over the set type (PairSet below; BottomkSet, hulk_bottomk_tile.h, the bottom-k metric's):
+// its index arithmetic, one call of SET::tile and its own epilogue over pair_distance<SET::METRIC>.
 // k_smash (hulk_pairwise.hip: one set against itself, the whole N x N matrix) KEEPS A LOOP OF ITS OWN, the same text with `if`
 // for `if constexpr`: through pair_tile its weighted form ran 1.1 % slower on the MI355X than with its own loop (N = 8,192,
 // S = 512: 5.29e12 against 5.35e12 pair-slots/s, medians of six runs of nine each, the runs of either build within 0.7 % of
@@ -121,6 +123,20 @@ __device__ __forceinline__ void pair_tile(const double *__restrict__ aT, const d
         __syncthreads();
     }
 }
+
+// a prepared set [S][pitch] as the kernels see it (view(): from its two buffers, on the host or inside a kernel).  tile(): this set the subject side, `other` the other side (BottomkSet,
+// hulk_bottomk_tile.h, has the same two members); SET::METRIC is the pair_distance of the epilogue
+template <int M>
+struct PairSet {
+    static constexpr int METRIC = M;
+    const double *mT, *wT;
+    uint32_t pitch;
+    static __host__ __device__ PairSet view(const double *d_mT, const double *d_wT, uint32_t rows, uint32_t) { return PairSet{d_mT, d_wT, rows}; }
+    __device__ __forceinline__ void tile(uint32_t a_first, const PairSet &other, uint32_t b_first, uint32_t S, double (&acc)[4][4],
+                                         double (&uni)[4], uint32_t (&cnt)[4][4]) const {
+        pair_tile<M>(mT, wT, pitch, a_first, other.mT, other.pitch, b_first, S, acc, uni, cnt);
+    }
+};
 
 // the distance of one pair from the tile's sums: the expression every user stores or compares, so that a pair's distance is the
 // same bits in hulk_smash's matrix, in a search's list and against a clustering's threshold.  (Where the weighted quotient is

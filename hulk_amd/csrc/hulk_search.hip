@@ -9,7 +9,8 @@
 //                   accumulators a thread that add in slot order; layout and contract are written there) over two different sets.
 //                   The SUBJECT side supplies mins, |w| and the union, the other side mins only: ROLE row = the queries are the
 //                   subjects, ROLE column = the strip's sketches are (for jaccard the two are one kernel).  Tails in M, P and S
-//                   are zero rows / columns as in k_smash; nothing outside block x strip is written
+//                   are zero rows / columns as in k_smash; nothing outside block x strip is written.  One template over the set
+//                   type: PairSet<0>, PairSet<1> in both roles, BottomkSet (symmetric: ROLE row only)
 //   k_search_select a wave owns a query: lane l < K holds entry l of its list, sorted by the 96-bit key (distance bits, database
 //                   index) — a non-negative, non-NaN double orders like its uint64 bits.  It reads the strip's row 64 values at
 //                   a time (coalesced, eight such loads in flight), rejects against the K-th key (after the first strip nearly everything fails this one
@@ -29,44 +30,34 @@ namespace {
 
 constexpr int SELECT_AHEAD = 8;
 
-// a: the subject side, slot-major [S][AP], columns a0 .. a0 + na of it; b: the other side [S][BP], columns b0 .. b0 + nb.
+// a: the subject side, columns a0 .. a0 + na of it; b: the other side, columns b0 .. b0 + nb (PairSet: slot-major [S][pitch];
+// BottomkSet: rows of the prepared lists, symmetric, so the queries are always a and the rows of `out`).
 // out[q][p], pitch doubles per query row: COLUMN 0 the subjects are the queries (q = a, p = b), COLUMN 1 the others are.
 // Columns behind na / nb inside a tile are read (the arrays are padded: see hulk_search) and never written.
-// search_dist_tile is the kernel's text around the tile: tile(s0, q0, acc, uni, cnt) fills the sums of the workgroup's tile at (s0, q0)
-template <int METRIC, int COLUMN, class TILE>
-__device__ __forceinline__ void search_dist_tile(uint32_t na, uint32_t nb, uint32_t S, double *__restrict__ out, uint32_t pitch, TILE tile) {
+// search_dist is the kernel's text, a function under k_search_dist: as the kernel's own body hipcc compiles it to other code (k_dendro_offer, hulk_dendrogram.hip)
+template <class SET, int COLUMN>
+__device__ __forceinline__ void search_dist(const SET a, uint32_t a0, uint32_t na, const SET b, uint32_t b0, uint32_t nb, uint32_t S,
+                                            double *__restrict__ out, uint32_t pitch) {
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;     // other quad, subject quad inside the tile
     const uint32_t s0 = blockIdx.y * PAIR_TS, q0 = blockIdx.x * PAIR_TQ;        // tile origin, relative to a0 / b0
     double acc[4][4], uni[4];
     uint32_t cnt[4][4];
-    tile(s0, q0, acc, uni, cnt);
+    a.tile(a0 + s0, b, b0 + q0, S, acc, uni, cnt);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t s = s0 + 4 * ty + i;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t q = q0 + 4 * tx + j;
-            if (s < na && q < nb) out[COLUMN ? (size_t)q * pitch + s : (size_t)s * pitch + q] = pair_distance<METRIC>(acc[i][j], uni[i], cnt[i][j], S);
+            if (s < na && q < nb) out[COLUMN ? (size_t)q * pitch + s : (size_t)s * pitch + q] = pair_distance<SET::METRIC>(acc[i][j], uni[i], cnt[i][j], S);
         }
     }
 }
 
-template <int METRIC, int COLUMN>
-__global__ __launch_bounds__(128) void k_search_dist(const double *__restrict__ aT, const double *__restrict__ awT, uint32_t AP, uint32_t a0,
-                                                     uint32_t na, const double *__restrict__ bT, uint32_t BP, uint32_t b0, uint32_t nb,
-                                                     uint32_t S, double *__restrict__ out, uint32_t pitch) {
-    search_dist_tile<METRIC, COLUMN>(na, nb, S, out, pitch, [&](uint32_t s0, uint32_t q0, double (&acc)[4][4], double (&uni)[4], uint32_t (&cnt)[4][4]) {
-        pair_tile<METRIC>(aT, awT, AP, a0 + s0, bT, BP, b0 + q0, S, acc, uni, cnt);
-    });
-}
-
-// HULK_METRIC_BOTTOMK: the same text over bottomk_tile's count (hulk_bottomk_tile.h) — rows a0 .. a0 + na of the prepared queries
-// against rows b0 .. b0 + nb of the prepared strip; symmetric, so the queries are always the rows of `out`
-__global__ __launch_bounds__(128) void k_search_dist_bottomk(const BottomkSet a, uint32_t a0, uint32_t na, const BottomkSet b, uint32_t b0,
-                                                             uint32_t nb, uint32_t S, double *__restrict__ out, uint32_t pitch) {
-    search_dist_tile<0, 0>(na, nb, S, out, pitch, [&](uint32_t s0, uint32_t q0, double (&)[4][4], double (&)[4], uint32_t (&cnt)[4][4]) {
-        bottomk_tile(a, a0 + s0, b, b0 + q0, S, cnt);
-    });
+template <class SET, int COLUMN>
+__global__ __launch_bounds__(128) void k_search_dist(const SET a, uint32_t a0, uint32_t na, const SET b, uint32_t b0, uint32_t nb, uint32_t S,
+                                                     double *__restrict__ out, uint32_t pitch) {
+    search_dist<SET, COLUMN>(a, a0, na, b, b0, nb, S, out, pitch);
 }
 
 // dist [mq][pitch]: row r = query qbase + r against database sketches pbase .. pbase + np.  lkey / lidx [M][K]: the running lists,
@@ -115,17 +106,6 @@ bool search_plan(uint32_t m, uint64_t n_db, uint32_t S, uint64_t scratch_bytes, 
     Pb = std::min<uint64_t>(Pb, std::min<uint64_t>((n_db + 63) / 64 * 64, SEARCH_MAX_PB));
     *Mb_out = (uint32_t)Mb; *Pb_out = (uint32_t)Pb;
     return true;
-}
-
-template <int METRIC, int COLUMN>
-void search_dist(const double *qmT, const double *qwT, uint32_t QP, uint32_t qb, uint32_t mq, const double *dmT, const double *dwT,
-                 uint32_t DP, uint32_t np, uint32_t S, double *d_dist, uint32_t pitch) {
-    if (COLUMN)
-        hipLaunchKernelGGL((k_search_dist<METRIC, 1>), dim3((mq + PAIR_TQ - 1) / PAIR_TQ, (np + PAIR_TS - 1) / PAIR_TS), dim3(128), 0, nullptr,
-                           dmT, dwT, DP, 0u, np, qmT, QP, qb, mq, S, d_dist, pitch);
-    else
-        hipLaunchKernelGGL((k_search_dist<METRIC, 0>), dim3((np + PAIR_TQ - 1) / PAIR_TQ, (mq + PAIR_TS - 1) / PAIR_TS), dim3(128), 0, nullptr,
-                           qmT, qwT, QP, qb, mq, dmT, DP, 0u, np, S, d_dist, pitch);
 }
 
 }  // namespace
@@ -179,27 +159,33 @@ extern "C" int hulk_search(int device, const uint64_t *q_mins, const double *q_w
     ONESHOT_CHK(own.alloc(&d_lkey, LK)); ONESHOT_CHK(own.alloc(&d_lidx, LK));
     ONESHOT_CHK(hipMemset(d_lkey, 0xff, LK * 8)); ONESHOT_CHK(hipMemset(d_lidx, 0xff, LK * 4));
     ONESHOT_CHK(hipMemset(d_qmT + (size_t)QP * S, 0, 64 * 8)); ONESHOT_CHK(hipMemset(d_qwT + (size_t)QP * S, 0, 64 * 8));
-    // bottomk: the same buffers hold the sorted run-length form (bottomk_view), the strips' too
-    if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, q_mins, m, S, d_raw_m, d_qmT, d_qwT));
-    else ONESHOT_CHK(upload_prepared(nullptr, q_mins, q_weights, m, S, d_raw_m, d_raw_w, d_qmT, d_qwT));
+    // bottomk: the same buffers hold the sorted run-length form (BottomkSet::view), the strips' too
+    ONESHOT_CHK(upload_set(nullptr, metric, q_mins, q_weights, m, S, d_raw_m, d_raw_w, d_qmT, d_qwT));
     double ms_dist = 0.0, ms_select = 0.0;
     uint32_t strips = 0, blocks = 0;
     for (uint64_t p0 = 0; p0 < n_db; p0 += Pb, strips++) {
         const uint32_t np = (uint32_t)std::min<uint64_t>(Pb, n_db - p0);
         // (hipMemcpy on the null stream: behind the kernels that read the previous strip)
-        if (bottomk) ONESHOT_CHK(upload_bottomk(nullptr, db_mins + (size_t)p0 * S, np, S, d_raw_m, d_dmT, d_dwT));
-        else ONESHOT_CHK(upload_prepared(nullptr, db_mins + (size_t)p0 * S, db_weights + (size_t)p0 * S, np, S, d_raw_m, d_raw_w, d_dmT, d_dwT));
+        const double *db_w = db_weights ? db_weights + (size_t)p0 * S : nullptr;        // (bottomk: may be NULL)
+        ONESHOT_CHK(upload_set(nullptr, metric, db_mins + (size_t)p0 * S, db_w, np, S, d_raw_m, d_raw_w, d_dmT, d_dwT));
         const uint32_t NP = smash_padded_n(np);                     // the pitch k_smash_prep gave this strip
         blocks = 0;
         for (uint32_t qb = 0; qb < m; qb += Mb, blocks++) {
             const uint32_t mq = std::min(Mb, m - qb);
             ONESHOT_CHK(hipEventRecord(ev[0], nullptr));
-            if (bottomk)
-                hipLaunchKernelGGL(k_search_dist_bottomk, dim3((np + PAIR_TQ - 1) / PAIR_TQ, (mq + PAIR_TS - 1) / PAIR_TS), dim3(128), 0, nullptr,
-                                   bottomk_view(d_qmT, d_qwT, QP, S), qb, mq, bottomk_view(d_dmT, d_dwT, NP, S), 0u, np, S, d_dist, Pb);
-            else if (metric != HULK_METRIC_WEIGHTED_JACCARD) search_dist<0, 0>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
-            else if (column) search_dist<1, 1>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
-            else search_dist<1, 0>(d_qmT, d_qwT, QP, qb, mq, d_dmT, d_dwT, NP, np, S, d_dist, Pb);
+            with_set(metric, d_qmT, d_qwT, QP, S, [&](auto qs) {
+                using SET = decltype(qs);
+                const SET ds = SET::view(d_dmT, d_dwT, NP, S);
+                if constexpr (SET::METRIC == 1) {                   // ROLE column: the strip is the subject side.  The symmetric
+                    if (column) {                                   // metrics have no such instance: the role changes nothing
+                        hipLaunchKernelGGL((k_search_dist<SET, 1>), dim3((mq + PAIR_TQ - 1) / PAIR_TQ, (np + PAIR_TS - 1) / PAIR_TS), dim3(128), 0,
+                                           nullptr, ds, 0u, np, qs, qb, mq, S, d_dist, Pb);
+                        return;
+                    }
+                }
+                hipLaunchKernelGGL((k_search_dist<SET, 0>), dim3((np + PAIR_TQ - 1) / PAIR_TQ, (mq + PAIR_TS - 1) / PAIR_TS), dim3(128), 0, nullptr,
+                                   qs, qb, mq, ds, 0u, np, S, d_dist, Pb);
+            });
             ONESHOT_CHK(hipGetLastError());
             ONESHOT_CHK(hipEventRecord(ev[1], nullptr));
             hipLaunchKernelGGL(k_search_select, dim3((mq + 3) / 4), dim3(256), 0, nullptr, d_dist, Pb, mq, np, qb, (uint32_t)p0, K, lim,
