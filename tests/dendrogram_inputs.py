@@ -48,11 +48,15 @@ def kruskal(D):
             x = parent[x]
         return x
     a, b, d = [], [], []
-    for x, y, h in zip(i[order].tolist(), j[order].tolist(), w[order].tolist()):
-        rx, ry = find(x), find(y)
-        if rx != ry:
-            parent[max(rx, ry)] = min(rx, ry)
-            a.append(x); b.append(y); d.append(h)
+    for at in range(0, len(order), 1 << 16):                        # in pieces: a spanning tree is complete long before the last edge
+        piece = order[at:at + (1 << 16)]
+        for x, y, h in zip(i[piece].tolist(), j[piece].tolist(), w[piece].tolist()):
+            rx, ry = find(x), find(y)
+            if rx != ry:
+                parent[max(rx, ry)] = min(rx, ry)
+                a.append(x); b.append(y); d.append(h)
+        if len(a) == n - 1:                                         # every later edge closes a cycle
+            break
     return np.array(a, dtype=np.uint32), np.array(b, dtype=np.uint32), np.array(d, dtype=np.float64)
 
 

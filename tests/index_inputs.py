@@ -253,6 +253,158 @@ def check_few_bands(s=33, bands=2):
     return missed
 
 
+# ---- 7. the staging buffer's second piece ---------------------------------------------------------------------------------------------------
+# upload_rows (hulk_index.hip) sends raw mins up INDEX_STAGE = 2^23 entries at a time; piece k lands at d_out + k * 2^23.  At S = 512
+# the first piece is 16,384 sketches exactly, and 64 more make a second one — on the build side for the database and on the query
+# side for as many queries.  The arrays are 67 MB each and are NOT cached: the tests free them when they are done.
+STAGE_S, STAGE_N, STAGE_D = 512, 16448, 0.05
+STAGE_BORDER = (1 << 23) // STAGE_S                                # 16,384: the first sketch of the second piece
+STAGE_COPIES = (0, 1, STAGE_BORDER - 1, STAGE_BORDER, STAGE_N - 1)  # rows with a byte-identical query
+STAGE_NEAR = tuple(range(STAGE_BORDER - 4, STAGE_BORDER + 4))      # rows with a query that differs in u_max slots: a hit at the threshold's edge
+STAGE_FAR = tuple(range(STAGE_BORDER - 8, STAGE_BORDER - 4)) + tuple(range(STAGE_BORDER + 4, STAGE_BORDER + 8))    # ... in u_max + 1 slots: none
+STAGE_K = 2
+
+
+def stage_constants():
+    import os
+    import re
+    text = open(os.path.join(si.ROOT, "hulk_amd", "csrc", "hulk_index.hip")).read()
+    m = re.search(r"constexpr size_t INDEX_STAGE = (\d+)u << (\d+);", text)
+    return int(m.group(1)) << int(m.group(2))
+
+
+def stage_database():
+    """[16448][512] random 50-bit mins (any two rows differ in every slot: check_stage_database)"""
+    return np.random.default_rng(8200).integers(0, 1 << 50, size=(STAGE_N, STAGE_S), dtype=np.uint64)
+
+
+def stage_near_copy(rng, row, differ, spread):
+    """row with `differ` slots replaced by values no row holds (above 2^50); spread: one in each of the first `differ` bands"""
+    out = row.copy()
+    if spread:
+        edges = band_edges(STAGE_S, default_bands(STAGE_S, STAGE_D))
+        at = [int(rng.integers(edges[j], edges[j + 1])) for j in range(differ)]
+    else:
+        at = rng.choice(STAGE_S, size=differ, replace=False)
+    out[at] = (np.uint64(1 << 51) + rng.integers(0, 1 << 40, size=differ, dtype=np.uint64))
+    return out
+
+
+def stage_query(rng, db, r, kind):
+    """the query made of database row r -> (query, its distance from r as the kernels compute it, or None if r is no hit)"""
+    u = u_max(STAGE_S, STAGE_D)
+    if kind == "near":
+        return stage_near_copy(rng, db[r], u, spread=False), 1.0 - (float(STAGE_S - u) / float(STAGE_S))
+    if kind == "far":
+        return stage_near_copy(rng, db[r], u + 1, spread=(r % 2 == 0)), None
+    return db[r].copy(), 0.0
+
+
+def stage_build_queries(db):
+    """64 queries with their hits in both pieces of the database -> (queries [64][512], [(the row a query was made of, its kind)])"""
+    rng = np.random.default_rng(8201)
+    plan = [(r, "copy") for r in STAGE_COPIES] + [(r, "near") for r in STAGE_NEAR] + [(r, "far") for r in STAGE_FAR]
+    rest = [r for r in rng.permutation(STAGE_N).tolist() if r not in STAGE_COPIES + STAGE_NEAR + STAGE_FAR]
+    plan += [(r, "copy") for r in [r for r in rest if r < STAGE_BORDER][:22] + [r for r in rest if r >= STAGE_BORDER][:21]]
+    plan = [plan[i] for i in rng.permutation(len(plan)).tolist()]
+    return np.array([stage_query(rng, db, r, kind)[0] for r, kind in plan], dtype=np.uint64), plan
+
+
+def stage_distances(qm, db):
+    """[m][n] jaccard distances in numpy: 1.0 - (slots equal as doubles) / S, the yardstick's expression (mins below 2^53 are exact)"""
+    out = np.empty((len(qm), len(db)))
+    for i, q in enumerate(qm):
+        out[i] = 1.0 - ((db == q).sum(axis=1).astype(np.float64) / float(STAGE_S))
+    return out
+
+
+def stage_candidates(qm, db, D):
+    """[m][n] bool from band_keys — computed for the database rows that share a slot with some query; a row that shares none has no
+    band in common with any query and equal keys would be a collision of the 64-bit hash"""
+    b = default_bands(STAGE_S, STAGE_D)
+    related = np.flatnonzero((D < 1.0).any(axis=0))
+    cand = np.zeros(D.shape, dtype=bool)
+    cand[:, related] = candidates(band_keys(qm, b), band_keys(db[related], b))
+    return cand, related
+
+
+def check_stage_database(db):
+    assert stage_constants() == 1 << 23 and STAGE_BORDER * STAGE_S == 1 << 23 < STAGE_N * STAGE_S, NO_TEST + "the database fits one piece"
+    assert (STAGE_N - STAGE_BORDER) * STAGE_S < 1 << 23 and u_max(STAGE_S, STAGE_D) == 25 and default_bands(STAGE_S, STAGE_D) == 26
+    rng = np.random.default_rng(8202)
+    for a, b in rng.integers(0, STAGE_N, size=(200, 2)).tolist():
+        assert a == b or not (db[a] == db[b]).any(), NO_TEST + f"rows {a} and {b} share a slot"
+    for r in STAGE_COPIES + STAGE_NEAR + STAGE_FAR:
+        assert np.flatnonzero((db == db[r]).any(axis=1)).tolist() == [r], NO_TEST + f"row {r} shares a slot with another row"
+
+
+def check_stage_build(db, qm, plan):
+    """-> (D [64][n], candidates): every query is at 1.0 from every row but its own; copies at 0, near-copies at the last distance
+    within the threshold, the others one slot beyond it; hits on both sides of the border"""
+    u, d = u_max(STAGE_S, STAGE_D), STAGE_D
+    D = stage_distances(qm, db)
+    cand, related = stage_candidates(qm, db, D)
+    rows = [r for r, _ in plan]
+    assert sorted(related.tolist()) == sorted(set(rows)) and len(plan) == 64, NO_TEST + "a query is related to another row than its own"
+    for i, (r, kind) in enumerate(plan):
+        assert np.flatnonzero(D[i] < 1.0).tolist() == [r]
+        differ = int((qm[i] != db[r]).sum())
+        assert differ == {"copy": 0, "near": u, "far": u + 1}[kind], NO_TEST + f"query {i} of row {r} differs in {differ} slots"
+        assert (D[i, r] <= d) == (kind != "far") and (kind == "far" or cand[i, r]), NO_TEST + f"query {i} of row {r}"
+        if kind == "far":
+            assert cand[i, r] == (r % 2 == 1), NO_TEST + "a far copy with a slot in every band is no candidate, one with an intact band is"
+    assert int(cand.sum()) == 64 - len(STAGE_FAR) // 2
+    hit = np.array([r for i, (r, kind) in enumerate(plan) if kind != "far"])
+    assert (hit < STAGE_BORDER).sum() >= 20 and (hit >= STAGE_BORDER).sum() >= 20, NO_TEST + "too few hits on one side of the border"
+    for r in STAGE_COPIES:
+        assert (r, "copy") in plan
+    sub = np.array(sorted(set(rows) | set(range(60, 70))))
+    assert np.array_equal(bits_of(D[:, sub]), bits_of(jaccard_blocks(qm, db[sub]))), "the numpy distances are not the oracle's"
+    return D, cand
+
+
+def bits_of(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def stage_full_queries(db):
+    """16,448 queries, query i made of row perm[i]: a copy, but for the queries on either side of the border of the QUERY side
+    (STAGE_NEAR: u_max slots differ, STAGE_FAR: u_max + 1) -> (queries, perm, the expected (index [m][2], distance, count))"""
+    rng = np.random.default_rng(8203)
+    perm = rng.permutation(STAGE_N)
+    u = u_max(STAGE_S, STAGE_D)
+    qm = db[perm]                                                    # (a copy)
+    index = np.full((STAGE_N, STAGE_K), NONE, dtype=np.uint32); dist = np.full((STAGE_N, STAGE_K), np.nan); count = np.ones(STAGE_N, dtype=np.uint32)
+    index[:, 0] = perm; dist[:, 0] = 0.0
+    for i in STAGE_NEAR:
+        qm[i] = stage_near_copy(rng, db[perm[i]], u, spread=False)
+        dist[i, 0] = 1.0 - (float(STAGE_S - u) / float(STAGE_S))
+    for i in STAGE_FAR:
+        qm[i] = stage_near_copy(rng, db[perm[i]], u + 1, spread=(i % 2 == 0))
+        index[i, 0] = NONE; dist[i, 0] = np.nan; count[i] = 0
+    return qm, perm, (index, dist, count)
+
+
+def check_stage_full(db, qm, perm, want):
+    index, dist, count = want
+    assert sorted(perm.tolist()) == list(range(STAGE_N)), NO_TEST + "not a permutation"
+    assert (perm[:STAGE_BORDER] >= STAGE_BORDER).any() and (perm[STAGE_BORDER:] < STAGE_BORDER).any()
+    differ = (qm != db[perm]).sum(axis=1)
+    u = u_max(STAGE_S, STAGE_D)
+    assert sorted(np.flatnonzero(differ).tolist()) == sorted(STAGE_NEAR + STAGE_FAR), NO_TEST + "the planted queries are not around the border"
+    assert (differ[list(STAGE_NEAR)] == u).all() and (differ[list(STAGE_FAR)] == u + 1).all()
+    assert (count[list(STAGE_FAR)] == 0).all() and int(count.sum()) == STAGE_N - len(STAGE_FAR)
+    assert (dist[list(STAGE_NEAR), 0] <= STAGE_D).all() and (dist[list(STAGE_NEAR), 0] > 0).all()
+    # by construction a query shares slots with its own row alone; held to the oracle on the planted queries and a sample
+    rng = np.random.default_rng(8204)
+    some = np.array(sorted(set(STAGE_NEAR + STAGE_FAR + STAGE_COPIES) | set(rng.integers(0, STAGE_N, size=20).tolist())))
+    D = stage_distances(qm[some], db)
+    got = select(D, STAGE_K, max_distance=STAGE_D)
+    for g, w in zip(got, (index[some], dist[some], count[some])):
+        assert np.array_equal(g.view(np.uint8), w.view(np.uint8)), NO_TEST + "the expected lists are not the yardstick's"
+    assert ((D < 1.0).sum(axis=1) == 1).all(), NO_TEST + "a query shares a slot with another row than its own"
+
+
 # ---- the file format, restated ------------------------------------------------------------------------------------------------------------
 MAGIC = b"HULKIDX\n"
 

@@ -351,3 +351,39 @@ def test_cpp_host_matches_the_python_binding(tmp_path):
         assert open(str(tmp_path / "cpp.hulk-index"), "rb").read() == open(str(tmp_path / "py.hulk-index"), "rb").read()
     r = subprocess.run([exe, qf, df, str(s), "5", "1.0", "0", "-1", "0", str(tmp_path / "x")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 1 and "hulk::Error -30|" in r.stdout and "use hulk_search" in r.stdout
+
+
+# ---- the staging buffer's second piece ---------------------------------------------------------------------------------------------------
+def test_build_in_two_staging_pieces():
+    """S = 512, n = 16,448: upload_rows sends the database up in a piece of 16,384 sketches and one of 64, the second to d_out + 2^23.
+    64 queries whose only hits are copies and near-copies of rows in both pieces, on either side of the border"""
+    from hulk_amd.smash import Index, search
+    db = ii.stage_database()
+    ii.check_stage_database(db)
+    qm, plan = ii.stage_build_queries(db)
+    D, cand = ii.check_stage_build(db, qm, plan)
+    with Index.build(db, ii.STAGE_D) as ix:
+        assert (ix.info["n"], ix.info["sketch_size"], ix.info["bands"]) == (ii.STAGE_N, ii.STAGE_S, ii.default_bands(ii.STAGE_S, ii.STAGE_D))
+        got, st = run(ix, qm, D, cand, ii.STAGE_K, None, "two pieces of the database")
+        assert int(got[2].sum()) == 64 - len(ii.STAGE_FAR)
+    ones = np.ones(db.shape)
+    assert same_bytes(got, search(qm, ones[:64], db, ones, ii.STAGE_K, "jaccard", max_distance=ii.STAGE_D)), "hulk_search"
+    del db, ones, D, cand
+
+
+def test_queries_in_two_staging_pieces():
+    """m = 16,448 queries at S = 512: the query side of upload_rows takes its second piece.  Query i is a copy (or a planted
+    near-copy) of database row perm[i] and shares no slot with any other row: its list is known by construction"""
+    from hulk_amd.smash import Index, search
+    db = ii.stage_database()
+    qm, perm, want = ii.stage_full_queries(db)
+    ii.check_stage_full(db, qm, perm, want)
+    with Index.build(db, ii.STAGE_D) as ix:
+        st = {}
+        got = ix.search(qm, ii.STAGE_K, stats=st)
+    assert_hits(got, want, "two pieces of the queries")
+    assert same_bytes(got, want)
+    assert st["within"] == ii.STAGE_N - len(ii.STAGE_FAR) and st["candidates"] == st["within"] + len(ii.STAGE_FAR) // 2, st
+    ones = np.ones(db.shape)
+    assert same_bytes(got, search(qm, ones, db, ones, ii.STAGE_K, "jaccard", max_distance=ii.STAGE_D)), "hulk_search"
+    del db, qm, ones

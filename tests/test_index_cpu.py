@@ -173,3 +173,17 @@ def test_shapes_beyond_the_launch_limits_are_refused_before_any_hip_call():
     o = _lib.IndexOpts(max_distance=0.5, bands=65535)
     assert L.hulk_index_build(0, m.ctypes.data, 65538, 65535, ctypes.byref(o), ctypes.byref(h)) == ERR_ARG
     assert b"sketches x bands must be below 2^32" in L.hulk_last_error(None) and h.value is None
+
+
+def test_inputs_of_the_second_staging_piece():
+    """S = 512, n = m = 16,448: the database and the full set of queries each need a second piece of upload_rows' staging buffer,
+    and the planted copies and near-copies sit on both sides of the border"""
+    db = ii.stage_database()
+    ii.check_stage_database(db)
+    qm, plan = ii.stage_build_queries(db)
+    D, cand = ii.check_stage_build(db, qm, plan)
+    lists, n_cand, n_within = ii.expected(D, cand, ii.STAGE_K, ii.STAGE_D)
+    assert n_within == 64 - len(ii.STAGE_FAR) == int(lists[2].sum()) and n_cand == n_within + len(ii.STAGE_FAR) // 2
+    full, perm, want = ii.stage_full_queries(db)
+    ii.check_stage_full(db, full, perm, want)
+    del db, qm, D, cand, full, perm, want
