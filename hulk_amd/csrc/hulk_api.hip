@@ -748,6 +748,21 @@ int hulk_debug_read(hulk_ctx *c, uint32_t what, void *out, uint64_t *bytes_io) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HULK_OK;
 }
+
+int hulk_debug_jump(hulk_ctx *c, const uint64_t *values, uint64_t n, uint32_t region_len, uint32_t *bins_out, uint64_t *guard_hits) {
+    if (!c) return fail(c, HULK_ERR_ARG, "NULL");
+    if (n == 0) {                                                   // the step path's counter
+        if (!guard_hits) return fail(c, HULK_ERR_ARG, "NULL");
+        { int rcs = sync_all(c); if (rcs != HULK_OK) return rcs; }
+        HIPCHK(c, step_guard_hits(guard_hits));
+        return HULK_OK;
+    }
+    if (!values || !bins_out) return fail(c, HULK_ERR_ARG, "NULL");
+    if (n > (1ull << 28) || region_len == 0) return fail(c, HULK_ERR_ARG, "hulk_debug_jump: n <= 2^28, region_len >= 1");
+    { int rcs = sync_all(c); if (rcs != HULK_OK) return rcs; }
+    HIPCHK(c, launch_debug_jump(c->stream, values, n, region_len, c->B, bins_out, guard_hits));
+    return HULK_OK;
+}
 #endif
 
 int hulk_get_device_checks(hulk_ctx *c, uint32_t *lds_order_ok, uint32_t *cms_chain_form) {

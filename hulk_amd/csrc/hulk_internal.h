@@ -127,6 +127,13 @@ hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParam
 // what launch_minimizer_post records in `geom` (host integers, profiling build only: the test hook HULK_DEBUG_NIBBLE):
 // spectra of the launch, parts per spectrum, bin ranges, log2 of a range's bins, threads of a histogram workgroup
 constexpr int SPECTRUM_GEOM_WORDS = 5;
+#ifdef HULK_EXPERIMENTS
+// hulk_debug_jump (below): host arrays in and out, synchronous on `s`
+hipError_t launch_debug_jump(hipStream_t s, const uint64_t *values, uint64_t n, uint32_t region_len, int32_t num_bins,
+                             uint32_t *bins_out, uint64_t *guard_hits);
+// the guarded lane-steps of the step path's k_jump_bin launches on the current device since the last call (read, then wiped)
+hipError_t step_guard_hits(uint64_t *out);
+#endif
 uint32_t minimizer_list_rcap(uint32_t w, bool pair);
 hipError_t launch_long_group(hipStream_t s, const uint8_t *d_bases, const LongSeqDesc *d_desc, uint32_t n_seqs,
                              uint64_t max_npos, MinimizerParams P, uint64_t *d_xs, uint8_t *d_valid, uint64_t *d_table,
@@ -239,6 +246,17 @@ inline double now_s() { return std::chrono::duration<double>(std::chrono::steady
 // context accessors for hulk_ingest_device.hip (defined in hulk_flush.hip; not part of the ABI)
 }  // namespace hulk
 struct hulk_ctx;
+#ifdef HULK_EXPERIMENTS
+// Test hook of the profiling build for k_jump_bin alone (tests/test_gpu_jump_pair.py binds it itself; it is no part of the
+// documented hook set of include/hulk_hip.h): `n` 64-bit values (host), laid out as regions of `region_len` values, go through
+// k_jump_bin with the context's num_bins and the HULK_JUMP_* settings of the process.  bins_out [n] (host) receives the bins;
+// *guard_hits (may be NULL) the number of lane-steps that took the kernel's exact step because the guard of the paired step
+// fired (0 under HULK_JUMP_NO_GUARD).  Synchronous.
+// With n == 0 (values and bins_out may be NULL) nothing is launched: *guard_hits receives the guarded lane-steps of the k_jump_bin
+// launches of the STEP PATH (hulk_add_reads ...) on the context's device since the last such call, and the counter is wiped.
+extern "C" int hulk_debug_jump(hulk_ctx *ctx, const uint64_t *values, uint64_t n, uint32_t region_len, uint32_t *bins_out,
+                               uint64_t *guard_hits);
+#endif
 namespace hulk {
 hipStream_t ctx_stream(hulk_ctx *c);
 uint64_t ctx_min_read_len(const hulk_ctx *c);

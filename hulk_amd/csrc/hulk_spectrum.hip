@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <vector>
 
 namespace hulk {
 namespace {
@@ -17,26 +18,49 @@ namespace {
 // again densely (no lock-step tail per 64 values); no LDS, 8 waves/SIMD.
 // Output: key = spectrum slot << 20 | bin  (k^4 < 2^20 for k <= 31).
 // ------------------------------------------------------------------------------------------
-// The step loop of the jump kernels in assembly (fixed registers v40..v58, s60..s63): hipcc's version of the same loop
-// carries two v_mov_b64 and a dozen scalar mask instructions per pair of steps; this one is the 14 VALU instructions of a
-// step (v_cmp and v_trunc_f64 among them) plus s_and and the exit test, the LCG state ping-ponging between v[40:41] and v[42:43].
+// The step loop of the jump kernels in assembly (fixed registers v40..v58, v60..v63, s60..s65): hipcc's version of the same loop
+// carries two v_mov_b64 and a dozen scalar mask instructions per pair of steps.  One trip of this one advances the LCG TWICE
+// (28 VALU instructions, ONE v_rcp_f64), the LCG state going v[40:41] -> v[42:43] -> v[40:41].
 //  * key * a + 1: the upper dword's two cross products are two chained v_mad_u64_u32 (0 + lo * a_hi, then + hi * a_lo; only the
 //    lower dword of the sum is used) and one v_add_u32 onto the upper dword of lo * a_lo + 1.
 //  * r * 2^-31 = ((key >> 33) + 1) * 2^-31 without a conversion: the shift result m is written into the lower dword of a pair
 //    whose upper dword is held at 0x43300000, which IS the double 2^52 + m, and ONE fma(2^52 + m, 2^-31, 2^-31 - 2^21) gives
 //    (m + 1) * 2^-31 exactly (the product 2^21 + m * 2^-31 is exact inside the fma, the sum is representable, and so is the
 //    constant 2^-31 - 2^21: 52 significant bits).  VOP3 takes one scalar operand: the constant lives in v[56:57].
+//
+// One reciprocal per two steps.  The reference's step is j = int64(float64(b+1) * (float64(1<<31) / float64(r))), and the exact
+// sequence (quot31_exact: v_rcp_f64 + two Newton steps = RN(2^31 / r), then one fma) reproduces Go's two roundings.  The
+// result needs them in one case only.  Let Q = (b+1) * 2^31 / r exactly.  Go's p is within Q * 2^-52 of Q; a non-integer Q is
+// at least 1 / r >= 2^-31 away from every integer, and p only matters while Q < 2^21 (n < 2^20 for every legal k: the key word
+// is slot << 20 | bin; beyond 2^21 both sides leave), where Q * 2^-52 < 2^-31: so trunc(p) = floor(Q) and (p >= n) = (Q >= n)
+// unless Q IS an integer.  Any approximation p~ of relative error eps decides the same way as long as it is farther than
+// Q * eps from the nearest integer.  The key does not depend on b (key' = a * key + 1), so the divisors of two steps are known
+// before the first product, and with x = r * 2^-31 (so that 2^31 / r = 1 / x):
+//      P = RN(x_a * x_b),  rho = one Newton step on v_rcp_f64(P),  q_a = RN(rho * x_b) ~ 1 / x_a,  q_b = RN(rho * x_a) ~ 1 / x_b.
+// Measured on gfx950 (tools/ubench/rcp_pair_seed.hip, profiles/k1b_pair.md): over 2^30 pairs from this LCG and over every
+// single r in [1, 2^31] the seed's relative error is at most 2^-24.36, rho's after ONE Newton step 2^-48.66 (the seed's square,
+// 2^-48.72, plus the fma's rounding), and |1 - x * q| at most 2^-48.59 with the roundings of P and of the two products in it;
+// p~ = fma(t, q, q) adds 2^-53: eps < 2^-48.5, far inside the 2^-43 the guard below is sized for (a seed up to 2^-21.5 would do).
+//  * The guard.  For p~ < 2^21 with exponent e, bits 12..31 of its lower dword are fraction bits of weights 2^(e-40) .. 2^(e-21).
+//    A p~ within Q * 2^-42 < 2^(e-41) of an integer has them all zero or all one: (lo + 0x1000) < 0x2000 unsigned, two VALU
+//    instructions.  Otherwise p~ is at least 2^(e-40) from every integer, 2^7 times the error, and decides as Go does.  (For
+//    p~ >= 2^21 the test may fire for nothing; that lane leaves either way.)  Random data fires it with probability 2^-19 per
+//    lane and step.  When any live lane's guard fires the wave branches — a scalar branch, nothing else on the common path —
+//    to ONE exact step inside the block (labels 5/7/9): for the flagged lanes only, today's v_rcp_f64 on the step's own x plus
+//    two Newton steps and the fma, whose p replaces p~ before the exit test.  (The second half's x is made again from the key
+//    in v41: no register holds it across the first half.)  An integer Q is therefore still rounded exactly as Go rounds it.
 // Lanes that reach p >= n leave the exec mask and keep their t.  The loop ends when at most `cut`
-// lanes are still running (cut = 0: when none is): chains take 12.8 +- 3.5 steps, so the last few lanes of a round
-// of 64 would keep the whole wave busy for ~24 — they are handed over instead (`left` = their mask, key/t = their
-// state at a step boundary) and finished in a denser round of the wave's pool (below).
+// lanes are still running (cut = 0: when none is), tested after either half: chains take 12.8 +- 3.5 steps, so the last few
+// lanes of a round of 64 would keep the whole wave busy for ~24 — they are handed over instead (`left` = their mask, key/t =
+// their state at a step boundary) and finished in a denser round of the wave's pool (below).
 // p >= n is tested on the upper dwords alone: p is a non-negative finite double and n < 2^20 is an integer whose
 // double has a zero lower dword, so bits(p) >= bits(n) <=> hi(p) >= hi(n)  (v_cmp_lt_u32 instead of v_cmp_nge_f64).
 //
 // The block is entered and left without a copy: the C++ values are bound to the loop's registers by physical-register
 // constraints.  The three loop-invariant registers (v47, v[56:57], v58) are written once per kernel by jump_consts() and only
 // read here; key and t are in/out operands in v[40:41] and v[44:45], so a caller's value is computed into them and used out
-// of them; the only move left in the block is the odd exit's, which brings the live key back from v[42:43].
+// of them; the only move left in the block is the odd exit's, which brings the live key back from v[42:43] (the trip has
+// already written the second step's key over v[40:41]).
 // The block runs in wave-uniform control flow and takes the lanes it is to work on as a scalar mask (`entry`): lanes outside
 // it keep key and t as they came and are never in `left`.  `left` comes out as what it is, EXEC at the exit in a scalar
 // pair, and is used as a mask from there on (lane_in, rank_in): no lane ever holds it as a bool.
@@ -54,49 +78,95 @@ __device__ __forceinline__ JumpConsts jump_consts(double fn) {
                  : [clo] "s"((uint32_t)cb), [chi] "s"((uint32_t)(cb >> 32)), [fhi] "v"(fhi));
     return K;
 }
-__device__ __forceinline__ unsigned long long jump_steps_asm(uint64_t &key, double &t, const JumpConsts &K,
+// thr: the guard's window, 0x2000 (0 = it never fires: HULK_JUMP_NO_GUARD of the profiling build, which also counts the lanes
+// that took the exact step, per wave, in a scalar register; the shipping build has no counter)
+constexpr uint32_t JUMP_GUARD_WINDOW = 0x2000u;
+struct JumpGuard { uint32_t thr, hits; };
+#ifdef HULK_EXPERIMENTS
+#define HULK_JGUARD_COUNT "s_bcnt1_i32_b64 s63, vcc\n\ts_add_u32 %[gh], %[gh], s63\n\t"
+#define HULK_JGUARD_OUT(x) , [gh] "+s"(x)
+#else
+#define HULK_JGUARD_COUNT
+#define HULK_JGUARD_OUT(x)
+#endif
+__device__ __forceinline__ unsigned long long jump_steps_asm(uint64_t &key, double &t, const JumpConsts &K, JumpGuard &G,
                                                              unsigned long long entry, uint32_t cut) {
     unsigned long long left;
-#define HULK_JSTEP(KS_LO, KS_HI, KD, KD_HI, EXIT)                                    \
+    // key' = key * a + 1 into KD, x = ((key' >> 33) + 1) * 2^-31 into X
+#define HULK_JLCG(KS_LO, KS_HI, KD, KD_HI, X)                                        \
     "v_mad_u64_u32 v[52:53], s[62:63], " KS_LO ", %[ahi], 0\n\t"                     \
     "v_mad_u64_u32 v[54:55], s[62:63], " KS_HI ", %[alo], v[52:53]\n\t"              \
     "v_mad_u64_u32 " KD ", s[62:63], " KS_LO ", %[alo], 1\n\t"                       \
     "v_add_u32 " KD_HI ", " KD_HI ", v54\n\t"                                        \
     "v_lshrrev_b32 v46, 1, " KD_HI "\n\t"                                            \
-    "v_fma_f64 v[48:49], v[46:47], %[p31], v[56:57]\n\t"                             \
-    "v_rcp_f64 v[50:51], v[48:49]\n\t"                                               \
-    "s_nop 0\n\t"                                                                    \
-    "v_fma_f64 v[52:53], -v[48:49], v[50:51], 1.0\n\t"                               \
-    "v_fma_f64 v[50:51], v[50:51], v[52:53], v[50:51]\n\t"                           \
-    "v_fma_f64 v[52:53], -v[48:49], v[50:51], 1.0\n\t"                               \
-    "v_fma_f64 v[50:51], v[50:51], v[52:53], v[50:51]\n\t"                           \
-    "v_fma_f64 v[54:55], v[44:45], v[50:51], v[50:51]\n\t"                           \
+    "v_fma_f64 " X ", v[46:47], %[p31], v[56:57]\n\t"
+    // p~ = fma(t, q, q) and its guard (to GUARDED and back at BACK with p in v[54:55]), the exit test, t = trunc(p), the cut
+#define HULK_JHALF(Q, GUARDED, BACK)                                                 \
+    "v_fma_f64 v[54:55], v[44:45], " Q ", " Q "\n\t"                                 \
+    "v_add_u32 v52, 0x1000, v54\n\t"                                                 \
+    "v_cmp_gt_u32 vcc, %[gthr], v52\n\t"                                             \
+    "s_cbranch_vccnz " GUARDED "\n"                                                  \
+    BACK ":\n\t"                                                                     \
     "v_cmp_lt_u32 vcc, v55, v58\n\t"                                                 \
     "s_and_b64 exec, exec, vcc\n\t"                                                  \
     "v_trunc_f64 v[44:45], v[54:55]\n\t"                                             \
     "s_bcnt1_i32_b64 s62, exec\n\t"                                                  \
-    "s_cmp_le_u32 s62, %[cut]\n\t"                                                   \
-    "s_cbranch_scc1 " EXIT "\n\t"
+    "s_cmp_le_u32 s62, %[cut]\n\t"
     asm volatile(
         "s_and_saveexec_b64 s[60:61], %[entry]\n\t"
         "1:\n\t"
-        HULK_JSTEP("v40", "v41", "v[42:43]", "v43", "3f")
-        HULK_JSTEP("v42", "v43", "v[40:41]", "v41", "2f")
-        "s_branch 1b\n\t"
+        HULK_JLCG("v40", "v41", "v[42:43]", "v43", "v[48:49]")
+        HULK_JLCG("v42", "v43", "v[40:41]", "v41", "v[50:51]")
+        "v_mul_f64 v[52:53], v[48:49], v[50:51]\n\t"               // P
+        "v_rcp_f64 v[54:55], v[52:53]\n\t"
+        "s_nop 0\n\t"
+        "v_fma_f64 v[60:61], -v[52:53], v[54:55], 1.0\n\t"
+        "v_fma_f64 v[54:55], v[54:55], v[60:61], v[54:55]\n\t"     // rho
+        "v_mul_f64 v[60:61], v[54:55], v[50:51]\n\t"               // q_a
+        "v_mul_f64 v[62:63], v[54:55], v[48:49]\n\t"               // q_b
+        HULK_JHALF("v[60:61]", "5f", "6")
+        "s_cbranch_scc1 3f\n\t"
+        HULK_JHALF("v[62:63]", "7f", "8")
+        "s_cbranch_scc0 1b\n\t"
+        "s_branch 2f\n"
+        "7:\n\t"                                   // the exact step, second half: its x again, then as the first half's
+        "v_lshrrev_b32 v46, 1, v41\n\t"
+        "v_fma_f64 v[48:49], v[46:47], %[p31], v[56:57]\n\t"
+        "s_mov_b32 s62, 1\n\t"
+        "s_branch 9f\n"
+        "5:\n\t"
+        "s_mov_b32 s62, 0\n"
+        "9:\n\t"                                   // x in v[48:49], the flagged lanes in vcc, s62: which half to go back to
+        "s_and_saveexec_b64 s[64:65], vcc\n\t"
+        HULK_JGUARD_COUNT
+        "v_rcp_f64 v[50:51], v[48:49]\n\t"
+        "s_nop 0\n\t"
+        "v_fma_f64 v[52:53], -v[48:49], v[50:51], 1.0\n\t"
+        "v_fma_f64 v[50:51], v[50:51], v[52:53], v[50:51]\n\t"
+        "v_fma_f64 v[52:53], -v[48:49], v[50:51], 1.0\n\t"
+        "v_fma_f64 v[50:51], v[50:51], v[52:53], v[50:51]\n\t"
+        "v_fma_f64 v[54:55], v[44:45], v[50:51], v[50:51]\n\t"
+        "s_mov_b64 exec, s[64:65]\n\t"
+        "s_cmp_eq_u32 s62, 0\n\t"
+        "s_cbranch_scc1 6b\n\t"
+        "s_branch 8b\n"
         "3:\n\t"                                   // left after the first half: the live key is in v[42:43]
         "v_mov_b32 v40, v42\n\t"
-        "v_mov_b32 v41, v43\n\t"
+        "v_mov_b32 v41, v43\n"
         "2:\n\t"
         "s_mov_b64 %[left], exec\n\t"
         "s_mov_b64 exec, s[60:61]\n\t"
-        : [left] "=s"(left), "+{v[40:41]}"(key), "+{v[44:45]}"(t)
-        : [entry] "s"(entry), "{v47}"(K.two52_hi), "{v[56:57]}"(K.bias), "{v58}"(K.n_hi),
+        : [left] "=s"(left), "+{v[40:41]}"(key), "+{v[44:45]}"(t) HULK_JGUARD_OUT(G.hits)
+        : [entry] "s"(entry), "{v47}"(K.two52_hi), "{v[56:57]}"(K.bias), "{v58}"(K.n_hi), [gthr] "s"(G.thr),
           [alo] "s"(0x87B0B0FDu), [ahi] "s"(0x27BB2EE6u), [cut] "s"(cut), [p31] "s"(0x3E00000000000000ull /* 2^-31 */)
-        : "v42", "v43", "v46", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55",
-          "s60", "s61", "s62", "s63", "vcc", "scc", "memory");
-#undef HULK_JSTEP
+        : "v42", "v43", "v46", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v60", "v61", "v62", "v63",
+          "s60", "s61", "s62", "s63", "s64", "s65", "vcc", "scc", "memory");
+#undef HULK_JLCG
+#undef HULK_JHALF
     return left;
 }
+#undef HULK_JGUARD_COUNT
+#undef HULK_JGUARD_OUT
 
 // The pool: the slow chains of a wave, kept in four registers per lane — {key (a pair), slot << 20 | t, index into ml.key} in
 // pool position = lane, positions [0, pc) in use, pc wave-uniform.  The index is global and the slot travels with the entry, so
@@ -134,11 +204,11 @@ __device__ __forceinline__ void pool_push(JumpPool &p, unsigned long long m, uin
 }
 // one dense round over the pool (pc >= 1): runs until at most pcut of its chains are live, stores the keys of those that ended
 // and moves the survivors to the front; the positions behind them are unused and take whatever arrives
-__device__ __forceinline__ void pool_round(JumpPool &p, uint32_t *__restrict__ key, const JumpConsts &K, uint32_t pcut) {
+__device__ __forceinline__ void pool_round(JumpPool &p, uint32_t *__restrict__ key, const JumpConsts &K, JumpGuard &G, uint32_t pcut) {
     const unsigned long long entry = lanes_below(p.pc);
     uint64_t k = p.key;
     double t = (double)(p.word & 0xFFFFFu);
-    const unsigned long long left = jump_steps_asm(k, t, K, entry, pcut);
+    const unsigned long long left = jump_steps_asm(k, t, K, G, entry, pcut);
     p.word = (p.word & ~0xFFFFFu) | (uint32_t)(int32_t)t;
     if (lane_in(entry & ~left)) key[p.at] = p.word;
     const uint32_t n = (uint32_t)__popcll(left);
@@ -155,7 +225,8 @@ __device__ __forceinline__ void pool_round(JumpPool &p, uint32_t *__restrict__ k
 // and then hands over the rest, whose state is still in the senders' own registers: cut + pcut <= 64, so it fits.  After its
 // last region the wave drains the pool.  cut == 0 (and the C++ loop, use_c): every round runs to its last chain, no pool.
 __global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_regions, int32_t num_bins, int use_c,
-                                                  uint32_t cut, uint32_t pcut, uint32_t R) {
+                                                  uint32_t cut, uint32_t pcut, uint32_t R, uint32_t guard_thr,
+                                                  unsigned long long *guard_hits) {
     const int lane = lane_id();
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     const uint32_t r0 = wave * R;
@@ -164,6 +235,7 @@ __global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_r
     const double fn = (double)num_bins;
     const JumpConsts K = jump_consts(fn);
     JumpPool pool{0ull, 0u, 0u, 0u};
+    JumpGuard G{guard_thr, 0u};
     for (uint32_t region = r0; region < r1; region++) {
         const uint32_t cnt = ml.cnt[region];
         const uint64_t *xl = ml.x + (size_t)region * ml.rcap;
@@ -183,7 +255,7 @@ __global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_r
             double t = 0.0;                                         // float64(b), b = 0 before the first step
             unsigned long long left;                                // the lanes whose chain is not finished
             if (!use_c) {
-                left = jump_steps_asm(key, t, K, entry, cut);
+                left = jump_steps_asm(key, t, K, G, entry, cut);
             } else {
                 if (idx < cnt) {
                     uint64_t kk = key;
@@ -205,14 +277,17 @@ __global__ __launch_bounds__(256) void k_jump_bin(MinimizerList ml, uint32_t n_r
                 if (pool.pc + (uint32_t)__popcll(left) > 64u) {
                     const unsigned long long head = __ballot(rank_in(left) < 64u - pool.pc) & left;   // its first 64 - pc
                     if (head) pool_push(pool, head, key, word, base + idx);
-                    pool_round(pool, ml.key, K, pcut);
+                    pool_round(pool, ml.key, K, G, pcut);
                     left &= ~head;
                 }
                 pool_push(pool, left, key, word, base + idx);
             }
         }
     }
-    while (pool.pc) pool_round(pool, ml.key, K, 0u);
+    while (pool.pc) pool_round(pool, ml.key, K, G, 0u);
+#ifdef HULK_EXPERIMENTS
+    if (guard_hits && G.hits && lane == 0) atomicAdd(guard_hits, (unsigned long long)G.hits);
+#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -511,19 +586,8 @@ __global__ void k_add_hist(uint32_t *hist, const uint32_t *add, int32_t n) {
 }  // namespace
 
 // ---------------------------------------------------------------------------- host wrappers
-// K1b: jump hash of the list (dense key array); K1c: spectrum ranges in LDS, merged without atomics
-hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParams P, const MinimizerList &ml,
-                                 uint32_t *d_hists, uint32_t *d_slow_list, uint32_t *d_slow_count, hipEvent_t jump_begin,
-                                 hipEvent_t jump_end, hipEvent_t wait_before_spectra, uint32_t *geom) {
-    if (n_reads == 0) return hipSuccess;
-    hipError_t e = hipSuccess;
-    const uint32_t n_regions = (uint32_t)((n_reads + FAST_READS_PER_WAVE - 1) / FAST_READS_PER_WAVE);
-    const uint32_t nblk = (n_regions + 1023) / 1024;
-    prof_mark(s, "k_region_bsum");
-    hipLaunchKernelGGL(k_region_bsum, dim3(nblk), dim3(1024), 0, s, ml.cnt, ml.bsum, ml.dmask, ml.dsum, n_regions);
-    prof_mark(s, "k_region_offsets");
-    hipLaunchKernelGGL(k_region_offsets, dim3(nblk), dim3(1024), 0, s, ml.cnt, ml.bsum, ml.off, n_regions, ml.nib_over, ml.dmask,
-                       ml.dsum, d_slow_list, d_slow_count);
+// k_jump_bin with the settings of the build: the defaults, or in the profiling build the HULK_JUMP_* switches (read once)
+static void launch_jump(hipStream_t s, const MinimizerList &ml, uint32_t n_regions, int32_t num_bins, unsigned long long *guard_hits) {
     // k_jump_bin needs no LDS; a dummy allocation caps its occupancy so that the flush kernels of the
     // previous batch (other stream) find free wave slots next to it
     static int jump_lds = -1;
@@ -537,13 +601,95 @@ hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParam
     if (jump_pcut < 0) { const char *ec = HULK_EXP_ENV("HULK_JUMP_PCUT"); jump_pcut = ec ? atoi(ec) : JUMP_PCUT_DEFAULT; }
     static int jump_regions = -1;
     if (jump_regions < 0) { const char *ec = HULK_EXP_ENV("HULK_JUMP_REGIONS"); jump_regions = ec ? atoi(ec) : JUMP_REGIONS_DEFAULT; if (jump_regions < 1) jump_regions = 1; if (jump_regions > 64) jump_regions = 64; }
+    // (the switch: without the guard an integer quotient is rounded as the shared reciprocal happens to round it — to show that
+    //  the tests of the guard fail)
+    static const uint32_t guard_thr = HULK_EXP_ENV("HULK_JUMP_NO_GUARD") ? 0u : JUMP_GUARD_WINDOW;
     const uint32_t cut = jump_c ? 0u : (uint32_t)jump_cut;
     const uint32_t pcut = std::min<uint32_t>((uint32_t)std::max(jump_pcut, 0), 64u - cut);     // cut + pcut <= 64: see the kernel
     const uint32_t R = (uint32_t)jump_regions;
+    hipLaunchKernelGGL(k_jump_bin, dim3((n_regions + 4 * R - 1) / (4 * R)), dim3(256), (size_t)jump_lds, s, ml, n_regions, num_bins, jump_c,
+                       cut, pcut, R, guard_thr, guard_hits);
+}
+
+#ifdef HULK_EXPERIMENTS
+// The guard counter of the STEP PATH's launches (launch_minimizer_post), profiling build only: one 64-bit device counter per
+// device of the process, made at its first launch there; read and wiped by step_guard_hits (hulk_debug_jump with n == 0)
+static unsigned long long *step_guard_counter() {
+    static unsigned long long *d_hits[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    if (!d_hits[dev] && (hipMalloc((void **)&d_hits[dev], 8) != hipSuccess || hipMemset(d_hits[dev], 0, 8) != hipSuccess)) d_hits[dev] = nullptr;
+    return d_hits[dev];
+}
+// (the caller has synchronised the streams that launched)
+hipError_t step_guard_hits(uint64_t *out) {
+    unsigned long long *d = step_guard_counter();
+    if (!d) return hipErrorOutOfMemory;
+    unsigned long long h = 0;
+    hipError_t e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemset(d, 0, 8);
+    *out = h;
+    return e;
+}
+
+// hulk_debug_jump: `n` values laid out as regions of region_len (the last one shorter), slot 0, through k_jump_bin as the step
+// path launches it; the one allocation `d` holds x [n] | hits (8 B) | key [n], off [regions + 1], cnt [regions] | slot [n]
+hipError_t launch_debug_jump(hipStream_t s, const uint64_t *values, uint64_t n, uint32_t region_len, int32_t num_bins,
+                             uint32_t *bins_out, uint64_t *guard_hits) {
+    const uint32_t n_regions = (uint32_t)((n + region_len - 1) / region_len);
+    std::vector<uint32_t> words((size_t)n + 2 * (size_t)n_regions + 1, 0u);       // key [n] | off [regions + 1] | cnt [regions]
+    uint32_t *h_off = words.data() + n, *h_cnt = h_off + n_regions + 1;
+    for (uint32_t r = 0; r < n_regions; r++) {
+        h_off[r] = r * region_len;
+        h_cnt[r] = (uint32_t)std::min<uint64_t>(region_len, n - (uint64_t)r * region_len);
+    }
+    h_off[n_regions] = (uint32_t)n;
+    uint8_t *d = nullptr;
+    const size_t xb = (size_t)n * 8, wb = words.size() * 4;
+    hipError_t e = hipMalloc((void **)&d, xb + 8 + wb + (size_t)n);
+    if (e != hipSuccess) return e;
+    MinimizerList ml{};
+    ml.x = (uint64_t *)d;
+    unsigned long long *d_hits = (unsigned long long *)(d + xb);
+    ml.key = (uint32_t *)(d + xb + 8); ml.off = ml.key + n; ml.cnt = ml.off + n_regions + 1;
+    ml.slot = d + xb + 8 + wb;
+    ml.rcap = region_len;
+    unsigned long long hits = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(ml.x, values, xb, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d + xb, 0, 8 + wb + (size_t)n, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ml.off, h_off, (size_t)(2 * n_regions + 1) * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) { launch_jump(s, ml, n_regions, num_bins, d_hits); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(words.data(), ml.key, (size_t)n * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hits, d_hits, 8, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    hipFree(d);
+    if (e != hipSuccess) return e;
+    for (uint64_t i = 0; i < n; i++) bins_out[i] = words[i] & 0xFFFFFu;
+    if (guard_hits) *guard_hits = hits;
+    return hipSuccess;
+}
+#endif
+// K1b: jump hash of the list (dense key array); K1c: spectrum ranges in LDS, merged without atomics
+hipError_t launch_minimizer_post(hipStream_t s, uint64_t n_reads, MinimizerParams P, const MinimizerList &ml,
+                                 uint32_t *d_hists, uint32_t *d_slow_list, uint32_t *d_slow_count, hipEvent_t jump_begin,
+                                 hipEvent_t jump_end, hipEvent_t wait_before_spectra, uint32_t *geom) {
+    if (n_reads == 0) return hipSuccess;
+    hipError_t e = hipSuccess;
+    const uint32_t n_regions = (uint32_t)((n_reads + FAST_READS_PER_WAVE - 1) / FAST_READS_PER_WAVE);
+    const uint32_t nblk = (n_regions + 1023) / 1024;
+    prof_mark(s, "k_region_bsum");
+    hipLaunchKernelGGL(k_region_bsum, dim3(nblk), dim3(1024), 0, s, ml.cnt, ml.bsum, ml.dmask, ml.dsum, n_regions);
+    prof_mark(s, "k_region_offsets");
+    hipLaunchKernelGGL(k_region_offsets, dim3(nblk), dim3(1024), 0, s, ml.cnt, ml.bsum, ml.off, n_regions, ml.nib_over, ml.dmask,
+                       ml.dsum, d_slow_list, d_slow_count);
     if (jump_begin) { e = hipEventRecord(jump_begin, s); if (e != hipSuccess) return e; }      // bench.py: k_jump_bin alone
     prof_mark(s, "k_jump_bin");
-    hipLaunchKernelGGL(k_jump_bin, dim3((n_regions + 4 * R - 1) / (4 * R)), dim3(256), (size_t)jump_lds, s, ml, n_regions, P.num_bins, jump_c,
-                       cut, pcut, R);
+#ifdef HULK_EXPERIMENTS
+    launch_jump(s, ml, n_regions, P.num_bins, step_guard_counter());
+#else
+    launch_jump(s, ml, n_regions, P.num_bins, nullptr);
+#endif
     if (jump_end) { e = hipEventRecord(jump_end, s); if (e != hipSuccess) return e; }
     // the kernels below write the spectra of the ring: the flush that last read them has to be done
     if (wait_before_spectra) { e = hipStreamWaitEvent(s, wait_before_spectra, 0); if (e != hipSuccess) return e; }
